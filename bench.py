@@ -9,8 +9,12 @@ mask-and-realign rounds for reads with middle hits).  Headline workload = BASELI
 ("1M synthetic 8 kb reads with 1% chimeras, middle scan enabled") per GPU; reads are sharded
 over ranks with no data-path collective (weak scaling).
 
+A plain run sets up, warms up, times exactly --steps steps (`value`, `ms_per_step`, the per-kernel times and the roofline of
+that region) and prints the line; --dump-outputs DIR also writes what the last timed step returned (dump_outputs).
+Everything below is measured only with --full.
+
 Prints ONE JSON line on rank 0, under 8 KB, numbers only (DESIGN.md section 9 names every key; the unabridged record goes
-to --full-json, default gpurun_out/bench_full.json):
+to --full-json when given):
   roofline     -- the dominant kernel (score-only whole-read scan), timed with HIP events on its launch stream inside the
                   timed region (pc_get_timing); traffic from profiles/<round>_summary.json when that profile was taken with
                   the library now loaded (traffic_measured_in_this_run is always false)
@@ -91,6 +95,37 @@ def one_step(pl, reads, n_check, world, proofs=False, prefilter=False):
     st, et = pl.phase_b(reads, matching)
     hits = pl.phase_c(reads, st, et, matching, prove=proofs, prefilter=prefilter)
     return matching, st, et, hits
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, matching, st, et, hits, prefix=""):
+    """--dump-outputs: what one_step returned, as float64 DIR/<prefix><name>.npy (every value is an integer below 2^53 or the
+    float64 identity itself, so nothing is rounded): the matching sets, every read's start / end trim, the middle hits.  Over
+    DUMP_BYTES in all, the per-read and per-hit arrays keep a fixed, seeded sample of their rows (read_sample / hit_sample
+    hold the row indices kept)."""
+    os.makedirs(path, exist_ok=True)
+    per_read = {"start_trim": st, "end_trim": et}
+    per_hit = {"middle_hit_read": hits.read, "middle_hit_adapter": hits.adapter, "middle_hit_start": hits.start,
+               "middle_hit_end": hits.end, "middle_hit_identity": hits.identity}
+    arrays = {"matching_sets": np.asarray(matching, dtype=np.float64),
+              "middle_hit_rounds_alignments": np.asarray([hits.rounds, hits.alignments], dtype=np.float64)}
+    n_read, n_hit = int(st.numel()), int(hits.read.numel())
+    budget = DUMP_BYTES - (1 << 20)                        # (1 MB for the small arrays and the .npy headers)
+    sample = 8 * (len(per_read) * n_read + len(per_hit) * n_hit) > budget
+    # with the row indices kept as one more array per group
+    rows_bytes = 8 * ((len(per_read) + 1) * n_read + (len(per_hit) + 1) * n_hit)
+    for group, n, name in ((per_read, n_read, "read_sample"), (per_hit, n_hit, "hit_sample")):
+        keep = None
+        if sample:
+            keep = np.sort(np.random.default_rng(12345).choice(n, size=n * budget // rows_bytes, replace=False))
+            arrays[name] = keep.astype(np.float64)
+        for key, t in group.items():
+            a = t.detach().cpu().numpy().astype(np.float64)
+            arrays[key] = a if keep is None else a[keep]
+    for key, a in arrays.items():
+        np.save(os.path.join(path, prefix + key + ".npy"), a)
 
 
 def step_end_trim(pl, reads, n_check):
@@ -1834,8 +1869,12 @@ def main():
     ap.add_argument("--cli-reads", type=int, default=2000, help="reads of the reference-CLI baseline (B1); 0 disables it and the drop-in leg")
     ap.add_argument("--dropin-reads", type=int, default=20000, help="reads of the drop-in leg (unchanged reference Python over the HIP library)")
     ap.add_argument("--dropin-threads", type=int, default=16, help="--threads of the drop-in leg's second run (the first uses 1)")
-    ap.add_argument("--full-json", default=os.environ.get("PC_BENCH_FULL", ""), help="also write the unabridged record here "
-                    "(default: gpurun_out/bench_full.json under the repo)")
+    ap.add_argument("--full-json", default=os.environ.get("PC_BENCH_FULL", ""), help="also write the unabridged record here")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline: repeated regions, "
+                    "the pruned / prefiltered / 2-bit variants, CPU baselines and parity, the reference CLI and drop-in, live "
+                    "counter traffic and the other legs (without it: set up, warm up, time --steps steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step returned to DIR/<name>.npy "
+                    "(float64)")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it starts its own N ranks: the same command re-executed
@@ -1932,89 +1971,93 @@ def main():
     timing = pl.aligner.get_timing()
     pl.aligner.set_timing(False)
 
-    # ---- AFTER it: the same region twice more (run-to-run spread; `value` stays the first region's) --------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, matching, st, et, hits, prefix=("rank%d_" % rank) if world > 1 else "")
+
+    # ---- AFTER it (--full): the same region twice more (run-to-run spread; `value` stays the first region's) ---------
     region_ms = [dt / args.steps * 1e3]
-    for _ in range(max(0, args.repeats - 1)):
+    for _ in range(max(0, args.repeats - 1) if args.full else 0):
         _, dtr, _ = region(args.steps)
         region_ms.append(dtr / args.steps * 1e3)
 
-    # ---- the same steps with the two optional exact prunings (score bound for the identity thresholds:
-    # fewer tracebacks, identical sets / trims / hits).  Reported as an extra field; never `value`.
-    psteps = max(1, min(args.steps, 5))
-    one_step(pl, reads, n_check, world, proofs=True)
-    (_, _, _, hits_p), dt_proofs, _ = region(psteps, proofs=True)
-    same_hits = bool(hits_p.read.numel() == hits.read.numel() and torch.equal(hits_p.read, hits.read) and
-                     torch.equal(hits_p.start, hits.start) and torch.equal(hits_p.end, hits.end))
-
-    # ---- the same steps with the exact bit-parallel prefilter in front of the middle scan (the
-    # alternative the reference's README.md:355-357 names): pairs farther than max_edits(m, threshold) from every
-    # substring are proven non-hits and never reach the DP.  Reported BESIDE the headline, never as `value`.
-    one_step(pl, reads, n_check, world, prefilter=True)
-    pl.aligner.set_timing(True)
-    pl.aligner.get_timing()
-    fsteps = max(1, min(args.steps, 10))
-    (_, st_f, et_f, hits_f), dt_pf, _ = region(fsteps, prefilter=True)
-    timing_pf = pl.aligner.get_timing()
-    pl.aligner.set_timing(False)
-    pf_regions = [dt_pf / fsteps * 1e3]
-    for _ in range(max(0, args.repeats - 1)):          # this variant has a host round trip per step: report its spread too
-        _, dtr, _ = region(fsteps, prefilter=True)
-        pf_regions.append(dtr / fsteps * 1e3)
-    dt_pf = sorted(pf_regions)[len(pf_regions) // 2] * fsteps / 1e3          # the MEDIAN region is the one reported
-    same_hits_f = bool(hits_f.read.numel() == hits.read.numel() and torch.equal(hits_f.read, hits.read) and
-                       torch.equal(hits_f.adapter, hits.adapter) and torch.equal(hits_f.start, hits.start) and
-                       torch.equal(hits_f.end, hits.end) and torch.equal(st_f, st) and torch.equal(et_f, et) and
-                       (hits_f.rounds, hits_f.alignments) == (hits.rounds, hits.alignments))
-
-    # ---- the same step with the reads RESIDENT AT 2 BITS PER BASE (north_star: "2-bit-packed read windows"): the plane
-    # io.pack_reads makes stays in HBM (a quarter of the bytes), the prefilter's seed scan reads it directly
-    # (pc_prefilter_packed), and only the two 150-base end windows of every read and the few reads that survive the
-    # prefilter are ever turned into bytes (pc_unpack_windows).  Beside the headline, never `value`.
     pk_out = None
-    if world == 1 and not args.no_extra:
-        try:
-            from porechop_amd.io import pack_reads
-            from porechop_amd.pipeline import DeviceReads
-            nb_ = int(reads.off[-1].item()) + int(reads.length[-1].item())
-            h_ = reads.arena[:nb_].cpu().numpy()
-            pk_, exc_ = pack_reads(h_, nb_)
-            del h_
-            t0p = time.perf_counter()
-            reads_pk = DeviceReads.packed_only(pl.aligner, torch.from_numpy(pk_).to(dev), nb_,
-                                               torch.from_numpy(exc_).to(dev) if exc_.size else None, reads.off, reads.length,
-                                               end_size=params.end_size)
-            pl.aligner.sync()
-            torch.cuda.synchronize()
-            build_ms = (time.perf_counter() - t0p) * 1e3
-            for _ in range(2):                       # (the first step over a new resident form sizes the library's scratch buffers)
-                one_step(pl, reads_pk, n_check, world, prefilter=True)
-            pl.aligner.set_timing(True)
-            pl.aligner.get_timing()
-            stats0 = dict(pl.stats)
-            barrier()
-            t0p = time.perf_counter()
-            for _ in range(fsteps):
-                _, st_k, et_k, hits_k = one_step(pl, reads_pk, n_check, world, prefilter=True)
-            pl.aligner.sync()
-            barrier()
-            dt_pk = time.perf_counter() - t0p
-            timing_pk = pl.aligner.get_timing()
-            pl.aligner.set_timing(False)
-            same_k = bool(hits_k.read.numel() == hits.read.numel() and torch.equal(hits_k.read, hits.read) and
-                          torch.equal(hits_k.adapter, hits.adapter) and torch.equal(hits_k.start, hits.start) and
-                          torch.equal(hits_k.end, hits.end) and torch.equal(st_k, st) and torch.equal(et_k, et))
-            pk_out = {"reads_per_s": args.reads * fsteps / dt_pk, "ms_per_step": dt_pk / fsteps * 1e3, "same_trims_and_middle_hits": same_k,
-                      "hbm_bytes_resident": int(reads_pk.plane.numel()) + int(reads_pk.ends[0].numel()),
-                      "hbm_bytes_resident_as_bytes": int(reads.arena.numel()),
-                      "bytes_unpacked_per_step": (pl.stats.get("bases_unpacked_after_prefilter", 0) - stats0.get("bases_unpacked_after_prefilter", 0)) // fsteps,
-                      "packed_route_refused": pl.stats.get("packed_route_refused", 0) - stats0.get("packed_route_refused", 0),
-                      "upload_and_end_windows_ms": build_ms,
-                      "kernel_ms_per_step": {k: v[0] / fsteps for k, v in timing_pk.items()},
-                      "seed_scan_ms": timing_pk["seed_scan"][0] / max(1, timing_pk["seed_scan"][1]) if timing_pk["seed_scan"][1] else None,
-                      "seed_scan_plane_gb_per_s": (nb_ / 4 / 1e9) / (timing_pk["seed_scan"][0] / 1e3 / fsteps) if timing_pk["seed_scan"][0] else None}
-            del reads_pk
-        except Exception as e:      # an extra measurement must never break the bench line
-            pk_out = {"failed": repr(e)}
+    if args.full:
+        # ---- the same steps with the two optional exact prunings (score bound for the identity thresholds:
+        # fewer tracebacks, identical sets / trims / hits).  Reported as an extra field; never `value`.
+        psteps = max(1, min(args.steps, 5))
+        one_step(pl, reads, n_check, world, proofs=True)
+        (_, _, _, hits_p), dt_proofs, _ = region(psteps, proofs=True)
+        same_hits = bool(hits_p.read.numel() == hits.read.numel() and torch.equal(hits_p.read, hits.read) and
+                         torch.equal(hits_p.start, hits.start) and torch.equal(hits_p.end, hits.end))
+
+        # ---- the same steps with the exact bit-parallel prefilter in front of the middle scan (the
+        # alternative the reference's README.md:355-357 names): pairs farther than max_edits(m, threshold) from every
+        # substring are proven non-hits and never reach the DP.  Reported BESIDE the headline, never as `value`.
+        one_step(pl, reads, n_check, world, prefilter=True)
+        pl.aligner.set_timing(True)
+        pl.aligner.get_timing()
+        fsteps = max(1, min(args.steps, 10))
+        (_, st_f, et_f, hits_f), dt_pf, _ = region(fsteps, prefilter=True)
+        timing_pf = pl.aligner.get_timing()
+        pl.aligner.set_timing(False)
+        pf_regions = [dt_pf / fsteps * 1e3]
+        for _ in range(max(0, args.repeats - 1)):          # this variant has a host round trip per step: report its spread too
+            _, dtr, _ = region(fsteps, prefilter=True)
+            pf_regions.append(dtr / fsteps * 1e3)
+        dt_pf = sorted(pf_regions)[len(pf_regions) // 2] * fsteps / 1e3          # the MEDIAN region is the one reported
+        same_hits_f = bool(hits_f.read.numel() == hits.read.numel() and torch.equal(hits_f.read, hits.read) and
+                           torch.equal(hits_f.adapter, hits.adapter) and torch.equal(hits_f.start, hits.start) and
+                           torch.equal(hits_f.end, hits.end) and torch.equal(st_f, st) and torch.equal(et_f, et) and
+                           (hits_f.rounds, hits_f.alignments) == (hits.rounds, hits.alignments))
+
+        # ---- the same step with the reads RESIDENT AT 2 BITS PER BASE (north_star: "2-bit-packed read windows"): the plane
+        # io.pack_reads makes stays in HBM (a quarter of the bytes), the prefilter's seed scan reads it directly
+        # (pc_prefilter_packed), and only the two 150-base end windows of every read and the few reads that survive the
+        # prefilter are ever turned into bytes (pc_unpack_windows).  Beside the headline, never `value`.
+        if world == 1 and not args.no_extra:
+            try:
+                from porechop_amd.io import pack_reads
+                from porechop_amd.pipeline import DeviceReads
+                nb_ = int(reads.off[-1].item()) + int(reads.length[-1].item())
+                h_ = reads.arena[:nb_].cpu().numpy()
+                pk_, exc_ = pack_reads(h_, nb_)
+                del h_
+                t0p = time.perf_counter()
+                reads_pk = DeviceReads.packed_only(pl.aligner, torch.from_numpy(pk_).to(dev), nb_,
+                                                   torch.from_numpy(exc_).to(dev) if exc_.size else None, reads.off, reads.length,
+                                                   end_size=params.end_size)
+                pl.aligner.sync()
+                torch.cuda.synchronize()
+                build_ms = (time.perf_counter() - t0p) * 1e3
+                for _ in range(2):                       # (the first step over a new resident form sizes the library's scratch buffers)
+                    one_step(pl, reads_pk, n_check, world, prefilter=True)
+                pl.aligner.set_timing(True)
+                pl.aligner.get_timing()
+                stats0 = dict(pl.stats)
+                barrier()
+                t0p = time.perf_counter()
+                for _ in range(fsteps):
+                    _, st_k, et_k, hits_k = one_step(pl, reads_pk, n_check, world, prefilter=True)
+                pl.aligner.sync()
+                barrier()
+                dt_pk = time.perf_counter() - t0p
+                timing_pk = pl.aligner.get_timing()
+                pl.aligner.set_timing(False)
+                same_k = bool(hits_k.read.numel() == hits.read.numel() and torch.equal(hits_k.read, hits.read) and
+                              torch.equal(hits_k.adapter, hits.adapter) and torch.equal(hits_k.start, hits.start) and
+                              torch.equal(hits_k.end, hits.end) and torch.equal(st_k, st) and torch.equal(et_k, et))
+                pk_out = {"reads_per_s": args.reads * fsteps / dt_pk, "ms_per_step": dt_pk / fsteps * 1e3, "same_trims_and_middle_hits": same_k,
+                          "hbm_bytes_resident": int(reads_pk.plane.numel()) + int(reads_pk.ends[0].numel()),
+                          "hbm_bytes_resident_as_bytes": int(reads.arena.numel()),
+                          "bytes_unpacked_per_step": (pl.stats.get("bases_unpacked_after_prefilter", 0) - stats0.get("bases_unpacked_after_prefilter", 0)) // fsteps,
+                          "packed_route_refused": pl.stats.get("packed_route_refused", 0) - stats0.get("packed_route_refused", 0),
+                          "upload_and_end_windows_ms": build_ms,
+                          "kernel_ms_per_step": {k: v[0] / fsteps for k, v in timing_pk.items()},
+                          "seed_scan_ms": timing_pk["seed_scan"][0] / max(1, timing_pk["seed_scan"][1]) if timing_pk["seed_scan"][1] else None,
+                          "seed_scan_plane_gb_per_s": (nb_ / 4 / 1e9) / (timing_pk["seed_scan"][0] / 1e3 / fsteps) if timing_pk["seed_scan"][0] else None}
+                del reads_pk
+            except Exception as e:      # an extra measurement must never break the bench line
+                pk_out = {"failed": repr(e)}
 
     out = None
     if rank == 0:
@@ -2071,7 +2114,7 @@ def main():
                 # ... and measured IN THIS RUN where the box has rocprofv3: two --pmc passes (one counter each, nothing else enabled)
                 # over a child process that runs two headline steps and nothing else (tools/run_leg.py) -- the guide's recipe,
                 # spawned from here so that the driver's own line carries counters of the library it ran
-                if not args.no_extra and not args.no_live_traffic:
+                if args.full and not args.no_extra and not args.no_live_traffic:
                     live = live_traffic("pc_spec_score" if jit else "scan_kernel")
                     if live:
                         roof["traffic_from_profile"] = roof["traffic"]
@@ -2081,20 +2124,22 @@ def main():
                         roof["traffic_source"] = "this-run (rocprofv3 --pmc FETCH_SIZE, then --pmc WRITE_SIZE, over `python tools/run_leg.py headline 2`, spawned by bench.py)"
         kern_ms = {k: v[0] / args.steps for k, v in timing.items()}
         srt = sorted(region_ms)
-        pf = {"reads_per_s": total_reads * fsteps / dt_pf, "ms_per_step": dt_pf / fsteps * 1e3, "steps": fsteps,
-              "same_trims_and_middle_hits": same_hits_f, "speedup_vs_headline": (dt / args.steps) / (dt_pf / fsteps),
-              "ms_per_step_by_region": pf_regions,
-              "kernel_ms_per_step": {k: v[0] / fsteps for k, v in timing_pf.items()},
-              "pairs_reaching_the_dp_per_step": pl.stats.get("pairs_middle_scanned_after_prefilter", 0) // max(1, fsteps * len(pf_regions) + 1),
-              "pairs_prefiltered_per_step": pl.stats.get("pairs_middle_prefiltered", 0) // max(1, fsteps * len(pf_regions) + 1),
-              "note": "not the headline: every (read, adapter) pair of the middle scan first goes through the exact prefilter -- a hit "
-                      "needs the adapter within max_edits(m, --middle_threshold) unit-cost edits of a substring of the read; that is "
-                      "decided exactly by one HBM-bound pass that finds the exact q-gram seeds such an occurrence must contain, Myers' "
-                      "bit-vector edit distance on the finds -- and only the surviving pairs run the DP; everything else is proven "
-                      "not to be a hit (csrc/pc_prefilter.hip, tests/test_prefilter_bound.py, tests/test_gpu_prefilter.py)"}
-        pf["roofline"] = prefilter_roofline(timing_pf, mean_trim_len, A)
-        if pk_out is not None:
-            pf["reads_resident_at_2_bits_per_base"] = pk_out
+        pf = None
+        if args.full:
+            pf = {"reads_per_s": total_reads * fsteps / dt_pf, "ms_per_step": dt_pf / fsteps * 1e3, "steps": fsteps,
+                  "same_trims_and_middle_hits": same_hits_f, "speedup_vs_headline": (dt / args.steps) / (dt_pf / fsteps),
+                  "ms_per_step_by_region": pf_regions,
+                  "kernel_ms_per_step": {k: v[0] / fsteps for k, v in timing_pf.items()},
+                  "pairs_reaching_the_dp_per_step": pl.stats.get("pairs_middle_scanned_after_prefilter", 0) // max(1, fsteps * len(pf_regions) + 1),
+                  "pairs_prefiltered_per_step": pl.stats.get("pairs_middle_prefiltered", 0) // max(1, fsteps * len(pf_regions) + 1),
+                  "note": "not the headline: every (read, adapter) pair of the middle scan first goes through the exact prefilter -- a hit "
+                          "needs the adapter within max_edits(m, --middle_threshold) unit-cost edits of a substring of the read; that is "
+                          "decided exactly by one HBM-bound pass that finds the exact q-gram seeds such an occurrence must contain, Myers' "
+                          "bit-vector edit distance on the finds -- and only the surviving pairs run the DP; everything else is proven "
+                          "not to be a hit (csrc/pc_prefilter.hip, tests/test_prefilter_bound.py, tests/test_gpu_prefilter.py)"}
+            pf["roofline"] = prefilter_roofline(timing_pf, mean_trim_len, A)
+            if pk_out is not None:
+                pf["reads_resident_at_2_bits_per_base"] = pk_out
         out = {
             "metric": "reads/sec (and read-bp/sec) end+middle adapter scan, 8 kb reads",
             "value": reads_per_s, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -2121,16 +2166,17 @@ def main():
                        "matching_sets": [pl.sets[i].name for i in matching],
                        "middle_hits_per_step": int(hits.read.numel()), "mask_rounds": hits.rounds,
                        "kernel_ms_per_step": kern_ms,
-                       "library_sha1": library_fingerprint(),
-                       "optional_exact_pruning": {"reads_per_s": total_reads * psteps / dt_proofs,
-                                                  "ms_per_step": dt_proofs / psteps * 1e3, "same_middle_hits": same_hits,
-                                                  "note": "not the headline: phase A and the middle scan trace back only "
-                                                          "pairs whose score can still reach the identity threshold "
-                                                          "(DESIGN.md section 7)"},
-                       "exact_prefilter": pf},
+                       "library_sha1": library_fingerprint()},
             "roofline": roof,
         }
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full:
+            out["config"]["optional_exact_pruning"] = {"reads_per_s": total_reads * psteps / dt_proofs,
+                                                       "ms_per_step": dt_proofs / psteps * 1e3, "same_middle_hits": same_hits,
+                                                       "note": "not the headline: phase A and the middle scan trace back only "
+                                                               "pairs whose score can still reach the identity threshold "
+                                                               "(DESIGN.md section 7)"}
+            out["config"]["exact_prefilter"] = pf
+        if args.full and args.cpu_seconds > 0 and world == 1:
             try:
                 out["cpu_baseline"], out["parity"] = cpu_baseline(reads, pl, matching, st, et, hits, args.cpu_seconds, host_cores())
                 out["config"]["speedup_vs_cpu_baseline"] = reads_per_s / out["cpu_baseline"]["value"]
@@ -2141,7 +2187,7 @@ def main():
                 out.setdefault("parity", {})["phase_a_rederived_on_cpu"] = cpu_phase_a_check(reads, pl, host_cores())
             except Exception as e:
                 out.setdefault("parity", {})["phase_a_rederived_on_cpu"] = {"failed": repr(e)}
-        if args.cpu_seconds > 0 and world == 1 and args.cli_reads > 0:
+        if args.full and args.cpu_seconds > 0 and world == 1 and args.cli_reads > 0:
             from tests.ref_cli import staged
             if staged():
                 import shutil
@@ -2177,7 +2223,7 @@ def main():
                     shutil.rmtree(work, ignore_errors=True)
             else:
                 out["cpu_baseline"]["b1_cli"] = {"failed": "no staged reference under oracle/_ref/porechop_ref (make -C oracle ref)"}
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             try:
                 out.setdefault("parity", {})["device_crosscheck"] = device_crosscheck(pl, reads, matching, st, et, dev)
             except Exception as e:
@@ -2186,7 +2232,7 @@ def main():
     del reads, pl
     torch.cuda.empty_cache()
     also = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         # the per-GPU shape of BASELINE configs[4], on EVERY rank (its own barriers / MAX over ranks inside)
         note("leg configs4_per_gpu")
         try:
@@ -2198,7 +2244,7 @@ def main():
                 raise                                    # a rank that fails alone would hang the others' collectives
             also["configs4_per_gpu"] = {"failed": repr(e)}
         torch.cuda.empty_cache()
-    if world > 1 and not args.no_extra:
+    if args.full and world > 1 and not args.no_extra:
         # what N GPUs of one node SHARE is only in these two: BASELINE configs[4] as a fixed total from host memory, and one file
         # in -> one file out over the ranks.  Every rank takes part (collectives inside); a failure ends the job on every rank.
         for name, fn in (("configs4_fixed_total", lambda: leg_fixed_total(dev, args, host_cores(), world, rank, barrier)),
@@ -2209,7 +2255,7 @@ def main():
                 also[name] = r_
             torch.cuda.empty_cache()
     if rank == 0:
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             legs = (("configs1", lambda: leg_configs1(dev, args, host_cores())),
                     ("configs2", lambda: leg_configs2(dev, args, host_cores())),
                     ("ragged_lengths", lambda: leg_ragged(dev, args, host_cores(), out["read_bp_per_s"])),
@@ -2228,13 +2274,13 @@ def main():
                 out["value_incl_h2d"] = also["from_host_memory"]["reads_per_s"]
         if also:
             out["config"]["also_measured"] = also
-        full_path = args.full_json or os.path.join(REPO, "gpurun_out", "bench_full.json")
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(full_path)), exist_ok=True)
-            with open(full_path, "w") as f:
-                json.dump(out, f, indent=1)
-        except Exception:
-            pass
+        if args.full_json:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.full_json)), exist_ok=True)
+                with open(args.full_json, "w") as f:
+                    json.dump(out, f, indent=1)
+            except Exception:
+                pass
         print(json.dumps(compact_line(out), separators=(",", ":")))
     if world > 1:
         dist.barrier()

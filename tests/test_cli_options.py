@@ -1,15 +1,17 @@
 """`python -m porechop_amd` takes the reference's command line: every option of porechop/porechop.py:82-203 with the same name,
-destination, type, default, choices and arity -- introspected from both argparse parsers (only where /root/reference exists).
+destination, type, default, choices and arity -- introspected from both argparse parsers (only where build() staged the reference
+under oracle/_ref/porechop_ref).
 The one intended difference: --threads defaults to 1 (accepted for compatibility; the alignments run on the GPU)."""
 import argparse
 import os
+import shutil
 import sys
 import tempfile
 
 import pytest
 
-REFERENCE = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
+REFERENCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "porechop_ref")
+pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "porechop")), reason="no staged reference (make -C oracle ref)")
 
 
 def _parsers():
@@ -22,8 +24,9 @@ def _parsers():
     argparse.ArgumentParser.parse_args = grab
     old_argv, old_path = sys.argv, list(sys.path)
     try:
-        from tests.golden.make_golden import stage_reference
-        ref = stage_reference(tempfile.mkdtemp(prefix="pc_cli_"))
+        ref = os.path.join(tempfile.mkdtemp(prefix="pc_cli_"), "ref")
+        shutil.copytree(os.path.join(REFERENCE, "porechop"), os.path.join(ref, "porechop"),
+                        ignore=shutil.ignore_patterns("__pycache__"))
         sys.path.insert(0, ref)
         for m in [k for k in sys.modules if k == "porechop" or k.startswith("porechop.")]:
             del sys.modules[m]

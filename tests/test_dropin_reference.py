@@ -1,4 +1,4 @@
-"""porechop_amd.dropin under the UNCHANGED reference Python (only where /root/reference exists):
+"""porechop_amd.dropin under the UNCHANGED reference Python (only where build() staged it under oracle/_ref/porechop_ref):
 the reference CLI runs over its own fixtures with the three phase drivers wrapped; the backend is
 the CPU oracle here (no GPU in this container -- the GPU backend's strings are proven identical
 to the oracle's by tests/test_gpu_parity.py).  Checks: byte-identical output files (md5 from the
@@ -14,10 +14,10 @@ from contextlib import redirect_stderr, redirect_stdout
 
 import pytest
 
-REFERENCE = "/root/reference"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REFERENCE = os.path.join(REPO, "oracle", "_ref", "porechop_ref")          # its Python and fixtures, staged by build()
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
+pytestmark = pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="no staged reference (make -C oracle ref)")
 
 
 class OracleBackend:

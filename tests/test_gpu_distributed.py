@@ -124,7 +124,8 @@ def test_two_ranks_share_one_file_and_each_writes_its_own_span(tmp_path):
 def test_one_rank_launcher_equals_plain_bench():
     """`python -m torch.distributed.run --nproc-per-node 1 bench.py --gpus 1` (the driver's launch line) and plain
     `python bench.py`: the same workload, the same results (matching sets, hits, parity), throughput of the same order."""
-    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "200000", "--cpu-seconds", "0", "--no-extra", "--repeats", "1"]
+    args = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--reads", "200000", "--cpu-seconds", "0", "--no-extra", "--repeats", "1",
+            "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     plain = subprocess.run([sys.executable, "bench.py"] + args, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert plain.returncode == 0, plain.stderr[-2000:]
@@ -151,7 +152,7 @@ def test_two_ranks_on_one_gpu_emit_the_configs4_leg_for_both_ranks():
     and middle hits as the full computation on every rank), both ranks' timed regions, and phase A's check-read shares must
     sum to --check_reads (porechop.py:86)."""
     args = ["--gpus", "2", "--steps", "1", "--warmup", "1", "--reads", "60000", "--reads4", "30000", "--cpu-seconds", "0", "--repeats", "1",
-            "--reads4-total", "100000", "--reads-e2e", "40000"]
+            "--reads4-total", "100000", "--reads-e2e", "40000", "--full"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", PC_DIST_BACKEND="gloo")
     # the PLAIN command: bench.py starts its own two ranks (tests/test_bench_launch_cpu.py covers the launch alone)
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)

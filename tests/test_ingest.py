@@ -1,6 +1,6 @@
 """Host ingest (porechop_amd/csrc/pc_io.cpp) against the reference's own loaders
-(porechop/misc.py load_fasta_or_fastq + NanoporeRead.__init__) on the reference's fixture files when
-the checkout is present, and against a Python restatement of those semantics on generated
+(porechop/misc.py load_fasta_or_fastq + NanoporeRead.__init__) on the reference's fixture files where
+build() staged them under oracle/_ref/porechop_ref, and against a Python restatement of those semantics on generated
 FASTA/FASTQ(.gz) files everywhere."""
 import gzip
 import os
@@ -11,7 +11,7 @@ import pytest
 
 from porechop_amd.io import ReadSet
 
-REFERENCE = "/root/reference"
+REFERENCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "porechop_ref")
 
 
 def python_semantics(path):
@@ -110,7 +110,7 @@ def test_errors(tmp_path):
         ReadSet(trunc)
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference checkout not present")
+@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="no staged reference (make -C oracle ref)")
 def test_against_reference_loaders_on_its_fixtures():
     sys.path.insert(0, REFERENCE)
     for m in [k for k in sys.modules if k == "porechop" or k.startswith("porechop.")]:

@@ -81,17 +81,18 @@ def test_read_blocks_do_not_change_the_outputs(oracle, tmp_path, monkeypatch):
 
 def test_panel_default_is_the_recorded_one_and_agrees_with_the_reference_module():
     """load_panel() uses the recorded panel.json whatever is importable as `porechop` (the tested, benchmarked
-    panel); reading porechop.adapters.ADAPTERS is an explicit opt-in, and where /root/reference exists the two
-    must be the same table."""
+    panel); reading porechop.adapters.ADAPTERS is an explicit opt-in, and where build() staged the reference under
+    oracle/_ref/porechop_ref the two must be the same table."""
     import os
     import sys
     import pytest
     from porechop_amd import panel
     recorded = panel.load_panel()
     assert len(recorded) == 119 and panel.PANEL_SOURCE == "recorded"
-    if not os.path.isdir("/root/reference/porechop"):
-        pytest.skip("reference checkout not present")
-    sys.path.insert(0, "/root/reference")
+    ref = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "porechop_ref")
+    if not os.path.isdir(os.path.join(ref, "porechop")):
+        pytest.skip("no staged reference (make -C oracle ref)")
+    sys.path.insert(0, ref)
     try:
         for m in [k for k in sys.modules if k == "porechop" or k.startswith("porechop.")]:
             del sys.modules[m]
@@ -100,7 +101,7 @@ def test_panel_default_is_the_recorded_one_and_agrees_with_the_reference_module(
         live = panel.load_panel(prefer_reference=True)
         assert panel.PANEL_SOURCE == "reference module"
     finally:
-        sys.path.remove("/root/reference")
+        sys.path.remove(ref)
         for m in [k for k in sys.modules if k == "porechop" or k.startswith("porechop.")]:
             del sys.modules[m]
     assert [(s.name, s.start, s.end) for s in live] == [(s.name, s.start, s.end) for s in recorded]

@@ -4,8 +4,8 @@ splits, writing) against the REFERENCE CLI's own output files on the reference's
 The goldens are the md5s tests/golden/make_golden.py recorded while running the unchanged reference
 (`runs` in tests/golden/ref_calls.json.gz).  The alignments here come from the oracle through the
 Aligner-shaped stand-in of tests/cpu_aligner.py -- this test is about the HOST logic; the same
-runner on the GPU is tests/test_gpu_runner.py.  Needs the fixture files of /root/reference/test, so
-it runs in the build container only."""
+runner on the GPU is tests/test_gpu_runner.py.  Needs the reference's fixture files, which build() stages under
+oracle/_ref/porechop_ref/test where the reference is present."""
 import hashlib
 import os
 
@@ -14,8 +14,8 @@ import pytest
 from tests.cpu_aligner import OracleAligner
 from tests.golden_io import load_ref_calls
 
-REF_TEST = "/root/reference/test"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF_TEST), reason="reference fixtures not present")
+REF_TEST = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "porechop_ref", "test")
+pytestmark = pytest.mark.skipif(not os.path.isdir(REF_TEST), reason="no staged reference fixtures (make -C oracle ref)")
 
 
 def md5_of_outputs(path):

@@ -13,7 +13,7 @@ if [ "${2:-tests}" = tests ]; then
 fi
 [ -x tools/ubench_valu ] && timeout 120 tools/ubench_valu > $OUT/${TAG}_ubench_valu.txt 2>&1
 [ -x tools/ubench_row ] && timeout 120 tools/ubench_row > $OUT/${TAG}_ubench_row.txt 2>&1
-timeout 900 python bench.py --steps 10 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --steps 10 --warmup 3 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
 tail -c 3000 $OUT/${TAG}_bench.json
 if [ "${3:-profile}" = profile ]; then
   timeout 1500 bash tools/profile_round.sh $TAG 400000 2>&1 | tail -30

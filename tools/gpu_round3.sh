@@ -15,7 +15,7 @@ for WHAT in "$@"; do
       PC_CHECK_RANGE=1 PC_JIT_CHECK_RANGE=1 PC_JIT_MIN_CELLS=1 PC_JIT_CACHE_DIR=off timeout 900 python tools/fuzz_parity.py 40 7 > $OUT/${TAG}_fuzz_check_range.txt 2>&1
       tail -4 $OUT/${TAG}_fuzz_check_range.txt ;;
     bench)
-      timeout 900 python bench.py --steps 10 --warmup 3 > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
+      timeout 900 python bench.py --steps 10 --warmup 3 --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; echo "bench rc=$?"
       tail -c 600 $OUT/${TAG}_bench.err; wc -c $OUT/${TAG}_bench.json ;;
     profile:*)
       LEGS=$(echo ${WHAT#profile:} | tr ',' ' ')

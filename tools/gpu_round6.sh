@@ -16,7 +16,7 @@ for WHAT in "$@"; do
       timeout 300 python __graft_entry__.py smoke 2>&1 | tail -1 ;;
     bench*)
       ARGS=$(echo ${WHAT#bench} | tr ':' ' ')
-      ( time timeout 1800 python bench.py $ARGS --full-json $OUT/${TAG}_bench_full.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ) 2>&1 | grep real; echo "bench rc=$?"
+      ( time timeout 1800 python bench.py $ARGS --full --full-json $OUT/${TAG}_bench_full.json > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err ) 2>&1 | grep real; echo "bench rc=$?"
       tail -c 600 $OUT/${TAG}_bench.err; wc -c $OUT/${TAG}_bench.json ;;
     profile:*)
       LEGS=$(echo ${WHAT#profile:} | tr ',' ' ')

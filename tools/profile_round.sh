@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --reads $READS --steps 2 --warmup 1 --cpu-seconds 0 --no-extra"
+CMD="python $ROOT/bench.py --reads $READS --steps 2 --warmup 1 --cpu-seconds 0 --no-extra --full"
 W=/tmp/prof_work; rm -rf $W; mkdir -p $W
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $W/trace -o trace -- $CMD > $OUT/bench_trace.log 2>&1
 find $W/trace -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
@@ -28,7 +28,7 @@ timeout 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_
 CC=$(find $W/VALU -name "*counter_collection.csv" | head -1)
 if [ -n "$CC" ]; then head -1 $CC > $OUT/pmc_VALU.csv; grep -E "pck::|pc_spec" $CC >> $OUT/pmc_VALU.csv; fi
 if [ "${3:-legs}" = legs ]; then
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $W/legs -o trace -- python $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 > $OUT/bench_legs.log 2>&1
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $W/legs -o trace -- python $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --full > $OUT/bench_legs.log 2>&1
   find $W/legs -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats_all_legs.csv \;
 fi
 for f in $OUT/bench_*.log; do tail -1 $f > $f.json; grep -v "^W2\|^I2\|^E2" $f | tail -5 > $f.tail; rm $f; done

@@ -13,7 +13,7 @@ import sys
 
 tag, rnd, reads = sys.argv[1], sys.argv[2], int(sys.argv[3])
 src = os.path.join("gpurun_out", "prof_" + tag)
-out = {"command": "python bench.py --reads %d --steps 2 --warmup 1 --cpu-seconds 0 --no-extra" % reads, "reads_per_gpu": reads,
+out = {"command": "python bench.py --reads %d --steps 2 --warmup 1 --cpu-seconds 0 --no-extra --full" % reads, "reads_per_gpu": reads,
        "kernels": {}}
 for r in csv.DictReader(open(os.path.join(src, "kernel_stats.csv"))):
     name = r["Name"]
@@ -60,7 +60,7 @@ for f in ("kernel_stats.csv", "kernel_trace_scan.csv", "pmc_FETCH_SIZE.csv", "pm
 # the full default run (all legs): per-kernel stats only
 legs = os.path.join(src, "kernel_stats_all_legs.csv")
 if os.path.isfile(legs):
-    out["all_legs"] = {"command": "python bench.py --steps 2 --warmup 1 --cpu-seconds 0", "kernels": {}}
+    out["all_legs"] = {"command": "python bench.py --steps 2 --warmup 1 --cpu-seconds 0 --full", "kernels": {}}
     for r in csv.DictReader(open(legs)):
         if "pck::" in r["Name"] or "pc_spec" in r["Name"]:
             out["all_legs"]["kernels"][r["Name"]] = {"calls": int(r["Calls"]), "avg_ms": float(r["AverageNs"]) / 1e6,
