@@ -11,7 +11,8 @@
 // Identities are the doubles Python sees: (100.0 * matches) / length printed with %f and parsed
 // back, i.e. rounded half-to-even at 6 decimals (porechop/src/alignment.cpp:113-121,
 // nanopore_read.py:476-491); a failed alignment (field 0 == -1) scores 0.0, and so does a score-only record
-// (field 0 == -2) that the exact pruning of phase B proved irrelevant and left untraced (pc_select.hip).
+// (field 0 == -2) that the exact pruning of phase B proved irrelevant and left untraced (pc_select.hip).  A bin
+// entry without a job (-1) or whose pair is not traced is absent from the barcode call, not 0.0.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -71,33 +72,37 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a)
     if (a.nbins <= 0 || !a.call) return;
 
     // ---- barcode call ------------------------------------------------------------------------
-    // bin k has a start entry (job bin_start[k]) and an end entry (job bin_end[k]); a missing entry
-    // scores 0.0.  Python sorts (name, score) lists with a stable descending sort: among equal
-    // scores the entry inserted first wins -- start entries before end entries, bins in order.
+    // bin k has a start entry (job bin_start[k]) and an end entry (job bin_end[k]).  A missing entry (job -1: the bin
+    // has no set on that side, or the set does not match) or an untraced one is ABSENT, as it is absent from the
+    // reference's dicts: never best nor second best; a side without any entry is ('none', 0.0).  Python sorts
+    // (name, score) lists with a stable descending sort: among equal scores the entry inserted first wins -- start
+    // entries before end entries, bins in order.
+    constexpr double kAbsent = -1.0;                   // below every identity (identities are >= 0)
     auto score_of = [&](const int32_t *jobs, int k) -> double {
         const int j = jobs[k];
-        return (j < 0 || untraced(j)) ? 0.0 : full_identity(load_rec(a.records, a.job_off[j] + r));
+        return (j < 0 || untraced(j)) ? kAbsent : full_identity(load_rec(a.records, a.job_off[j] + r));
     };
     int call = -1;
     if (a.require_two) {
-        // best and second best (the next entry of the sorted list) of each side
+        // best and second best (the next entry of the sorted list) of each side; bi = -1: 'none'
         auto best_two = [&](const int32_t *jobs, int &bi, double &bv, double &second) {
-            bi = 0; bv = score_of(jobs, 0); second = -1.0;
-            for (int k = 1; k < a.nbins; ++k) {
+            bi = -1; bv = kAbsent; second = kAbsent;
+            for (int k = 0; k < a.nbins; ++k) {
                 const double v = score_of(jobs, k);
                 if (v > bv) { second = bv; bv = v; bi = k; }
                 else if (v > second) second = v;
             }
-            if (a.nbins < 2) second = 0.0;
+            bv = bv > 0.0 ? bv : 0.0;
+            second = second > 0.0 ? second : 0.0;
         };
         int si, ei; double sv, s2, ev, e2;
         best_two(a.bin_start, si, sv, s2);
         best_two(a.bin_end, ei, ev, e2);
         if (sv >= a.barcode_threshold && ev >= a.barcode_threshold && sv >= s2 + a.barcode_diff && ev >= e2 + a.barcode_diff && si == ei)
-            call = si;
+            call = si;                                 // (both sides 'none': the call is 'none' too)
     } else {
-        int bk = 0; double bv = score_of(a.bin_start, 0);
-        for (int k = 1; k < a.nbins; ++k) { const double v = score_of(a.bin_start, k); if (v > bv) { bv = v; bk = k; } }
+        int bk = -1; double bv = kAbsent;
+        for (int k = 0; k < a.nbins; ++k) { const double v = score_of(a.bin_start, k); if (v > bv) { bv = v; bk = k; } }
         for (int k = 0; k < a.nbins; ++k) { const double v = score_of(a.bin_end, k); if (v > bv) { bv = v; bk = k; } }
         // second best: the best score among the OTHER bins (a bin keeps the better of its two entries)
         double second = 0.0;
@@ -107,7 +112,7 @@ __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a)
             const double v = s > e ? s : e;
             second = v > second ? v : second;
         }
-        if (bv >= a.barcode_threshold && bv >= second + a.barcode_diff) call = bk;
+        if (bk >= 0 && bv >= a.barcode_threshold && bv >= second + a.barcode_diff) call = bk;
     }
     a.call[r] = call;
 }

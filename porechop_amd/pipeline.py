@@ -15,6 +15,7 @@ PyTorch is plumbing here: it owns the HBM buffers and the stream.
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
+import math
 import os
 
 import numpy as np
@@ -161,7 +162,10 @@ def call_barcodes(nbins: int, start_scores: torch.Tensor, end_scores: torch.Tens
     the same rules in pc_phase_b_reduce).
 
     start_scores / end_scores are float64 [R, K]: the full-adapter identity of bin k's start / end
-    sequence (the reference's two dicts, in insertion order; bin names are distinct).
+    sequence (the reference's two dicts, in insertion order; bin names are distinct), NaN where the
+    dict has no entry (a bin without that side's set, or an untraced pair).  A missing entry is left
+    out of the sorted lists, like the reference's: it is never best or second best, and a side with
+    no entry at all is ('none', 0.0).
     -> int64 [R] bin index, or -1 for 'none'.
 
     Ties are resolved as Python's stable sorted(..., reverse=True) resolves them there: among equal
@@ -171,11 +175,14 @@ def call_barcodes(nbins: int, start_scores: torch.Tensor, end_scores: torch.Tens
     none = torch.full((R,), -1, dtype=torch.int64, device=dev)
     if K == 0:
         return none.cpu().numpy()       # best = ('none', 0.0): the call is 'none' whatever the thresholds
+    start_scores = torch.nan_to_num(start_scores, nan=-math.inf)    # absent: below every identity
+    end_scores = torch.nan_to_num(end_scores, nan=-math.inf)
 
     def best_two(x):
         order = torch.sort(x, dim=1, descending=True, stable=True)
         second = order.values[:, 1] if x.shape[1] >= 2 else torch.zeros(R, dtype=x.dtype, device=dev)
-        return order.indices[:, 0], order.values[:, 0], second
+        present = order.values[:, 0] > -math.inf
+        return torch.where(present, order.indices[:, 0], none), torch.clamp(order.values[:, 0], min=0.0), torch.clamp(second, min=0.0)
 
     if require_two_barcodes:
         si, sv, s2 = best_two(start_scores)
@@ -187,12 +194,12 @@ def call_barcodes(nbins: int, start_scores: torch.Tensor, end_scores: torch.Tens
     else:
         both = torch.cat([start_scores, end_scores], dim=1)            # start entries first
         bi, bv, _ = best_two(both)
-        bk = bi % K
+        bk = torch.where(bi >= 0, bi % K, none)
         # second best = best score among the OTHER names (each name keeps its best of start/end)
         per_name = torch.maximum(start_scores, end_scores)
         other = per_name.masked_fill(torch.arange(K, device=dev)[None, :] == bk[:, None], -1.0)
         second = torch.clamp(other.max(dim=1).values, min=0.0)
-        ok = (bv >= barcode_threshold) & (bv >= second + barcode_diff)
+        ok = (bk >= 0) & (bv >= barcode_threshold) & (bv >= second + barcode_diff)
         call = torch.where(ok, bk, none)
     return call.cpu().numpy()
 
@@ -671,9 +678,9 @@ class Pipeline:
             full_for = {i for b in bins for i in b if i is not None}
             out = self.phase_b(reads, matching, full_for=full_for)
             fulls = out[2] if full_for else {}
-            zeros = torch.zeros(R, dtype=torch.float64, device=self.device)
-            S = [fulls.get((b[0], 0), zeros) if b[0] is not None else zeros for b in bins]
-            E = [fulls.get((b[1], 1), zeros) if b[1] is not None else zeros for b in bins]
+            absent = torch.full((R,), math.nan, dtype=torch.float64, device=self.device)
+            S = [fulls.get((b[0], 0), absent) if b[0] is not None else absent for b in bins]
+            E = [fulls.get((b[1], 1), absent) if b[1] is not None else absent for b in bins]
             S = torch.stack(S, dim=1) if bins else torch.zeros((R, 0), dtype=torch.float64, device=self.device)
             E = torch.stack(E, dim=1) if bins else torch.zeros((R, 0), dtype=torch.float64, device=self.device)
             return out[0], out[1], call_barcodes(len(bins), S, E, barcode_threshold, barcode_diff, require_two)
@@ -834,6 +841,7 @@ class Pipeline:
             cands, counts = survivors(True)
             if al.prefilter_overflowed():                # (rare: the seed list overflowed -- the mask above is incomplete)
                 cands, counts = survivors(False)
+                self.stats["prefilter_overflow_reruns"] = self.stats.get("prefilter_overflow_reruns", 0) + 1
             self.stats["pairs_middle_prefiltered"] = self.stats.get("pairs_middle_prefiltered", 0) + B * n
             cjobs, cmeta = [], []
             for g in range(G):
