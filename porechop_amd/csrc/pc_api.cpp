@@ -108,7 +108,7 @@ struct pc_ctx {
     std::vector<int> ad_len, ad_window, ad_span;
     bool panel_dirty = true;
     DevBuf d_ad_codes, d_ad_len, d_ad_window, d_ad_span;
-    DevBuf d_slab, d_fin, d_k1, d_woff2, d_wlen2, d_col0, d_ntot, d_frow, d_fscore, d_tcols, d_perm, d_bucket_cnt, d_bucket_slot[2], d_walk, d_err;
+    DevBuf d_slab, d_fin, d_k1, d_woff2, d_wlen2, d_col0, d_ntot, d_frow, d_fscore, d_tcols, d_perm, d_bucket_cnt, d_bucket_slot[2], d_err;
     // the tile table lives in one of two slots: a new table is built (on the context's own stream) in the slot
     // the scans two tables ago used, so building never waits for the scans in flight on the current one
     DevBuf d_tiles_slot[2], d_runs_slot[2];
@@ -119,20 +119,9 @@ struct pc_ctx {
     int slot = 0;
     // single-pass traced groups of one call (the row classes of phase A / phase B) run two at a time, every
     // other one on the context's own stream, each with its own region of the slab: the tail of one launch
-    // is filled by the next.  (No further streams: HIP maps streams onto four hardware queues, and a fifth
-    // stream would share a queue with -- and serialise behind -- a caller's upload stream; measured.)
+    // is filled by the next.  (No further streams: HIP maps streams onto four hardware queues, and a fifth stream
+    // shared a queue with -- and serialised behind -- a caller's upload stream: the record is named in DESIGN.md section 3.)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    // further streams for the single-pass groups of one call (phase A: four small row classes beside the 24-mers' launch):
-    // OFF unless PC_FORK_STREAMS = 1..3 asks for them.  Built and measured in round 6 (profiles/r06_fork_streams.txt): phase A
-    // alone 3.37 -> 3.19 ms with three, nothing in any leg of bench.py (configs[1] 4.26 against 4.29 ms) -- and HIP maps
-    // streams onto four hardware queues, so with them a caller's upload stream shared a queue with kernels: the step that
-    // streams its reads from host memory went from 98 to 129 ms.
-    static constexpr int kForkStreams = 3;
-#ifndef PC_DEFAULT_FORK_STREAMS
-#define PC_DEFAULT_FORK_STREAMS 0
-#endif
-    hipStream_t fork_stream[kForkStreams] = {nullptr, nullptr, nullptr};
-    hipEvent_t fork_join[kForkStreams] = {nullptr, nullptr, nullptr};
     // host-API staging
     DevBuf d_arena, d_woff, d_wlen, d_out;
     // pc_phase_b_reduce: job / bin tables in two slots (pinned host staging + device copy each); a slot is reused
@@ -640,12 +629,6 @@ bool trace16_plan(const pc_ctx *c, int rows, int cols, pcb::F16Plan *out)
     return true;
 }
 
-bool split_walk()
-{
-    static const bool on = [] { const char *e = getenv("PC_SPLIT_WALK"); return e && *e && *e != '0'; }();
-    return on;
-}
-
 int launch_traced(const pc_ctx *c, pck::ScanArgs &a, const Group &g, int grid, hipStream_t stream)
 {
     pcb::F16Plan fp;
@@ -656,24 +639,8 @@ int launch_traced(const pc_ctx *c, pck::ScanArgs &a, const Group &g, int grid, h
             return (e ? atoi(e) : 0) | ((r && *r && *r != '0') ? 4 : 0);
         }();
         a.debug = dbg;
-        // PC_SPLIT_WALK=1: the tracebacks as launches of their own (pck::walk_kernel), behind the scan of `grid` tiles at a time
-        // -- a walk's slab is its scan block's, so a launch covers at most as many tiles as it has blocks.  The request region
-        // of this group was reserved by pc_scan_device (walk_tiles_of).
-        if (split_walk() && !dbg && a.walk_req) {
-            const int ntiles = a.ntiles;
-            const pck::Tile *tiles = a.tiles;
-            for (int first = 0; first < ntiles; first += grid) {
-                const int cnt = std::min(grid, ntiles - first);
-                a.tiles = tiles + first; a.ntiles = cnt;
-                if (pck::launch_trace16(a, g.rows, cnt, stream) || pck::launch_walk(a, g.rows, cnt, stream)) return 1;
-            }
-            a.tiles = tiles; a.ntiles = ntiles;
-            return 0;
-        }
-        a.walk_req = nullptr; a.walk_req_tile = nullptr;
         return pck::launch_trace16(a, g.rows, grid, stream);
     }
-    a.walk_req = nullptr; a.walk_req_tile = nullptr;
     return pck::launch_trace(a, g.rows, g.pad, grid, stream);
 }
 
@@ -823,15 +790,11 @@ void pc_destroy(pc_ctx *c)
         if (c->red_done[i]) (void)hipEventDestroy(c->red_done[i]);
         if (c->h_red[i]) (void)hipHostFree(c->h_red[i]);
     }
-    for (int k = 0; k < pc_ctx::kForkStreams; ++k) {
-        if (c->fork_stream[k]) { (void)hipStreamSynchronize(c->fork_stream[k]); (void)hipStreamDestroy(c->fork_stream[k]); }
-        if (c->fork_join[k]) (void)hipEventDestroy(c->fork_join[k]);
-    }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
     DevBuf *bufs[] = {&c->d_ad_codes, &c->d_ad_len, &c->d_ad_window, &c->d_ad_span, &c->d_tiles_slot[0], &c->d_tiles_slot[1],
                       &c->d_runs_slot[0], &c->d_runs_slot[1], &c->d_slab, &c->d_fin, &c->d_k1, &c->d_woff2,
-                      &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_walk, &c->d_err, &c->d_arena,
+                      &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
                       &c->d_sd_entries, &c->d_sd_meta, &c->d_sd_eq, &c->d_sd_cand, &c->d_sd_count, &c->d_slow_ad, &c->d_slow_state,
                       &c->d_slow_trace};
@@ -911,7 +874,7 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     size_t slab_bytes = 0, fin_bytes = 0, slab_single = 0, fin_single = 0;
     std::vector<size_t> slab_off(c->groups.size(), 0), fin_off(c->groups.size(), 0), fin_region(c->groups.size(), 0);
     bool any_two = false;
-    int max_chunks = 1, n_single = 0;
+    int n_single = 0;
     for (const Group &g : c->groups) {
         size_t stride;
         const int cols = g.two_pass ? g.max_window + 1 : max_len;
@@ -926,7 +889,6 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         }
         slab_bytes = std::max(slab_bytes, (size_t)grid * stride * 4);
         const int chunks = g.two_pass ? group_chunks_for(c, g, max_len) : 1;
-        max_chunks = std::max(max_chunks, chunks);
         // score pass: chunked launches, and the chunked tails of big jobs (at most 8 chunks x resident waves)
         const int grid1 = grid_for(c, g, std::max<size_t>(g.tile_count * (size_t)chunks, (size_t)c->ncu * 64), 1, nullptr);
         // (x2: the specialised score kernel parks the two halves of a lane separately)
@@ -939,19 +901,6 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         if (c->groups[gi].two_pass) { slab_off[gi] = slab_single; fin_off[gi] = fin_single; }
     slab_bytes += slab_single; fin_bytes += fin_single;
     if ((rc = c->d_slab.ensure(slab_bytes + 256)) || (rc = c->d_fin.ensure(fin_bytes + 256))) return rc;
-    // walk requests (PC_SPLIT_WALK): a region of min(grid, tiles) tiles per group; the groups of a call may run side by side
-    std::vector<size_t> walk_off(c->groups.size(), 0);
-    size_t walk_tiles = 0;
-    if (split_walk()) {
-        for (size_t gi = 0; gi < c->groups.size(); ++gi) {
-            const Group &g = c->groups[gi];
-            const int cols = g.two_pass ? g.max_window + 1 : max_len;
-            const int grid = grid_for(c, g, g.tile_count, cols, nullptr);
-            walk_off[gi] = walk_tiles;
-            walk_tiles += (size_t)std::min<size_t>((size_t)grid, g.tile_count);
-        }
-        if ((rc = c->d_walk.ensure(walk_tiles * (2 * 64 * 16 + 4) + 256))) return rc;
-    }
     // (PC_NO_TRACE_FORK=1 keeps them on one stream: a profile whose per-kernel durations add up to the step)
     static const bool no_trace_fork = [] { const char *e = getenv("PC_NO_TRACE_FORK"); return e && *e && *e != '0'; }();
     const bool fork = n_single >= 2 && stream != c->stream && !no_trace_fork;
@@ -994,40 +943,23 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     }
     size_t unit_at = 0;
     size_t score_launch_no = 0;
-    (void)max_chunks;
-    // The two-pass end scan (end windows, packed-fp16 traced kernel): pass 1 = the traced kernel's own score-only variant over
-    // the very same tiles (five instead of 13.25 packed ops per two cells, no trace slab) leaves every pair's end cell; the pairs
-    // of each segment are ordered by end column (coarsely); pass 2 traces, per pair, only the columns its path can occupy
-    // (plan_kernel: a tile runs min(latest end column, window) columns, a pair traces I + (match I - score) / g + 2 of them).
-    // Exact by the bounds of pc_bounds.h / plan_kernel; PC_NO_TWO_PASS_ENDS=1 keeps the single traced pass.
-    // MEASURED (profiles/r06_two_pass_ends.txt): it does not pay as built.  The score-only variant of the traced kernel still
-    // issues 229 instructions per 28-row column against 465 traced -- half a traced pass before anything is traced -- so only
-    // pairs that end early win (start windows: +6 % on 1 M pairs), end windows lose (their path lies at the window's END: the
-    // second pass runs ~110 warm-up columns to trace 40: -12 %), and small launches pay four launches' latency for one.
-    // OFF unless PC_TWO_PASS_ENDS=1.  What it brought stays in use where the end cells are known anyway (PC_MODE_TRACE_AT, the
-    // traced minority of a pruned phase B): pairs ordered by end column, a tile as long as its latest end cell needs,
-    // every pair's own traced-column bound.
-    static const bool use_t2 = [] { const char *e = getenv("PC_TWO_PASS_ENDS"); return e && *e && *e != '0'; }();
-    static const int t2_min_cols = [] { const char *e = getenv("PC_TWO_PASS_MIN_COLS"); return e && atoi(e) > 0 ? atoi(e) : 96; }();
-    auto two_pass_ends = [&](const Group &g) -> bool {
-        pcb::F16Plan fp;
-        return use_t2 && !g.two_pass && g.rows > 0 && g.nseg > 0 && mode == PC_MODE_TRACE && max_len >= t2_min_cols &&
-               !getenv("PC_DEBUG_TRACE") && !getenv("PC_CHECK_RANGE") && trace16_plan(c, g.rows, max_len, &fp);
-    };
-    // PC_MODE_TRACE_AT: the caller's pairs are taken by end column too (PC_NO_END_ORDER=1: as handed over)
+    // PC_MODE_TRACE_AT (the traced minority of a pruned phase B), where the end cells are the caller's: the pairs of each
+    // segment are taken by end column (coarsely), so that a tile is as long as its latest end cell needs, and every pair traces
+    // only the columns its path can occupy (plan_kernel).  PC_NO_END_ORDER=1: the pairs as handed over.  (The same scheme over
+    // PC_MODE_TRACE end windows, behind a score-only pass of the traced kernel, did not pay: profiles/r06_two_pass_ends.txt.)
     static const bool no_end_order = [] { const char *e = getenv("PC_NO_END_ORDER"); return e && *e && *e != '0'; }();
     auto ordered_trace_at = [&](const Group &g) -> bool {
         pcb::F16Plan fp;
         return !no_end_order && mode == PC_MODE_TRACE_AT && g.two_pass && g.rows > 0 && g.nseg > 0 && trace16_plan(c, g.rows, g.max_window + 1, &fp);
     };
-    bool any_t2 = false;
-    size_t t2_segments = 0;
+    bool any_ordered = false;
+    size_t ordered_segments = 0;         // segments up to the last one of an ordered group: the stride of the bucket counters
     for (const Group &g : c->groups)
-        if (two_pass_ends(g) || ordered_trace_at(g)) { any_t2 = true; t2_segments = std::max(t2_segments, g.seg_begin + g.nseg); }
-    if (any_t2) {
-        if ((rc = c->d_perm.ensure((size_t)npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * t2_segments * pck::kBuckets * 4 + 256))) return rc;
+        if (ordered_trace_at(g)) { any_ordered = true; ordered_segments = std::max(ordered_segments, g.seg_begin + g.nseg); }
+    if (any_ordered) {
+        if ((rc = c->d_perm.ensure((size_t)npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * ordered_segments * pck::kBuckets * 4 + 256))) return rc;
     }
-    if (any_two || any_t2) {
+    if (any_two) {                       // (an ordered group is a two-pass group)
         const size_t n = (size_t)npairs;
         if ((rc = c->d_k1.ensure(k1_ints * 4 + 256)) || (rc = c->d_woff2.ensure(n * 8)) || (rc = c->d_wlen2.ensure(n * 4)) ||
             (rc = c->d_col0.ensure(n * 4)) || (rc = c->d_ntot.ensure(n * 4)) || (rc = c->d_frow.ensure(n * 4)) ||
@@ -1035,30 +967,12 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             return rc;
     }
 
-    // Launch order with PC_FORK_STREAMS = 1..3 (default 0: two streams, table order): the single-pass groups smallest first,
-    // the ones that cannot fill the chip on further streams, the largest last -- a small row class (phase A: 80-470 tiles)
-    // occupies a fraction of the chip for the duration of ONE tile; enqueued behind the 24-mers' 17 000 tiles it waits for
-    // their last round and then runs alone.  Two-pass groups follow in their own order.
-    static const int fork_streams = [] {
-        const char *e = getenv("PC_FORK_STREAMS");
-        int n = (e && *e >= '0' && *e <= '9') ? atoi(e) : PC_DEFAULT_FORK_STREAMS;
-        return n < 0 ? 0 : n > pc_ctx::kForkStreams ? pc_ctx::kForkStreams : n;
-    }();
-    const bool wide_fork = fork_streams > 0;
+    // Launch order: the single-pass groups in table order (side by side on two streams, see pc_ctx), then the two-pass groups
     std::vector<size_t> order;
     for (size_t gi = 0; gi < c->groups.size(); ++gi) if (!c->groups[gi].two_pass) order.push_back(gi);
-    if (fork && wide_fork)
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return c->groups[x].tile_count < c->groups[y].tile_count; });
     for (size_t gi = 0; gi < c->groups.size(); ++gi) if (c->groups[gi].two_pass) order.push_back(gi);
-    bool fork_used[pc_ctx::kForkStreams] = {false, false, false};
     bool ctx_stream_used = false;
-    int small_forked = 0, large_forked = 0;
-    if (fork && wide_fork) {
-        for (int k = 0; k < fork_streams; ++k) {
-            if (!c->fork_stream[k] && hipStreamCreateWithFlags(&c->fork_stream[k], hipStreamNonBlocking) != hipSuccess) return PC_ERR_NO_DEVICE;
-            if (!c->fork_join[k] && hipEventCreateWithFlags(&c->fork_join[k], hipEventDisableTiming) != hipSuccess) return PC_ERR_NO_DEVICE;
-        }
-    }
+    int n_forked = 0;
     for (const size_t gi_ : order) {
         const Group &g = c->groups[gi_];
         pck::ScanArgs a;
@@ -1081,10 +995,6 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         a.ad_span = c->d_ad_span.as<int32_t>();
         a.ad_window = c->d_ad_window.as<int32_t>();
         a.win_by_out = 0;
-        if (split_walk() && walk_tiles) {
-            a.walk_req = (int32_t *)c->d_walk.p + walk_off[gidx] * 128 * 4;
-            a.walk_req_tile = (int32_t *)((char *)c->d_walk.p + walk_tiles * 2048) + walk_off[gidx];
-        }
         size_t stride;
         if (!g.two_pass) {
             a.win_off = d_win_off; a.win_len = d_win_len;
@@ -1093,60 +1003,14 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             const int grid = grid_for(c, g, g.tile_count, max_len, &stride);
             a.slab_stride = (int64_t)stride;
             const int64_t np = group_pairs(g, 0, g.tile_count);
-            // one traced pass, or the two-pass end scan (see above): score pass -> order by end column -> plan -> traced pass
-            auto run_group = [&](hipStream_t ps) -> int {
-                if (!two_pass_ends(g)) return launch_traced(c, a, g, grid, ps);
-                pcb::F16Plan fp;
-                (void)trace16_plan(c, g.rows, max_len, &fp);
-                pck::ScanArgs a1 = a;
-                a1.slab = nullptr; a1.slab_cols = 0; a1.slab_stride = 0;
-                a1.f16_cen = fp.cen; a1.f16_max_cols = fp.max_cols; a1.debug = 0;
-                if (pck::launch_trace16(a1, g.rows, grid, ps, true)) return 1;
-                pck::BucketArgs b;
-                memset(&b, 0, sizeof b);
-                b.records = d_out;
-                b.seg_first = (const int64_t *)c->d_bucket_slot[c->slot].p + g.seg_begin; b.nsegments = (int32_t)g.nseg;
-                b.blocks = (const pck::BucketBlock *)((const char *)c->d_bucket_slot[c->slot].p + c->bucket_blocks_at) + g.blk_begin;
-                b.nblocks = (int32_t)g.nblk;
-                b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBuckets;
-                b.cursors = c->d_bucket_cnt.as<uint32_t>() + (t2_segments + g.seg_begin) * pck::kBuckets;
-                b.perm = c->d_perm.as<int64_t>();
-                if (pck::launch_bucket_pairs(b, ps)) return 1;
-                pck::PlanArgs pl;
-                memset(&pl, 0, sizeof(pl));
-                pl.win_off = d_win_off; pl.win_len = d_win_len;
-                pl.win_off2 = c->d_woff2.as<int64_t>(); pl.win_len2 = c->d_wlen2.as<int32_t>();
-                pl.col02 = c->d_col0.as<int32_t>(); pl.ntot2 = c->d_ntot.as<int32_t>();
-                pl.force_row2 = c->d_frow.as<int32_t>(); pl.force_score2 = c->d_fscore.as<int32_t>();
-                pl.trace_cols2 = c->d_tcols.as<int32_t>();
-                pl.match = c->match; pl.gap_unit = std::min(-c->gap_open, -c->gap_extend);
-                pl.ad_window = c->d_ad_window.as<int32_t>();
-                pl.end_align = 1; pl.end_records = d_out; pl.window_cap = std::max(1, max_len);
-                pl.perm = b.perm;
-                pl.tiles = a.tiles; pl.ntiles = (int32_t)g.tile_count; pl.chunks = 1;
-                pl.err = a.err;
-                if (pck::launch_plan(pl, ps)) return 1;
-                pck::ScanArgs a2 = a;
-                a2.win_off = pl.win_off2; a2.win_len = pl.win_len2; a2.col0 = pl.col02; a2.n_total = pl.ntot2;
-                a2.win_by_out = 1;
-                a2.force_row = pl.force_row2; a2.force_score = pl.force_score2; a2.trace_cols = pl.trace_cols2;
-                a2.perm = b.perm;
-                return launch_traced(c, a2, g, grid, ps);
-            };
             if (fork) {
-                // groups that cannot fill the chip (fewer tiles than resident waves) take the further streams in turn and start
-                // first; the large ones alternate between the caller's stream and the context's as before (several large launches
-                // side by side only take each other's slots: measured 4.6 -> 4.7 ms on phase B's four row classes)
-                int lane;
-                if (wide_fork && (int64_t)g.tile_count < (int64_t)resident_waves(c, g)) lane = 2 + (small_forked++ % fork_streams);
-                else lane = (large_forked++ & 1);
-                hipStream_t ps = lane == 0 ? stream : lane == 1 ? c->stream : c->fork_stream[lane - 2];
-                if (lane == 1 && !ctx_stream_used) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0)); ctx_stream_used = true; }
-                if (lane >= 2 && !fork_used[lane - 2]) { HIP_TRY(hipStreamWaitEvent(ps, c->ev_fork, 0)); fork_used[lane - 2] = true; }
-                if ((rc = run_group(ps))) return PC_ERR_NO_DEVICE;
+                // every other group on the context's own stream
+                hipStream_t ps = (n_forked++ & 1) ? c->stream : stream;
+                if (ps == c->stream && !ctx_stream_used) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0)); ctx_stream_used = true; }
+                if ((rc = launch_traced(c, a, g, grid, ps))) return PC_ERR_NO_DEVICE;
             } else {
                 ScopedTimer tm(c, stream, 2, np);
-                if ((rc = run_group(stream))) return PC_ERR_NO_DEVICE;
+                if ((rc = launch_traced(c, a, g, grid, stream))) return PC_ERR_NO_DEVICE;
             }
         } else {
             const int64_t np = group_pairs(g, 0, g.tile_count);
@@ -1270,7 +1134,7 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
                         b.blocks = (const pck::BucketBlock *)((const char *)c->d_bucket_slot[c->slot].p + c->bucket_blocks_at) + g.blk_begin;
                         b.nblocks = (int32_t)g.nblk;
                         b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBuckets;
-                        b.cursors = c->d_bucket_cnt.as<uint32_t>() + (t2_segments + g.seg_begin) * pck::kBuckets;
+                        b.cursors = c->d_bucket_cnt.as<uint32_t>() + (ordered_segments + g.seg_begin) * pck::kBuckets;
                         b.perm = c->d_perm.as<int64_t>();
                         if (pck::launch_bucket_pairs(b, stream)) return PC_ERR_NO_DEVICE;
                         pl.perm = b.perm; a.perm = b.perm;
@@ -1298,11 +1162,6 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         if (ctx_stream_used) {
             HIP_TRY(hipEventRecord(c->ev_join, c->stream));
             HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
-        }
-        for (int k = 0; k < pc_ctx::kForkStreams; ++k) {
-            if (!fork_used[k]) continue;
-            HIP_TRY(hipEventRecord(c->fork_join[k], c->fork_stream[k]));
-            HIP_TRY(hipStreamWaitEvent(stream, c->fork_join[k], 0));
         }
         if (fork_timed) { (void)hipEventRecord(fork_timer.e1, stream); c->timed.push_back(fork_timer); }
     }

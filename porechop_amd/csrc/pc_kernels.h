@@ -39,8 +39,8 @@ struct ScanArgs {
     const int32_t *n_total;      // [npairs] whole read length                   (null => win_len)
     const int32_t *force_row;    // [npairs] end cell row (1..m) at the window's last column (null => scout)
     const int32_t *force_score;  // [npairs] score the forced cell must reproduce (null => unchecked)
-    const int64_t *perm;         // [npairs] optional: slot s of a tile holds pair perm[s] (a pair of the same segment: the second
-                                 // pass of the two-pass end scan takes a segment's pairs by end column -- bucket_pairs)
+    const int64_t *perm;         // [npairs] optional: slot s of a tile holds pair perm[s] (a pair of the same segment:
+                                 // PC_MODE_TRACE_AT takes a segment's pairs by end column -- bucket_pairs)
     const int32_t *trace_cols;   // [npairs] columns before the end cell the traced path can touch, + 2 (plan_kernel: from the
                                  // pair's own end row and score; null => the adapter's W + 2)
     const uint32_t *ad_codes;    // [nadapters][128] Dna5 codes 0..4
@@ -48,9 +48,6 @@ struct ScanArgs {
     const Tile *tiles;
     int32_t ntiles;
     int32_t *out;                // trace kernels: 8 x int32 per pair; score kernels: 4 x int32 per pair
-    int32_t *walk_req;           // optional: [ntiles][2][64][4] -- the traced kernel leaves every pair's end cell (score, I, J, tie) here
-    int32_t *walk_req_tile;      // and the tile's trace-free prefix, and walk_kernel (one block per tile, a launch of its own) does the
-                                 // traceback + digest: the scan's waves never sit through a walk's dependent loads
     uint32_t *slab;              // trace scratch: [grid][slab_cols][NW][64] dwords
     int64_t slab_stride;         // dwords per block
     int32_t slab_cols;
@@ -256,9 +253,7 @@ inline int pick_rows(int m_lo, int m_hi, bool *pad)
 int launch_trace(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
 int launch_score(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
 bool trace16_has(int rows);
-int launch_walk(const ScanArgs &a, int rows, int ntiles, void *stream);     // the tracebacks of a launch_trace16 launch that left requests
-int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream, bool score_only = false);   // packed-fp16 traced scan (needs a.f16_*);
-                                                                                   // score_only: its first pass (score records, no trace)
+int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream);   // packed-fp16 traced scan (needs a.f16_*)
 
 // The pairs of every segment (a run of output slots that share one adapter) in the order of their end columns, coarsely:
 // perm[segment's slots] = the segment's pairs, bucket (J / kBucketWidth, capped) by bucket; within a bucket in no particular

@@ -650,14 +650,6 @@ __device__ __forceinline__ int hlo(u32 x) { return (int)(float)HV(x).x; }
 __device__ __forceinline__ int hhi(u32 x) { return (int)(float)HV(x).y; }
 constexpr u32 H_NEGINF2 = 0xFC00FC00u, H_POSINF2 = 0x7C007C00u;
 
-// the trace slab is written once and read back only along the path, long after it has left the caches
-#if defined(PC_ABL_NOSTORE)          // timing experiment: the trace words are formed and dropped
-#define SLAB_STORE(p, v) asm volatile("" :: "v"(v))
-#elif !defined(PC_SLAB_TEMPORAL)
-#define SLAB_STORE(p, v) __builtin_nontemporal_store((v), (p))
-#else
-#define SLAB_STORE(p, v) (*(p) = (v))
-#endif
 // K trace words of one lane (K = 4, or the 1..3 of a column's last group) to the block's slab: one buffer store
 typedef u32 u32x2 __attribute__((ext_vector_type(2)));
 typedef u32 u32x3 __attribute__((ext_vector_type(3)));
@@ -665,19 +657,11 @@ typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 template <int K>
 __device__ __forceinline__ void slab_store_group(const __amdgpu_buffer_rsrc_t rsrc, const u32 (&w)[4], const int lane, const int soff)
 {
-#if defined(PC_ABL_NOSTORE)
-    asm volatile("" :: "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]));
-#else
-#ifdef PC_SLAB_TEMPORAL
-    constexpr int AUX = 0;
-#else
     constexpr int AUX = 2;          // nt: written once, read back only along the path, long after it has left the caches
-#endif
     if constexpr (K == 4) { const u32x4 v = {w[0], w[1], w[2], w[3]}; __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, lane * 16, soff, AUX); }
     else if constexpr (K == 3) { const u32x3 v = {w[0], w[1], w[2]}; __builtin_amdgcn_raw_buffer_store_b96(v, rsrc, lane * 12, soff, AUX); }
     else if constexpr (K == 2) { const u32x2 v = {w[0], w[1]}; __builtin_amdgcn_raw_buffer_store_b64(v, rsrc, lane * 8, soff, AUX); }
     else __builtin_amdgcn_raw_buffer_store_b32(w[0], rsrc, lane * 4, soff, AUX);
-#endif
 }
 #define PC_HMAX "v_pk_max_f16 "
 #define PC_HADD "v_pk_add_f16 "
@@ -737,11 +721,7 @@ __device__ __forceinline__ void slab_store_group(const __amdgpu_buffer_rsrc_t rs
 // (max) and err[5] (-min): the host-side range gate (pc_bounds.h f16_plan) asserted on the device; read with
 // pc_debug_value_range.  (-inf only ever enters as the initial H / V of a column and as the scout's mask; it is
 // absorbed by the first max and is not a "value formed".)
-// SCORE: the same kernel as a score-only FIRST pass of the two-pass end scan (PC_MODE_TRACE over end windows, pc_api.cpp):
-// every column runs the bare five-op recurrence of the warm-up loop below plus the packed scout, nothing is traced or stored,
-// and the pair's end cell leaves as a score record (-2, J, I, 0, score, 0, 0, 0) -- what plan_kernel (end_records) turns into
-// the window of the second, traced pass over the columns the path can occupy.
-template <int R, bool CHECK = false, bool SCORE = false>
+template <int R, bool CHECK = false>
 #ifndef PC_T16_WAVES_A
 #define PC_T16_WAVES_A 4
 #endif
@@ -753,11 +733,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
     // different rows are read by one instruction: rows must start in different bank groups.  The stride in 16-byte slots is
     // kept ODD -- consecutive rows then walk through all eight slots of the 32 banks.  (RP + 4 alone made it 32 dwords for
     // the 28-row class of the ligation adapters: every row in the same four banks, each load serialised up to 25 deep.)
-#ifdef PC_VARIANT_STRIDE4
-    constexpr int STRIDE = RP + 4;
-#else
     constexpr int STRIDE = ((RP / 4) % 2 == 0) ? RP + 4 : RP + 8;
-#endif
     constexpr int NW = (R + 3) / 4;          // trace dwords per column per lane
     __shared__ uint16_t lut_lo[256], lut_hi[256];             // byte -> table row offset (dwords) of the lo / hi stream
     __shared__ __attribute__((aligned(16))) u32 s_tab[25 * STRIDE];
@@ -775,10 +751,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
     const int eps = -a.gap_extend, CEN = a.f16_cen;
     const u32 OE2 = __builtin_amdgcn_readfirstlane(hpack2(a.gap_open + eps)), EPS2 = hpack2(eps), NEG2 = H_NEGINF2;
     const u32 TWO2 = 0x40004000u, EIGHT2 = 0x48004800u;
-    u32 *slab = SCORE ? nullptr : a.slab + (int64_t)blockIdx.x * a.slab_stride;
-#ifndef PC_SLAB_OLD
-    const __amdgpu_buffer_rsrc_t slab_rsrc = __builtin_amdgcn_make_buffer_rsrc(slab, 0, SCORE ? 0 : (int)(a.slab_stride * 4), 0x00020000);
-#endif
+    u32 *slab = a.slab + (int64_t)blockIdx.x * a.slab_stride;
+    const __amdgpu_buffer_rsrc_t slab_rsrc = __builtin_amdgcn_make_buffer_rsrc(slab, 0, (int)(a.slab_stride * 4), 0x00020000);
 
     for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
         const Tile tile = a.tiles[t];
@@ -815,7 +789,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
         __syncthreads();
 
         // ---- this lane's two pairs -----------------------------------------------------
-        // (a.perm: the second pass of the two-pass end scan takes the pairs of a segment in the order of their end columns --
+        // (a.perm: PC_MODE_TRACE_AT takes the pairs of a segment in the order of their end columns --
         // slot s of the tile holds pair perm[s] of the same segment)
         const bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
         const int64_t p_lo = (a.perm && have_lo) ? a.perm[tile.out_lo + lane] : tile.out_lo + lane;
@@ -858,7 +832,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
         int nmax = n_lo > n_hi ? n_lo : n_hi;
 #pragma unroll
         for (int s = 32; s >= 1; s >>= 1) { const int o = __shfl_xor(nmax, s); nmax = o > nmax ? o : nmax; }
-        if ((!SCORE && nmax > a.slab_cols) || nmax > a.f16_max_cols) {   // host sized the slab / chose this kernel from a wrong bound
+        if (nmax > a.slab_cols || nmax > a.f16_max_cols) {   // host sized the slab / chose this kernel from a wrong bound
             if (lane == 0) atomicAdd(a.err, 1u);
             nmax = 0;
         }
@@ -994,41 +968,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
                 for (int r = 0; r < R; ++r) fin[r * 64 + lane] = make_uint2(T[r], U[r]);
             }
             const u32 topn = hk_add(top, EPS2);                   // T~(0, j)
-#ifdef PC_ABL_NOTABLE                 // timing experiment: one table row for every column (its loads hoist out of the loop)
-            const uint4 *srow = (const uint4 *)(s_tab);
-#else
             const uint4 *srow = (const uint4 *)(s_tab + trow_j);
-#endif
             u32 d_last = 0, h_last = 0, v_last = 0;
-            if constexpr (SCORE) {
-                // ---- the column, score only: the bare recurrence (as in the warm-up columns above) -------------------
-                u32 dq = top, Tup = topn, Vp = NEG2;
-#pragma clang loop unroll(full)
-                for (int g = 0; g < RP / 4; ++g) {
-                    const uint4 v = srow[g];
-                    const u32 Sg[4] = {v.x, v.y, v.z, v.w};
-#pragma clang loop unroll(full)
-                    for (int k = 0; k < 4; ++k) {
-                        const int r = 4 * g + k;
-                        if (r < R) {
-                            const u32 Hs = hk_maximum(U[r], T[r]);
-                            const u32 d = hk_add(dq, Sg[k]);
-                            const u32 Vs = hk_maximum(Vp, Tup);
-                            const u32 Tn = hk_add(hk_maximum(hk_maximum(d, Hs), Vs), OE2);
-                            dq = T[r]; U[r] = Hs; T[r] = Tn; Tup = Tn; Vp = Vs;
-                        }
-                    }
-                }
-            } else {
-#ifdef PC_SLAB_OLD
-            u32 *trace_dst = slab + ((int64_t)((a.debug & 2) ? 0 : (j - 1)) * NW) * 64 + lane;
-#else
             // this column's trace words leave in groups of four: ONE buffer_store_dwordx4 per 16 rows (address = the block's
             // buffer resource + a scalar column offset + a per-lane constant: no 64-bit address arithmetic per column, a
             // quarter of the store instructions and of the address traffic of a dword per 4 rows)
             const int col_soff = ((a.debug & 2) ? 0 : (j - 1)) * (NW * 256);
             u32 tw[4] = {0u, 0u, 0u, 0u};
-#endif
 
             // ---- the column ------------------------------------------------------------------
             u32 S[RP];
@@ -1094,12 +1040,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
                     if ((pr & 3) == 1) accA = acc;
                     if ((pr & 3) == 3) {
                         const u32 wd = __builtin_amdgcn_perm(accA, acc, 0x06020400u);
-#ifdef PC_SLAB_OLD
-                        SLAB_STORE(&trace_dst[(pr >> 2) * 64], wd);
-#else
                         tw[(pr >> 2) & 3] = wd;
                         if (((pr >> 2) & 3) == 3) slab_store_group<4>(slab_rsrc, tw, lane, col_soff + (pr >> 4) * 1024);
-#endif
                     }
                 }
                 if (r == R - 1) { d_last = dh[r]; h_last = U[r]; v_last = vs; }
@@ -1118,15 +1060,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
                 constexpr int pr = R - 1;
                 const u32 wd = ((pr & 3) == 3) ? __builtin_amdgcn_perm(accA, acc, 0x06020400u)     // rows 4g..4g+3
                                                : __builtin_amdgcn_perm(acc, 0u, 0x0c060c04u);     // a last group of two rows
-#ifdef PC_SLAB_OLD
-                SLAB_STORE(&trace_dst[(pr >> 2) * 64], wd);
-#else
                 tw[(pr >> 2) & 3] = wd;
                 slab_store_group<((NW - 1) & 3) + 1>(slab_rsrc, tw, lane, col_soff + ((NW - 1) >> 2) * 1024);
-#endif
             }
 
-            }   // (traced column)
             if constexpr (CHECK) {
                 // only while a pair still runs: a finished stream re-reads its last bytes and its state is never used
                 if (j <= (n_lo > n_hi ? n_lo : n_hi)) {
@@ -1193,70 +1130,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
         }
         Best b_lo, b_hi;
         load_best(b_lo, b_hi);
-        if constexpr (SCORE) {
-            // the end cell as a score record (what PC_MODE_SCORE leaves: plan_kernel's end_records)
-            if (have_lo) { int4 *o = (int4 *)(a.out + p_lo * TRACE_OUT_INTS); o[0] = make_int4(-2, b_lo.J, b_lo.I, 0); o[1] = make_int4(b_lo.score, 0, 0, 0); }
-            if (have_hi) { int4 *o = (int4 *)(a.out + p_hi * TRACE_OUT_INTS); o[0] = make_int4(-2, b_hi.J, b_hi.I, 0); o[1] = make_int4(b_hi.score, 0, 0, 0); }
-            continue;
-        }
         if (a.debug & 1) {
             if (have_lo) a.out[p_lo * TRACE_OUT_INTS + 4] = b_lo.score;
             if (have_hi) a.out[p_hi * TRACE_OUT_INTS + 4] = b_hi.score;
             continue;
         }
-        if (a.walk_req) {        // the walks run in a launch of their own (walk_kernel): leave the end cells
-            ((int4 *)a.walk_req)[((int64_t)t * 2 + 0) * 64 + lane] = make_int4(b_lo.score, b_lo.I, b_lo.J, b_lo.tie);
-            ((int4 *)a.walk_req)[((int64_t)t * 2 + 1) * 64 + lane] = make_int4(b_hi.score, b_hi.I, b_hi.J, b_hi.tie);
-            if (lane == 0) a.walk_req_tile[t] = notrace_upto;
-            continue;
-        }
-#ifdef PC_SLAB_OLD
-        constexpr bool kGrouped = false;
-#else
-        constexpr bool kGrouped = true;
-#endif
-        traceback_pairs<CHECK, kGrouped>(a, slab, R, NW, lane, b_lo, b_hi, pad_lo, pad_hi,
-                               have_lo, have_hi, n_lo, n_hi, c0_lo, c0_hi, m_lo, m_hi, p_lo, p_hi, notrace_upto,
-                               w_lo, w_hi, tile.adapter_lo, tile.adapter_hi);
+        traceback_pairs<CHECK, true>(a, slab, R, NW, lane, b_lo, b_hi, pad_lo, pad_hi,
+                                     have_lo, have_hi, n_lo, n_hi, c0_lo, c0_hi, m_lo, m_hi, p_lo, p_hi, notrace_upto,
+                                     w_lo, w_hi, tile.adapter_lo, tile.adapter_hi);
     }
 }
 #undef PC_ROW16_FULL
 #undef PC_ROW16_FIRST
 #undef PC_ROW16_NOIND
-
-// ---------------------------------------------------------------------------------------------
-// The tracebacks of a traced launch as a launch of their own: one block (wave) per tile of that launch, tile t's slab at
-// block t's place.  A walk is a chain of dependent loads from memory no cache holds; inside the scan kernel a wave sits
-// through 40-60 of them with its 128 VGPRs of column state idle; here the waves are small (many per SIMD) and run beside the
-// next launch's scan.  Same code (traceback_pairs), same records.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void walk_kernel(ScanArgs a, int rows)
-{
-    const int t = blockIdx.x, lane = threadIdx.x;
-    const Tile tile = a.tiles[t];
-    const int NW = (rows + 3) >> 2;
-    const int m_lo = a.ad_len[tile.adapter_lo], m_hi = a.ad_len[tile.adapter_hi];
-    const int pad_lo = rows - m_lo, pad_hi = rows - m_hi;
-    const bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
-    const int64_t p_lo = (a.perm && have_lo) ? a.perm[tile.out_lo + lane] : tile.out_lo + lane;
-    const int64_t p_hi = (a.perm && have_hi) ? a.perm[tile.out_hi + lane] : tile.out_hi + lane;
-    const int64_t wi_lo = a.win_by_out ? p_lo : tile.win_lo + lane;
-    const int64_t wi_hi = a.win_by_out ? p_hi : tile.win_hi + lane;
-    const int n_lo = have_lo ? a.win_len[wi_lo] : 0, n_hi = have_hi ? a.win_len[wi_hi] : 0;
-    const int c0_lo = (have_lo && a.col0) ? a.col0[p_lo] : 0, c0_hi = (have_hi && a.col0) ? a.col0[p_hi] : 0;
-    const int4 r_lo = ((const int4 *)a.walk_req)[((int64_t)t * 2 + 0) * 64 + lane], r_hi = ((const int4 *)a.walk_req)[((int64_t)t * 2 + 1) * 64 + lane];
-    const Best b_lo = {r_lo.x, r_lo.y, r_lo.z, r_lo.w}, b_hi = {r_hi.x, r_hi.y, r_hi.z, r_hi.w};
-    const u32 *slab = a.slab + (int64_t)t * a.slab_stride;
-    traceback_pairs<false, true>(a, slab, rows, NW, lane, b_lo, b_hi, pad_lo, pad_hi, have_lo, have_hi, n_lo, n_hi, c0_lo, c0_hi, m_lo, m_hi,
-                                 p_lo, p_hi, a.walk_req_tile[t]);
-}
-
-int launch_walk(const ScanArgs &a, int rows, int ntiles, void *stream)
-{
-    if (ntiles <= 0) return 0;
-    hipLaunchKernelGGL(walk_kernel, dim3((unsigned)ntiles), dim3(64), 0, (hipStream_t)stream, a, rows);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Planner between the two passes of a whole-read scan: bounded window ending at the max cell.
@@ -1428,18 +1314,9 @@ bool trace16_has(int rows)
     return false;
 }
 
-int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream, bool score_only)
+int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
-    if (score_only) {
-#define PC_T16S(RR) case RR: hipLaunchKernelGGL((trace16_kernel<RR, false, true>), dim3(grid), dim3(64), 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -2;
-        switch (rows) {
-            PC_T16S(16) PC_T16S(20) PC_T16S(22) PC_T16S(24) PC_T16S(26) PC_T16S(28) PC_T16S(30) PC_T16S(32) PC_T16S(34) PC_T16S(36)
-            PC_T16S(38) PC_T16S(40) PC_T16S(48) PC_T16S(56) PC_T16S(64) PC_T16S(68) PC_T16S(72)
-            default: return -1;
-        }
-#undef PC_T16S
-    }
     if (a.debug & 4) {      // range-checking build, where instantiated
 #define PC_T16C(RR) case RR: hipLaunchKernelGGL((trace16_kernel<RR, true>), dim3(grid), dim3(64), 0, s, a); return hipGetLastError() == hipSuccess ? 0 : -2;
         switch (rows) {
