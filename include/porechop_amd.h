@@ -196,6 +196,46 @@ int pc_phase_b_reduce_masked(pc_ctx *ctx, const int32_t *d_records, int64_t n, i
                              double barcode_threshold, double barcode_diff, int require_two_barcodes,
                              int32_t *d_call, const uint64_t *d_traced_mask, void *stream);
 
+#define PC_EXPLAIN_INTS 12
+/* WHY pc_phase_b_reduce trimmed and called a read as it did: the per-read data the reference keeps in
+ * start_adapter_alignments / end_adapter_alignments and best / second-best barcodes (nanopore_read.py:178-183,200-205,
+ * 399-416), as arrays.  Every input means what it means for pc_phase_b_reduce[_masked]: record layout, job order, side,
+ * absent bins (-1), untraced pairs (d_traced_mask, may be NULL), -1 / -2 records read as "no alignment", identities as
+ * the %f-rounded doubles.  Two passes over the same records:
+ *
+ * SUMMARY pass (d_hit_first == NULL) writes d_summary[n][PC_EXPLAIN_INTS] and d_bscore[n][4]:
+ *   [0], [1]   start and end trim -- equal to what pc_phase_b_reduce writes
+ *   [2], [3]   number of qualifying start / end alignments: aligned identity > end_threshold, read_end - read_start >=
+ *              min_trim_size, and read_end != end_size (start side) / read_start != 0 (end side)
+ *   [4], [5]   deciding start / end job: the FIRST job in job order whose trim equals the read's trim; -1 when no
+ *              alignment raised the trim above 0
+ *   [6], [7]   best and second-best start bin, [8], [9] the same for the end side; -1 = 'none'
+ *   [10], [11] reserved, 0
+ *   d_bscore   the full-adapter identities of [6] .. [9], 0.0 beside a -1
+ * Best and second best are the first two entries of Python's stable descending sort of that side's PRESENT entries:
+ * among equal scores the earlier bin wins; a side with fewer than one / two present entries gives -1 with 0.0; an
+ * absent (bin job -1) or untraced entry is never listed, while a present failed alignment is listed with 0.0.
+ * nbins <= 0: [6] .. [9] are -1 and the scores 0.0.
+ *
+ * FILL pass (d_hit_first given: [n + 1], the exclusive prefix sum of [2] + [3] over the reads, with the total in
+ * entry n) reads d_summary (field [2]) and writes read r's qualifying alignments to rows d_hit_first[r] ... of
+ * d_hits[total][6]: its start alignments in job order, then its end alignments in job order -- the order the reference
+ * appends them.  A row is {job, read_start, read_end (exclusive), matches, aligned_len, full_len}; the two identities
+ * of the reference's tuple are 100 * matches / aligned_len and / full_len, rounded like every identity here.  A row
+ * beyond d_hit_first[r + 1] is not written.  d_bscore may be NULL in this pass.
+ * Alignment: d_records, d_summary and d_bscore must be 16-byte aligned (rows are read and written 16 bytes at a time),
+ * d_hits 8-byte aligned.
+ *
+ * Under the exact pruning below the non-deciding alignments and the second-best barcode are deliberately left
+ * untraced: full lists need records in which every pair is traced.  Host arrays are copied before the call returns;
+ * asynchronous on `stream`. */
+int pc_phase_b_explain(pc_ctx *ctx, const int32_t *d_records, int64_t n, int njobs,
+                       const int64_t *job_record_offset, const int32_t *job_side, int end_size,
+                       int min_trim_size, int extra_end_trim, double end_threshold, int nbins,
+                       const int32_t *bin_start_job, const int32_t *bin_end_job,
+                       const uint64_t *d_traced_mask, int32_t *d_summary, double *d_bscore,
+                       const int64_t *d_hit_first, int32_t *d_hits, void *stream);
+
 /* Exact pruning of phase B: of the ~200 end-window alignments a barcoded read gets, two or three decide its trims and
  * its barcode call; a score-only pass (PC_MODE_SCORE, 5 instead of 13.25 packed operations per two cells, no trace)
  * gives every alignment's end cell and score, and those bound what the alignment can contribute (the bounds and

@@ -7,9 +7,10 @@ import sys
 from .runner import Options, UsageError, run
 
 
-def main(argv=None):
+def build_parser(prog="porechop_amd"):
+    """The reference's option set (tests/test_cli_options.py compares it with porechop/porechop.py:85-185)."""
     d = Options()
-    p = argparse.ArgumentParser(prog="porechop_amd", description="MI355X adapter trimming with Porechop's semantics")
+    p = argparse.ArgumentParser(prog=prog, description="MI355X adapter trimming with Porechop's semantics")
     p.add_argument("-i", "--input", required=True)
     p.add_argument("-o", "--output")
     p.add_argument("--format", choices=["auto", "fasta", "fastq", "fasta.gz", "fastq.gz"], default=d.format)
@@ -37,7 +38,15 @@ def main(argv=None):
     # porechop.py:182-183 prints its bare version number and wrappers compare the whole line: exactly that, nothing after it
     # (the build string of this package is pc_version() / `python -c "import porechop_amd; print(porechop_amd.load_library().pc_version())"`)
     p.add_argument("--version", action="version", version="0.2.4")
-    a = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    run_cli(build_parser().parse_args(argv))
+
+
+def run_cli(a, **run_kw):
+    """Everything after the parsing: options, the run (run_kw: further keywords of runner.run), the summary lines."""
     try:
         scheme = tuple(int(x) for x in a.scoring_scheme.split(","))
     except ValueError:
@@ -60,7 +69,7 @@ def main(argv=None):
         device = "cuda:%d" % local
         dist.init_process_group(os.environ.get("PC_DIST_BACKEND", "nccl"))
     try:
-        res = run(a.input, output=a.output, barcode_dir=a.barcode_dir, options=opts, device=device)
+        res = run(a.input, output=a.output, barcode_dir=a.barcode_dir, options=opts, device=device, **run_kw)
     except (UsageError, ValueError) as e:
         sys.exit(str(e))
     except RuntimeError as e:                 # no GPU / no HIP library: there is no CPU path to fall back to

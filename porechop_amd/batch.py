@@ -195,6 +195,49 @@ class Aligner:
                                                 traced_mask.data_ptr() if traced_mask is not None else None, ctypes.c_void_p(s)),
               "pc_phase_b_reduce")
 
+    def phase_b_explain(self, records, n, job_record_offset, job_side, end_size, min_trim_size, extra_end_trim,
+                        end_threshold, bins=None, traced_mask=None):
+        """The per-read reasons behind phase_b_reduce (pc_phase_b_explain, both passes): same records, tables and
+        conventions.  -> (summary int32[n, 12], bscore float64[n, 4], hit_first int64[n + 1], hits int32[total, 6]) CUDA
+        tensors; the layout is documented in include/porechop_amd.h.  The prefix sum between the passes is a torch
+        cumsum; its total is the call's one host round trip.  Everything -- both launches, the allocations, the cumsum --
+        runs on torch's current stream, which is what orders the passes."""
+        import torch
+        assert records.is_cuda and records.dtype == torch.int32 and records.is_contiguous()
+        n = int(n)
+        dev = records.device
+        off = np.ascontiguousarray(job_record_offset, dtype=np.int64)
+        side = np.ascontiguousarray(job_side, dtype=np.int32)
+        assert off.shape[0] == side.shape[0]
+        if side.shape[0] and n:
+            assert int(off.min()) >= 0 and int(off.max()) + n <= int(records.shape[0]), "job records outside the record tensor"
+        nb = 0 if bins is None else len(bins)
+        bs = np.ascontiguousarray([b[0] for b in bins] if nb else [0], dtype=np.int32)
+        be = np.ascontiguousarray([b[1] for b in bins] if nb else [0], dtype=np.int32)
+        if traced_mask is not None:
+            assert traced_mask.is_cuda and traced_mask.dtype == torch.int64 and traced_mask.is_contiguous()
+            assert tuple(traced_mask.shape) == (len(side), (n + 63) // 64)
+        s = torch.cuda.current_stream().cuda_stream
+        summary = torch.zeros((n, 12), dtype=torch.int32, device=dev)
+        bscore = torch.zeros((n, 4), dtype=torch.float64, device=dev)
+        hit_first = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+
+        def launch(first, hits):
+            check(self.lib.pc_phase_b_explain(self._ctx, records.data_ptr(), n, len(side), off.ctypes.data, side.ctypes.data,
+                                              int(end_size), int(min_trim_size), int(extra_end_trim), float(end_threshold),
+                                              nb, bs.ctypes.data, be.ctypes.data,
+                                              traced_mask.data_ptr() if traced_mask is not None else None,
+                                              summary.data_ptr(), bscore.data_ptr(), first.data_ptr() if first is not None else None,
+                                              hits.data_ptr() if hits is not None else None, ctypes.c_void_p(s)),
+                  "pc_phase_b_explain")
+        launch(None, None)
+        torch.cumsum(summary[:, 2].to(torch.int64) + summary[:, 3].to(torch.int64), 0, out=hit_first[1:])
+        total = int(hit_first[-1].item()) if n else 0
+        hits = torch.zeros((total, 6), dtype=torch.int32, device=dev)
+        if total:
+            launch(hit_first, hits)
+        return summary, bscore, hit_first, hits
+
     def phase_b_select(self, records, n, job_off, job_side, job_len, job_calls, start_len, end_len, end_size, min_trim_size,
                        extra_end_trim, end_threshold, rnd, call_level, call_level_diff, mask_out, counts, mask_prev=None,
                        start_trim=None, end_trim=None, best_full=None, ub_trim_out=None, ub_full_out=None, stream=None):

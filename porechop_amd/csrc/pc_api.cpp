@@ -1289,6 +1289,66 @@ int pc_phase_b_reduce_masked(pc_ctx *c, const int32_t *d_records, int64_t n, int
     return PC_OK;
 }
 
+int pc_phase_b_explain(pc_ctx *c, const int32_t *d_records, int64_t n, int njobs, const int64_t *job_record_offset,
+                       const int32_t *job_side, int end_size, int min_trim_size, int extra_end_trim, double end_threshold,
+                       int nbins, const int32_t *bin_start_job, const int32_t *bin_end_job, const uint64_t *d_traced_mask,
+                       int32_t *d_summary, double *d_bscore, const int64_t *d_hit_first, int32_t *d_hits, void *stream_v)
+{
+    static_assert(PC_EXPLAIN_INTS == pck::EXPLAIN_INTS, "the header and the kernel disagree on the summary layout");
+    if (!c || n < 0 || njobs < 0 || nbins < 0) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    const bool fill = d_hit_first != nullptr;
+    if (!d_summary || (!fill && !d_bscore) || (njobs > 0 && (!d_records || !job_record_offset || !job_side))) return PC_ERR_BAD_ARG;
+    if (nbins > 0 && (!bin_start_job || !bin_end_job)) return PC_ERR_BAD_ARG;
+    for (int k = 0; k < nbins; ++k)
+        if (bin_start_job[k] >= njobs || bin_end_job[k] >= njobs) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    // tables, staged like pc_phase_b_reduce's (the same two slots): [njobs] int64 record offsets, then as int32
+    // job_side[njobs], bin_start[nbins], bin_end[nbins], job_sbin[njobs], job_ebin[njobs]
+    c->red_slot ^= 1;
+    const int sl = c->red_slot;
+    HIP_TRY(hipEventSynchronize(c->red_done[sl]));
+    const size_t off_bytes = ((size_t)std::max(njobs, 1) * 8 + 15) / 16 * 16;
+    const size_t tab_ints = 3 * (size_t)njobs + 2 * (size_t)nbins;
+    const size_t total = off_bytes + (tab_ints + 4) * 4;
+    if (c->h_red_cap[sl] < total) {
+        if (c->h_red[sl]) { (void)hipHostFree(c->h_red[sl]); c->h_red[sl] = nullptr; c->h_red_cap[sl] = 0; }
+        HIP_TRY(hipHostMalloc(&c->h_red[sl], total * 2, hipHostMallocDefault));
+        c->h_red_cap[sl] = total * 2;
+    }
+    int rc = c->d_red_slot[sl].ensure(total);
+    if (rc) return rc;
+    char *h = (char *)c->h_red[sl];
+    if (njobs > 0) memcpy(h, job_record_offset, (size_t)njobs * 8);
+    int32_t *tab = (int32_t *)(h + off_bytes);
+    if (njobs > 0) memcpy(tab, job_side, (size_t)njobs * 4);
+    int32_t *h_bs = tab + njobs, *h_be = h_bs + nbins, *h_sbin = h_be + nbins, *h_ebin = h_sbin + njobs;
+    // job -> bin, so that the kernel meets every barcode entry in its one walk over the jobs; a job that is the entry of
+    // two bins on one side has no inverse (the kernel walks the bins instead)
+    bool invertible = true;
+    for (int j = 0; j < njobs; ++j) h_sbin[j] = h_ebin[j] = -1;
+    for (int k = 0; k < nbins; ++k) {
+        h_bs[k] = bin_start_job[k]; h_be[k] = bin_end_job[k];
+        if (h_bs[k] >= 0) { if (h_sbin[h_bs[k]] >= 0) invertible = false; h_sbin[h_bs[k]] = k; }
+        if (h_be[k] >= 0) { if (h_ebin[h_be[k]] >= 0) invertible = false; h_ebin[h_be[k]] = k; }
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_red_slot[sl].p, h, total, hipMemcpyHostToDevice, stream));
+    pck::ExplainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.records = d_records; a.n = n; a.njobs = njobs;
+    a.job_off = c->d_red_slot[sl].as<int64_t>();
+    a.job_side = (const int32_t *)((char *)c->d_red_slot[sl].p + off_bytes);
+    a.end_size = end_size; a.min_trim_size = min_trim_size; a.extra_end_trim = extra_end_trim; a.end_threshold = end_threshold;
+    a.nbins = nbins; a.bin_start = a.job_side + njobs; a.bin_end = a.bin_start + nbins;
+    if (invertible && nbins > 0) { a.job_sbin = a.bin_end + nbins; a.job_ebin = a.job_sbin + njobs; }
+    a.traced_mask = (const unsigned long long *)d_traced_mask; a.mask_words = (n + 63) / 64;
+    a.summary = d_summary; a.bscore = d_bscore; a.hit_first = d_hit_first; a.hits = d_hits;
+    if (pck::launch_explain(a, stream)) return PC_ERR_NO_DEVICE;
+    HIP_TRY(hipEventRecord(c->red_done[sl], stream));
+    return PC_OK;
+}
+
 int pc_phase_b_select(pc_ctx *c, const int32_t *d_records, int64_t n, int njobs, const int64_t *d_job_record_offset,
                       const int32_t *d_job_side, const int32_t *d_job_adapter_len, const int32_t *d_job_calls,
                       const int32_t *d_start_len, const int32_t *d_end_len, int end_size, int min_trim_size,

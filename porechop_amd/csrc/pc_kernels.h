@@ -116,6 +116,31 @@ struct ReduceArgs {
                                              // 94 % of the records are score records the reduction would only skip)
 };
 int launch_reduce(const ReduceArgs &a, void *stream);
+
+// the per-read reasons behind that reduction (pc_explain.hip): the same records and tables as ReduceArgs
+constexpr int EXPLAIN_INTS = 12;     // PC_EXPLAIN_INTS: summary ints per read
+constexpr int EXPLAIN_HIT_INTS = 6;  // job, read_start, read_end (exclusive), matches, aligned_len, full_len
+struct ExplainArgs {
+    const int32_t *records;
+    int64_t n;
+    int32_t njobs;
+    const int64_t *job_off;
+    const int32_t *job_side;
+    int32_t end_size, min_trim_size, extra_end_trim;
+    double end_threshold;
+    int32_t nbins;
+    const int32_t *bin_start, *bin_end;      // [nbins] job of the bin's start / end entry, or -1 (device)
+    const int32_t *job_sbin, *job_ebin;      // [njobs] the inverse: the bin whose start / end entry job j is, or -1; NULL when a
+                                             // job serves two bins of one side (the kernel then walks bin_start / bin_end)
+    const unsigned long long *traced_mask;   // as ReduceArgs
+    int64_t mask_words;
+    int32_t *summary;                        // [n][EXPLAIN_INTS]: written by the summary pass, field 2 read by the fill pass
+    double *bscore;                          // [n][4] (summary pass)
+    const int64_t *hit_first;                // NULL: summary pass; else [n + 1], the fill pass
+    int32_t *hits;                           // [hit_first[n]][EXPLAIN_HIT_INTS]
+};
+int launch_explain(const ExplainArgs &a, void *stream);
+
 int launch_copy_windows(const uint8_t *arena, const int64_t *src_off, const int32_t *len, int64_t n, uint8_t *dst,
                         const int64_t *dst_off, int pad, void *stream);
 

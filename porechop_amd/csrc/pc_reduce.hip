@@ -17,32 +17,9 @@
 #include <stdint.h>
 
 #include "pc_kernels.h"
+#include "pc_record.h"
 
 namespace pck {
-
-namespace {
-
-struct Rec { int32_t rs, re, as, ae, score, matches, aligned_len, full_len; };
-
-__device__ __forceinline__ Rec load_rec(const int32_t *base, int64_t idx)
-{
-    const int4 a = ((const int4 *)(base + idx * TRACE_OUT_INTS))[0];
-    const int4 b = ((const int4 *)(base + idx * TRACE_OUT_INTS))[1];
-    return {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-}
-
-__device__ __forceinline__ double identity(int matches, int len)
-{
-    const double x = (100.0 * (double)matches) / (double)len;      // 0/0 -> NaN: compares false, like Python's nan
-    return rint(x * 1e6) / 1e6;
-}
-
-__device__ __forceinline__ double full_identity(const Rec &r)
-{
-    return r.rs < 0 ? 0.0 : identity(r.matches, r.full_len);
-}
-
-}  // namespace
 
 __global__ __launch_bounds__(256) void reduce_kernel(ReduceArgs a)
 {

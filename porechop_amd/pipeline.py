@@ -121,6 +121,18 @@ class MiddleHits:
     alignments: int = 0
 
 
+@dataclass
+class EndExplain:
+    """Why phase B trimmed and called each read as it did (Pipeline.phase_b_explain; the layout of the tensors is that of
+    pc_phase_b_explain, include/porechop_amd.h)."""
+    summary: torch.Tensor     # int32 [R, 12]   trims, numbers of qualifying alignments, deciding jobs, best / second-best bins
+    bscore: torch.Tensor      # float64 [R, 4]  full identities of the four bins of summary[:, 6:10]
+    hit_first: torch.Tensor   # int64 [R + 1]   read r's qualifying alignments are hits[hit_first[r] : hit_first[r + 1]]
+    hits: torch.Tensor        # int32 [H, 6]    job, read_start, read_end (exclusive), matches, aligned_len, full_len
+    jobs: List[Tuple[int, int]] = field(default_factory=list)     # job -> (side: 0 start / 1 end, index into Pipeline.sets)
+    bins: Optional[list] = None                                   # the bins the call was made over, or None
+
+
 def _round6(x):
     """float("%f" % x) for non-negative doubles: the value Python parses back from the C side's six printed decimals.
     The quotient is a TRUE division by a one-element device tensor: `tensor / 1e6` with a Python scalar is evaluated by
@@ -762,6 +774,104 @@ class Pipeline:
                 end_trim = torch.where(cond, torch.maximum(end_trim, (p.end_size - rs) + p.extra_end_trim), end_trim)
         self.stats["pairs_end"] += sum(int(j[1].shape[0]) for j in jobs)
         return (start_trim, end_trim, fulls) if full_for else (start_trim, end_trim)
+
+    def phase_b_explain(self, reads: DeviceReads, matching: List[int], bins=None, barcode_threshold: float = 75.0,
+                        barcode_diff: float = 5.0, require_two: bool = False):
+        """Phase B with its reasons kept: -> (start_trim, end_trim int32[R], call -- numpy int64[R] as phase_b_demux gives it,
+        or None without bins --, EndExplain).  The trims and the call are the ones phase_b / phase_b_demux return.
+
+        This route runs phase B with EVERY pair traced (prune=False).  Under the exact pruning only the alignments that can
+        decide a trim or a call are traced -- the non-deciding alignments and the second-best barcode are deliberately left
+        as score records -- so the full lists of qualifying alignments and the second-best scores do not exist there.
+        The per-read pass is a library kernel (pc_phase_b_explain); an injected test aligner without it takes the equivalent
+        torch formulation, as phase_b does for the trims."""
+        R = reads.n
+        p = self.p
+        dev = self.device
+        jobs, where = self._phase_b_jobs(reads, matching)
+        J = len(jobs)
+        call = None
+        if bins is not None:
+            job_of = {(si, side): k for k, (side, si) in enumerate(where)}
+            jb = [(job_of.get((b[0], 0), -1) if b[0] is not None else -1,
+                   job_of.get((b[1], 1), -1) if b[1] is not None else -1) for b in bins]
+            call = np.full(R, -1, dtype=np.int64)
+        if not jobs or not R:
+            summary = torch.zeros((R, 12), dtype=torch.int32, device=dev)
+            summary[:, 4:10] = -1
+            ex = EndExplain(summary, torch.zeros((R, 4), dtype=torch.float64, device=dev),
+                            torch.zeros(R + 1, dtype=torch.int64, device=dev), torch.zeros((0, 6), dtype=torch.int32, device=dev),
+                            list(where), bins)
+            return summary[:, 0].contiguous(), summary[:, 1].contiguous(), call, ex
+        sides = [w[0] for w in where]
+        outs, out, rec_off = self._scan_jobs(self._ends_arena(reads), jobs, MODE_TRACE, p.end_size, with_layout=True)
+        self.stats["pairs_end"] += J * R
+        if hasattr(self.aligner, "phase_b_explain"):
+            summary, bscore, hit_first, hits = self.aligner.phase_b_explain(
+                out, R, rec_off, sides, p.end_size, p.min_trim_size, p.extra_end_trim, p.end_threshold, bins=jb if bins else None)
+            if bins:
+                st = torch.zeros(R, dtype=torch.int32, device=dev)
+                et = torch.zeros(R, dtype=torch.int32, device=dev)
+                c = torch.full((R,), -1, dtype=torch.int32, device=dev)
+                self.aligner.phase_b_reduce(out, R, rec_off, sides, p.end_size, p.min_trim_size, p.extra_end_trim, p.end_threshold,
+                                            st, et, bins=jb, barcode_threshold=barcode_threshold, barcode_diff=barcode_diff,
+                                            require_two=require_two, call=c)
+                call = c.to(torch.int64).cpu().numpy()
+        else:
+            summary, bscore, hit_first, hits, S, E = self._explain_torch(torch.stack(outs), sides, jb if bins else [])
+            if bins:
+                call = call_barcodes(len(bins), S, E, barcode_threshold, barcode_diff, require_two)
+        ex = EndExplain(summary, bscore, hit_first, hits, list(where), bins)
+        return summary[:, 0].contiguous(), summary[:, 1].contiguous(), call, ex
+
+    def _explain_torch(self, rec, sides, jb):
+        """pc_phase_b_explain's contract in torch expressions, for aligners without the kernel (the CPU stand-in of the tests).
+        rec [J, R, 8] -> (summary, bscore, hit_first, hits, S, E); S / E float64 [R, K]: the bins' start / end identities,
+        NaN where absent (call_barcodes' input)."""
+        p = self.p
+        dev = self.device
+        J, R = int(rec.shape[0]), int(rec.shape[1])
+        full, partial = _identities(rec)
+        ok = rec[:, :, 0] >= 0                                         # -1 / -2: no alignment
+        full = torch.where(ok, full, torch.zeros_like(full))
+        rs, re = rec[:, :, 0], rec[:, :, 1] + 1
+        is_end = torch.tensor([bool(s) for s in sides], dtype=torch.bool, device=dev)[:, None]
+        qual = ok & (partial > p.end_threshold) & ((re - rs) >= p.min_trim_size) & torch.where(is_end, rs != 0, re != p.end_size)
+        trim = torch.where(is_end, (p.end_size - rs) + p.extra_end_trim, re + p.extra_end_trim)
+        summary = torch.zeros((R, 12), dtype=torch.int32, device=dev)
+        for col, side_rows in ((0, ~is_end), (1, is_end)):
+            q = qual & side_rows
+            t = torch.where(q, trim, torch.zeros_like(trim))
+            best = torch.clamp(t.max(dim=0).values, min=0)
+            decides = q & (t == best[None, :]) & (best[None, :] > 0)
+            summary[:, col] = best
+            summary[:, 2 + col] = q.sum(dim=0)
+            summary[:, 4 + col] = torch.where(decides.any(dim=0), decides.to(torch.int32).argmax(dim=0), torch.full_like(best, -1))
+        # rows: per read, its start alignments in job order, then its end alignments in job order
+        order = [j for j, s in enumerate(sides) if s == 0] + [j for j, s in enumerate(sides) if s != 0]
+        order_t = torch.tensor(order, dtype=torch.int64, device=dev)
+        at = torch.nonzero(qual[order_t].t())                           # (read, position in `order`), row-major
+        hr, hj = at[:, 0], order_t[at[:, 1]]
+        hits = torch.stack([hj.to(torch.int32), rs[hj, hr], re[hj, hr], rec[hj, hr, 5], rec[hj, hr, 6], rec[hj, hr, 7]], dim=1) \
+            if at.shape[0] else torch.zeros((0, 6), dtype=torch.int32, device=dev)
+        hit_first = torch.zeros(R + 1, dtype=torch.int64, device=dev)
+        hit_first[1:] = torch.cumsum(summary[:, 2].to(torch.int64) + summary[:, 3].to(torch.int64), 0)
+        # barcodes: the first two entries of the stable descending sort of each side's present entries
+        K = len(jb)
+        bscore = torch.zeros((R, 4), dtype=torch.float64, device=dev)
+        summary[:, 6:10] = -1
+        absent = torch.full((R,), math.nan, dtype=torch.float64, device=dev)
+        S = torch.stack([full[b[0]] if b[0] >= 0 else absent for b in jb], dim=1) if K else torch.zeros((R, 0), dtype=torch.float64, device=dev)
+        E = torch.stack([full[b[1]] if b[1] >= 0 else absent for b in jb], dim=1) if K else torch.zeros((R, 0), dtype=torch.float64, device=dev)
+        for col, x in ((0, S), (1, E)):
+            if not K:
+                break
+            srt = torch.sort(torch.nan_to_num(x, nan=-math.inf), dim=1, descending=True, stable=True)
+            for rank in range(min(2, K)):
+                present = srt.values[:, rank] > -math.inf
+                summary[:, 6 + 2 * col + rank] = torch.where(present, srt.indices[:, rank], torch.full_like(srt.indices[:, rank], -1))
+                bscore[:, 2 * col + rank] = torch.where(present, srt.values[:, rank], torch.zeros_like(srt.values[:, rank]))
+        return summary, bscore, hit_first, hits, S, E
 
     # ------------------------------------------------------------------------------------------
     def middle_adapter_list(self, matching: List[int]):

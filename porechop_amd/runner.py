@@ -77,6 +77,109 @@ class RunResult:
     # [first_read, first_read + local_reads) of the n_reads of the file; everywhere else first_read = 0, local_reads = n_reads
     first_read: int = 0
     local_reads: Optional[int] = None
+    explain: Optional["RunExplain"] = None                       # run(..., report=PATH): why every read was trimmed and called
+
+
+@dataclass
+class RunExplain:
+    """Host arrays behind the per-read report of run(..., report=PATH), for the reads of the run in input order.  The first
+    four are pc_phase_b_explain's outputs (include/porechop_amd.h); the middle hits are those of phase C."""
+    summary: np.ndarray                      # int32 [R, 12]
+    bscore: np.ndarray                       # float64 [R, 4]
+    hit_first: np.ndarray                    # int64 [R + 1]
+    hits: np.ndarray                         # int32 [H, 6]: job, read_start, read_end, matches, aligned_len, full_len
+    job_side: List[int]                      # job -> 0 (start) / 1 (end)
+    job_set: List[str]                       # job -> name of its adapter set
+    bin_names: Optional[List[str]]           # None when not demultiplexing
+    middle_first: np.ndarray                 # int64 [R + 1]
+    middle: np.ndarray                       # int64 [M, 3]: adapter (index into middle_names), read_start, read_end -- trimmed-read
+    middle_identity: np.ndarray              # float64 [M]     coordinates, discovery order
+    middle_names: List[str]
+    albacore: Optional[List[Optional[str]]] = None
+    calls: Optional[List[str]] = None        # the final call, after the Albacore rule
+
+    @staticmethod
+    def identity(matches, length):
+        """The %f-rounded identity the reference parses from a record with these fields."""
+        return float("%f" % ((100.0 * matches) / length)) if length else float("nan")
+
+    def end_alignments(self, r):
+        """-> (start list, end list) of (set name, full identity, aligned identity, read_start, read_end): the tuples of the
+        reference's start_adapter_alignments / end_adapter_alignments, with the set's name for the set."""
+        out = ([], [])
+        for j, rs, re, m, al, fl in self.hits[int(self.hit_first[r]):int(self.hit_first[r + 1])].tolist():
+            out[self.job_side[j]].append((self.job_set[j], self.identity(m, fl), self.identity(m, al), rs, re))
+        return out
+
+    def barcodes(self, r):
+        """-> ((best start name, identity), (second), (best end), (second)); 'none' / 0.0 as in the reference."""
+        return tuple((self.bin_names[k] if k >= 0 else "none", float(v))
+                     for k, v in zip(self.summary[r, 6:10].tolist(), self.bscore[r].tolist()))
+
+    def middle_hits(self, r):
+        """-> [(adapter name, read_start, read_end, full identity)] in discovery order."""
+        a, b = int(self.middle_first[r]), int(self.middle_first[r + 1])
+        return [(self.middle_names[ad], s_, e_, float(v)) for (ad, s_, e_), v in zip(self.middle[a:b].tolist(), self.middle_identity[a:b].tolist())]
+
+
+REPORT_COLUMNS = ["name", "length", "start_trim", "end_trim", "start_alignments", "end_alignments", "middle_hits",
+                  "best_start_barcode", "best_start_identity", "second_start_barcode", "second_start_identity",
+                  "best_end_barcode", "best_end_identity", "second_end_barcode", "second_end_identity", "albacore_call", "barcode_call"]
+
+
+def report_header():
+    return "#" + "\t".join(REPORT_COLUMNS) + "\n"
+
+
+def report_rows(ex: RunExplain, names, lengths):
+    """The report's rows for the reads of `ex` (TSV; list columns ';'-joined, '.' when empty or not applicable)."""
+    rows = []
+    for r in range(ex.summary.shape[0]):
+        starts, ends = ex.end_alignments(r)
+        fmt_end = lambda xs: ";".join("%s|%.6f|%.6f|%d|%d" % x for x in xs) or "."
+        mids = ";".join("%s|%d|%d|%.6f" % x for x in ex.middle_hits(r)) or "."
+        cols = [names[r].replace("\t", " "), str(int(lengths[r])), str(int(ex.summary[r, 0])), str(int(ex.summary[r, 1])),
+                fmt_end(starts), fmt_end(ends), mids]
+        if ex.bin_names is None:
+            cols += ["."] * 10
+        else:
+            for name, v in ex.barcodes(r):
+                cols += [name, "%.6f" % v]
+            alb = ex.albacore[r] if ex.albacore is not None else None
+            cols += [alb if alb is not None else ".", ex.calls[r]]
+        rows.append("\t".join(cols) + "\n")
+    return "".join(rows)
+
+
+def _chain(firsts, tables):
+    """Consecutive blocks of a prefix-indexed table as one: firsts[k] (exclusive prefix sums, n_k + 1 entries) index the rows
+    of tables[k] -> (first [sum n_k + 1], rows)."""
+    out, base = [np.zeros(1, dtype=np.int64)], 0
+    for f in firsts:
+        out.append(f[1:] + base)
+        base += int(f[-1])
+    return np.concatenate(out), np.concatenate(tables)
+
+
+def _host_explain(parts, R, pl, match_idx, hits_h, hits_id, bin_names, albacore, calls):
+    """RunExplain of R reads from the EndExplain of every block (in order) and the run's middle hits (hits_h [H, 4]: read,
+    adapter, start, end; hits_id [H]), both already on the host or moved here."""
+    if parts:
+        summary = np.concatenate([e.summary.cpu().numpy() for e in parts])
+        bscore = np.concatenate([e.bscore.cpu().numpy() for e in parts])
+        hit_first, hits = _chain([e.hit_first.cpu().numpy() for e in parts], [e.hits.cpu().numpy() for e in parts])
+        jobs = parts[0].jobs
+    else:
+        summary = np.zeros((R, 12), dtype=np.int32)
+        summary[:, 4:10] = -1
+        bscore = np.zeros((R, 4), dtype=np.float64)
+        hits, hit_first, jobs = np.zeros((0, 6), dtype=np.int32), np.zeros(R + 1, dtype=np.int64), []
+    order = np.argsort(hits_h[:, 0], kind="stable")                  # per read, in discovery order
+    middle_first = np.zeros(R + 1, dtype=np.int64)
+    np.cumsum(np.bincount(hits_h[:, 0], minlength=R), out=middle_first[1:])
+    return RunExplain(summary, bscore, hit_first, hits, [side for side, _ in jobs], [pl.sets[si].name for _, si in jobs], bin_names,
+                      middle_first, hits_h[order][:, 1:4], hits_id[order],
+                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, calls)
 
 
 # (read, adapter) pairs one block of phases B / C may hold at a time: 8 ints each, a few copies -> a few GB of HBM
@@ -261,9 +364,11 @@ def _find_sets(pl, panel, reads, check_idx, opts, barcode_dir, sharded=False):
     return matching, [index_of[id(s)] for s in matching], orientation
 
 
-def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None):
+def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None):
     """Phases B (+ barcode calls) and C for R resident reads -> (start_trim, end_trim [device int32], bin index per
-    read [numpy int64, -1 = none], MiddleHits or None, bin names)."""
+    read [numpy int64, -1 = none], MiddleHits or None, bin names).
+    explain: a list that receives the EndExplain of every block; phase B then runs with every pair traced
+    (Pipeline.phase_b_explain) -- the same trims and calls."""
     dev = pl.device
     start_trim = torch.zeros(R, dtype=torch.int32, device=dev)
     end_trim = torch.zeros(R, dtype=torch.int32, device=dev)
@@ -287,7 +392,13 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
         for b0 in range(0, R, block):
             b1 = min(R, b0 + block)
             sub = reads if (b0 == 0 and b1 == R) else DeviceReads(reads.arena, reads.off[b0:b1], reads.length[b0:b1])
-            if check_barcodes:
+            if explain is not None:
+                st_b, et_b, ci_b, ex_b = pl.phase_b_explain(sub, match_idx, bins if check_barcodes else None, opts.barcode_threshold,
+                                                            opts.barcode_diff, opts.require_two_barcodes)
+                explain.append(ex_b)
+                if check_barcodes:
+                    ci_parts.append(ci_b)
+            elif check_barcodes:
                 st_b, et_b, ci_b = pl.phase_b_demux(sub, match_idx, bins, opts.barcode_threshold, opts.barcode_diff,
                                                     opts.require_two_barcodes)
                 ci_parts.append(ci_b)
@@ -316,6 +427,20 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
                 hits = MiddleHits(*(torch.empty(0, dtype=dt, device=dev) for dt in
                                     (torch.int64, torch.int32, torch.int32, torch.int32, torch.float64)))
     return start_trim, end_trim, ci, hits, names
+
+
+def _concat_explain(blocks):
+    """One RunExplain for the reads of several consecutive blocks."""
+    if len(blocks) == 1:
+        return blocks[0]
+    cat = lambda name: np.concatenate([getattr(b, name) for b in blocks])
+    hit_first, hits = _chain([b.hit_first for b in blocks], [b.hits for b in blocks])
+    middle_first, middle = _chain([b.middle_first for b in blocks], [b.middle for b in blocks])
+    b0 = next((b for b in blocks if b.job_set), blocks[0])
+    return RunExplain(cat("summary"), cat("bscore"), hit_first, hits, b0.job_side, b0.job_set, b0.bin_names,
+                      middle_first, middle, cat("middle_identity"), b0.middle_names,
+                      None if b0.albacore is None else [a for b in blocks for a in b.albacore],
+                      None if b0.calls is None else [c for b in blocks for c in b.calls])
 
 
 def _plan_pieces(opts, lengths, st, et, h, calls, barcode_dir, discard_middle, matching, pl, match_idx):
@@ -375,13 +500,14 @@ def _stream_block_bytes():
 
 
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
-                 adapter_panel: List[AdapterSet] = None, block_bytes: int = None) -> Optional[RunResult]:
+                 adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
     Phase A and the set-level rules run once, on the first block, which must hold the check reads.  Everything after
     that is per read in Porechop (phases B and C, barcode calls, splitting, naming), so the output files are the ones
     run() writes.  Plain FASTA files (cut where a line begins with '>') and the gzip forms of both stream the same way.
+    report: the per-read report of run(), appended block after block (the same bytes as a whole run's).
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
@@ -538,7 +664,11 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     lt.start(); wt.start()
     st_all, et_all, calls_all = [], [], []
     matching = match_idx = orientation = None
+    report_fh, ex_blocks = None, []
     try:
+        if report is not None:
+            report_fh = open(report, "w")
+            report_fh.write(report_header())
         rs = first
         while rs is not None:
             if failure:
@@ -554,7 +684,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 matching, match_idx, orientation = _find_sets(pl, panel, reads, check_idx, opts, barcode_dir)
                 res.matching_sets = [s.name for s in matching]
                 res.barcode_orientation = orientation
-            start_trim, end_trim, ci, hits, _ = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation)
+            ex_parts = [] if report is not None else None
+            start_trim, end_trim, ci, hits, _ = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts)
             if hasattr(pl.aligner, "sync"):
                 pl.aligner.sync()
             if hits is not None and hits.read.numel():
@@ -568,6 +699,11 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 names_all = _barcode_bin_names(pl, match_idx, orientation)
                 calls = [names_all[k] if k >= 0 else "none" for k in ci]
                 calls_all.extend(calls)
+            if report is not None:
+                hid = hits.identity.cpu().numpy() if h.shape[0] else np.zeros(0, dtype=np.float64)
+                ex = _host_explain(ex_parts, R, pl, match_idx, h, hid, names_all if barcode_dir is not None else None, None, calls)
+                report_fh.write(report_rows(ex, [rs.name(i) for i in range(R)], rs.lengths))
+                ex_blocks.append(ex)
             pr, ps_, pn_, num, tlen, n_split = _plan_pieces(opts, rs.lengths, st, et, h, calls, barcode_dir, discard_middle,
                                                            matching, pl, match_idx)
             res.middle_hit_reads += n_split
@@ -593,10 +729,14 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
             pl.close()
         if gz_in is not None:
             gz_in.close()
+        if report_fh is not None:
+            report_fh.close()
+    if report is not None and ex_blocks:
+        res.explain = _concat_explain(ex_blocks)
     if failure:
         # a streamed run that fails part-way (a later block that cannot be parsed, a full disk) has already written the
         # earlier blocks: a whole-file run would have written nothing, so nothing is left behind here either
-        for path in list(paths):
+        for path in list(paths) + ([report] if report is not None else []):
             try:
                 if path and path != "-" and os.path.isfile(path):
                     os.remove(path)
@@ -833,9 +973,14 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
-        adapter_panel: List[AdapterSet] = None) -> RunResult:
+        adapter_panel: List[AdapterSet] = None, report: str = None) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
+
+    report=PATH writes the per-read explain report (REPORT_COLUMNS: the qualifying end alignments, the barcode scores and
+    the middle hits behind every trim and call, one TSV row per read in input order) and fills RunResult.explain.  Phase B
+    then runs with every pair traced (Pipeline.phase_b_explain); trims, calls and output files are the same bytes as
+    without it.  Not available in a sharded run.
 
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
@@ -855,10 +1000,13 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     input_path = str(input_path)
 
     import torch.distributed as dist
+    if report is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        raise UsageError("Error: the per-read report is not available in a sharded run (one process per GPU): run it in a single process")
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)):
-        streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel)
+        streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
+                                report=report)
         if streamed is not None:
             return streamed
 
@@ -915,7 +1063,8 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         lap("phase_a", sync=True)
 
         calls = None
-        start_trim, end_trim, ci, hits, names = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap)
+        ex_parts = [] if report is not None else None
+        start_trim, end_trim, ci, hits, names = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain=ex_parts)
         if hasattr(pl.aligner, "sync"):
             pl.aligner.sync()
 
@@ -942,6 +1091,14 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
             if albacore is not None:                               # nanopore_read.py:468-473
                 calls = [c if (a is None or a == c) else "none" for c, a in zip(calls, albacore)]
         res.start_trim, res.end_trim, res.barcode_calls = st, et, calls
+        if report is not None:
+            hid = hits.identity.cpu().numpy() if h.shape[0] else np.zeros(0, dtype=np.float64)
+            res.explain = _host_explain(ex_parts, R, pl, match_idx, h, hid, names_all if barcode_dir is not None else None,
+                                        albacore, calls)
+            with open(report, "w") as fh:
+                fh.write(report_header())
+                fh.write(report_rows(res.explain, [rs.name(i) for i in range(R)], rs.lengths))
+            lap("report")
 
         # ---- which pieces of which reads -------------------------------------------------
         fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
