@@ -8,9 +8,9 @@ instead of per-read Python objects:
                                             and barcode calls read off the path)  -> io.ReadSet (C++)
   phase A + rules    porechop.py:286-327, 374-390, 330-371, 410-436              -> Pipeline.phase_a, panel.py
   phase B            porechop.py:438-514 + nanopore_read.py:166-208              -> Pipeline.phase_b
-  barcode calls      nanopore_read.py:399-473 (determine_barcode)                -> call_barcodes (tensor ops)
+  barcode calls      nanopore_read.py:399-473 (determine_barcode)                -> pipeline.call_barcodes     
   phase C            porechop.py:533-595 + nanopore_read.py:210-243              -> Pipeline.phase_c
-  pieces to write    nanopore_read.py:56-147 (trim slices, split parts, naming)  -> plan_output (numpy)
+  pieces to write    nanopore_read.py:56-147 (trim slices, split parts, naming)  -> _plan_pieces (numpy)
   writing            porechop.py:607-734                                         -> ReadSet.write (C++)
 
 The alignments come from the GPU library only (Pipeline's default aligner); output files are
@@ -19,8 +19,6 @@ per-read dumps (verbosity >= 1 in the reference) are not reproduced: run() retur
 """
 import os
 import re
-import shutil
-import tempfile
 import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
@@ -31,8 +29,7 @@ import torch
 from . import panel as panel_rules
 from .distributed import gather_in_order, reduce_presence, shard_by_bases
 from .io import GzStream, ReadSet, gz_finish
-from .pipeline import AdapterSet, DeviceReads, Pipeline, ScanParams, trimmed_interval
-from .pipeline import call_barcodes as _call_barcodes
+from .pipeline import AdapterSet, DeviceReads, MiddleHits, Pipeline, ScanParams, trimmed_interval
 
 
 @dataclass
@@ -161,9 +158,10 @@ def _chain(firsts, tables):
     return np.concatenate(out), np.concatenate(tables)
 
 
-def _host_explain(parts, R, pl, match_idx, hits_h, hits_id, bin_names, albacore, calls):
-    """RunExplain of R reads from the EndExplain of every block (in order) and the run's middle hits (hits_h [H, 4]: read,
-    adapter, start, end; hits_id [H]), both already on the host or moved here."""
+def _host_explain(parts, R, pl, match_idx, sc, albacore):
+    """RunExplain of R reads from the EndExplain of every block (in order) and the host results of their scan (sc: _Scan, with
+    the middle hits' identities)."""
+    hits_h, hits_id = sc.hits, sc.identity
     if parts:
         summary = np.concatenate([e.summary.cpu().numpy() for e in parts])
         bscore = np.concatenate([e.bscore.cpu().numpy() for e in parts])
@@ -177,9 +175,9 @@ def _host_explain(parts, R, pl, match_idx, hits_h, hits_id, bin_names, albacore,
     order = np.argsort(hits_h[:, 0], kind="stable")                  # per read, in discovery order
     middle_first = np.zeros(R + 1, dtype=np.int64)
     np.cumsum(np.bincount(hits_h[:, 0], minlength=R), out=middle_first[1:])
-    return RunExplain(summary, bscore, hit_first, hits, [side for side, _ in jobs], [pl.sets[si].name for _, si in jobs], bin_names,
+    return RunExplain(summary, bscore, hit_first, hits, [side for side, _ in jobs], [pl.sets[si].name for _, si in jobs], sc.bin_names,
                       middle_first, hits_h[order][:, 1:4], hits_id[order],
-                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, calls)
+                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, sc.calls)
 
 
 # (read, adapter) pairs one block of phases B / C may hold at a time: 8 ints each, a few copies -> a few GB of HBM
@@ -222,12 +220,6 @@ def _load(input_path, check_read_count):
         calls = [_albacore_barcode(p) for p in fastqs]
         return rs, check, [calls[i] for i in fi]
     raise UsageError("Error: could not find " + input_path)
-
-
-def call_barcodes(names: List[str], start_scores: torch.Tensor, end_scores: torch.Tensor, opts: Options) -> np.ndarray:
-    """nanopore_read.py:399-466 for every read at once: see pipeline.call_barcodes (names[k] is bin k's name)."""
-    return _call_barcodes(len(names), start_scores, end_scores, opts.barcode_threshold, opts.barcode_diff,
-                          opts.require_two_barcodes)
 
 
 def barcode_bins(pl, bc_sets):
@@ -316,6 +308,70 @@ def gz_out_hint(opts, output, barcode_dir, input_path):
         return False
 
 
+def _open_pipeline(opts, device, aligner, adapter_panel):
+    """-> (adapter panel, Pipeline) for a run's options."""
+    panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
+    params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
+                        end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
+                        adapter_threshold=opts.adapter_threshold, check_reads=opts.check_reads,
+                        scores=tuple(int(x) for x in opts.scoring_scheme))
+    pl = Pipeline(panel, params, device=device, aligner=aligner)
+    if aligner is None:
+        # a one-shot run should not wait for hiprtc: specialised kernels are compiled on a worker
+        # thread and picked up by later launches (pc_jit_async, include/porechop_amd.h)
+        pl.aligner.lib.pc_jit_async(1)
+    return panel, pl
+
+
+def _upload(rs, dev, lo=0, hi=None):
+    """Reads [lo, hi) of a ReadSet (default: all of it, None for no ReadSet) on the device -> DeviceReads, None when there are
+    none.  A range takes its slice of the arena and 64 bytes past it (>= 16 must be readable past the end: the kernels fetch 16
+    columns per load); the whole set takes the whole arena, which ends in that padding."""
+    hi = (rs.count if rs is not None else 0) if hi is None else hi
+    if hi <= lo:
+        return None
+    a0 = int(rs.offsets[lo]) if lo else 0
+    a1 = rs.arena.size if hi == rs.count else min(int(rs.offsets[hi - 1]) + int(rs.lengths[hi - 1]) + 64, rs.arena.size)
+    return DeviceReads(torch.from_numpy(rs.arena[a0:a1]).to(dev), torch.from_numpy(rs.offsets[lo:hi] - a0).to(dev),
+                       torch.from_numpy(rs.lengths[lo:hi].copy()).to(dev))
+
+
+def _piece_files(piece_bins, n_pieces, barcode_dir, single, fmt, gz, known=()):
+    """The files of n_pieces pieces -> (bins, file index per piece [int32], paths).  Without bins everything goes to `single`.
+    With them (piece_bins: the call of every piece's read) each bin in use is barcode_dir/<bin>.<fmt>[.gz] (porechop.py:657-683):
+    the `known` bins first, as they come -- the bins of a streamed run's earlier blocks, the union over the ranks of a sharded
+    run -- then the others, sorted."""
+    if barcode_dir is None:
+        return [], np.zeros(n_pieces, dtype=np.int32), [single]
+    bins = list(known)
+    bins += sorted(set(piece_bins) - set(bins))
+    index = {b: k for k, b in enumerate(bins)}
+    pf = np.fromiter((index[b] for b in piece_bins), dtype=np.int32, count=n_pieces)
+    return bins, pf, [os.path.join(barcode_dir, b + "." + fmt + (".gz" if gz else "")) for b in bins]
+
+
+def _tally(pr, pn_, pf, nfiles, read_bases):
+    """(reads, bases) per file [int64, nfiles x 2] as the reference reports them: it counts reads, not pieces, and for a bin the
+    bases of those reads -- read_bases per read: their end-trimmed, or under --untrimmed whole, lengths (_plan_pieces) -- where
+    a single output file (read_bases None) counts the bases of its pieces."""
+    out = np.zeros((nfiles, 2), dtype=np.int64)
+    for k in range(nfiles):
+        sel = pf == k
+        rr = np.unique(pr[sel])
+        out[k] = rr.size, (pn_[sel] if read_bases is None else read_bases[rr]).sum()
+    return out
+
+
+def _finish_files(paths, gz, file_pos=None):
+    """After the last piece: the reference always creates its output file, so one that received nothing (file_pos[k] == 0;
+    None: the files exist) is created empty, and a gz file gets its end (io.gz_finish)."""
+    for k, path in enumerate(paths):
+        if file_pos is not None and file_pos[k] == 0:
+            open(path, "wb").close()
+        if gz:
+            gz_finish(path)
+
+
 def _emit(rs, pr, ps_, pn_, num, pf, paths, fastq, file_pos, gz, shared=False):
     """Pieces of one read set into their files at file_pos (updated): plain bytes (pc_readset_write_at / _shared), or --
     gz -- formatted and deflated by all cores in memory, then written (pc_readset_compress: what the reference gets from
@@ -366,7 +422,7 @@ def _find_sets(pl, panel, reads, check_idx, opts, barcode_dir, sharded=False):
 
 def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None):
     """Phases B (+ barcode calls) and C for R resident reads -> (start_trim, end_trim [device int32], bin index per
-    read [numpy int64, -1 = none], MiddleHits or None, bin names).
+    read [numpy int64, -1 = none], MiddleHits or None).
     explain: a list that receives the EndExplain of every block; phase B then runs with every pair traced
     (Pipeline.phase_b_explain) -- the same trims and calls."""
     dev = pl.device
@@ -374,7 +430,6 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
     end_trim = torch.zeros(R, dtype=torch.int32, device=dev)
     hits = None
     ci = np.full(R, -1, dtype=np.int64)
-    names = []
     if match_idx and R:
         # ---- phase B (+ barcode calls) ------------------------------------------------
         check_barcodes = barcode_dir is not None
@@ -384,7 +439,7 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
         # (8 ints per (read, adapter) pair, all middle adapters at once) is bounded by the block, not by
         # the input -- the reference holds one read's alignments at a time (nanopore_read.py:149-243).
         if check_barcodes:
-            names, bins = barcode_bins(pl, bc_sets)
+            bins = barcode_bins(pl, bc_sets)[1]
         n_mid = max(1, len(pl.middle_adapter_list(match_idx)))
         n_end = max(1, 2 * len(match_idx))
         block = max(MIN_READ_BLOCK, int(READ_BLOCK_PAIRS // max(n_mid, n_end)))
@@ -419,14 +474,52 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
         if check_barcodes:
             ci = np.concatenate(ci_parts)
         if not opts.no_split:
-            from .pipeline import MiddleHits
             if hit_parts:
                 hits = MiddleHits(*(torch.cat([getattr(h_, f) for h_ in hit_parts]) for f in ("read", "adapter", "start", "end", "identity")),
                                   max(h_.rounds for h_ in hit_parts), sum(h_.alignments for h_ in hit_parts))
             else:
                 hits = MiddleHits(*(torch.empty(0, dtype=dt, device=dev) for dt in
                                     (torch.int64, torch.int32, torch.int32, torch.int32, torch.float64)))
-    return start_trim, end_trim, ci, hits, names
+    return start_trim, end_trim, ci, hits
+
+
+@dataclass
+class _Scan:
+    """The per-read results of a scan, on the host."""
+    st: np.ndarray                           # int32 [R] start trims
+    et: np.ndarray                           # int32 [R] end trims
+    hits: np.ndarray                         # int64 [H, 4] middle hits: read, adapter, start, end (trimmed-read coordinates)
+    identity: Optional[np.ndarray]           # float64 [H], only for the per-read report
+    bin_names: Optional[List[str]]           # None when not demultiplexing
+    calls: Optional[List[str]]               # bin name per read, "none" without a call
+
+
+def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, read_base=0,
+                  gather=None):
+    """_scan_reads for R resident reads, then everything a run needs of it on the host -> _Scan.  The hits' reads are numbered
+    from read_base.  gather: called with the device tensors (start_trim, end_trim, bin index, hits [H, 4]) before they leave the
+    device -> the same four for the reads the _Scan is to cover (run() gathers every rank's there)."""
+    dev = pl.device
+    start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain)
+    if hasattr(pl.aligner, "sync"):
+        pl.aligner.sync()
+    if hits is not None and hits.read.numel():
+        h = torch.stack([hits.read + read_base, hits.adapter.to(torch.int64), hits.start.to(torch.int64),
+                         hits.end.to(torch.int64)], dim=1)
+    else:
+        h = torch.zeros((0, 4), dtype=torch.int64, device=dev)
+    if gather is not None:
+        start_trim, end_trim, ci_t, h = gather(start_trim, end_trim, torch.from_numpy(ci).to(dev), h)
+        ci = ci_t.cpu().numpy()
+    h = h.cpu().numpy()
+    identity = None
+    if explain is not None:
+        identity = hits.identity.cpu().numpy() if h.shape[0] else np.zeros(0, dtype=np.float64)
+    names = calls = None
+    if barcode_dir is not None:
+        names = _barcode_bin_names(pl, match_idx, orientation)            # the same list on every rank
+        calls = [names[k] if k >= 0 else "none" for k in ci]
+    return _Scan(start_trim.cpu().numpy(), end_trim.cpu().numpy(), h, identity, names, calls)
 
 
 def _concat_explain(blocks):
@@ -443,10 +536,12 @@ def _concat_explain(blocks):
                       None if b0.calls is None else [c for b in blocks for c in b.calls])
 
 
-def _plan_pieces(opts, lengths, st, et, h, calls, barcode_dir, discard_middle, matching, pl, match_idx):
-    """Which pieces of which reads are written (porechop.py:607-734, nanopore_read.py:76-147): lengths / st / et per
-    read (numpy), h = middle hits [H, 4] (read, adapter, start, end in trimmed-read coordinates), calls = bin name
-    per read or None -> (piece_read, piece_start, piece_len, piece_number, trimmed lengths, reads with middle hits)."""
+def _plan_pieces(opts, barcode_dir, lengths, sc, matching, pl, match_idx):
+    """Which pieces of which reads are written (porechop.py:607-734, nanopore_read.py:76-147): lengths per read (numpy), sc =
+    their _Scan -> (piece_read, piece_start, piece_len, piece_number, the bases per read that a bin's tally counts (_tally;
+    None when not binning), reads with middle hits)."""
+    st, et, h, calls = sc.st, sc.et, sc.hits, sc.calls
+    discard_middle = opts.discard_middle or barcode_dir is not None          # porechop.py:203-204
     s_pos, e_pos = trimmed_interval(torch.from_numpy(np.ascontiguousarray(lengths).copy()), torch.from_numpy(st), torch.from_numpy(et))
     s_pos, e_pos = s_pos.numpy(), e_pos.numpy()
     tlen = np.maximum(e_pos - s_pos, 0)
@@ -487,7 +582,7 @@ def _plan_pieces(opts, lengths, st, et, h, calls, barcode_dir, discard_middle, m
         pr, ps_, pn_, num = pr[order], ps_[order], pn_[order], num[order]
     else:
         pr, ps_, pn_, num = base_reads, p_start[base_reads], p_len[base_reads], np.zeros(base_reads.size, dtype=np.int64)
-    return pr, ps_, pn_, num, tlen, len(split_of)
+    return pr, ps_, pn_, num, p_len if barcode_dir is not None else None, len(split_of)
 
 
 # A plain FASTQ file larger than this is run as a stream of blocks (run_streamed); PC_STREAM_BLOCK_BYTES overrides
@@ -534,32 +629,18 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
             break
         first.close()
         first_bytes *= 4
-    discard_middle = opts.discard_middle or barcode_dir is not None
     res = RunResult(n_reads=0, read_type="FASTQ" if first.is_fastq else "FASTA")     # (plain FASTA streams too: cut at '>' lines)
     busy = {"load": time.perf_counter() - t_start, "scan": 0.0, "write": 0.0}
 
-    panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
-    params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
-                        end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
-                        adapter_threshold=opts.adapter_threshold, check_reads=opts.check_reads,
-                        scores=tuple(int(x) for x in opts.scoring_scheme))
-    pl = Pipeline(panel, params, device=device, aligner=aligner)
-    dev = pl.device
-    if aligner is None:
-        pl.aligner.lib.pc_jit_async(1)
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
 
     fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
     res.out_format = fmt
     fastq = fmt != "fasta"
-    whole = opts.untrimmed
     if barcode_dir is not None:
         os.makedirs(barcode_dir, exist_ok=True)
-        target = None
-    elif output is None:
-        target = "-"
-    else:
-        target = output                  # (gz: written compressed as it goes, no temporary file)
-    ext = "." + fmt + (".gz" if gz else "")
+    # the one file of a run without bins (gz: written compressed as it goes, no temporary file)
+    target = None if barcode_dir is not None else output if output is not None else "-"
 
     # ---- loader: blocks 1.. (block 0 is in hand) ------------------------------------------------------
     loaded = queue.Queue(maxsize=1)
@@ -610,46 +691,28 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
 
     # ---- writer ---------------------------------------------------------------------------------------
     to_write = queue.Queue(maxsize=1)
-    paths, file_pos, stats = [], np.zeros(0, dtype=np.int64), {}
+    bins, paths, file_pos, tally = [], [], np.zeros(0, dtype=np.int64), np.zeros((0, 2), dtype=np.int64)
 
     def writer():
-        nonlocal file_pos
+        nonlocal bins, paths, file_pos, tally
         io_lib.pc_io_set_thread_limit(share_w)
         try:
             while True:
                 item = to_write.get()
                 if item is None:
                     return
-                rs_, pr, ps_, pn_, num, bins_of_piece, tlen = item
+                rs_, pr, ps_, pn_, num, piece_bins, read_bases = item
                 t0 = time.perf_counter()
-                if barcode_dir is not None:
-                    pf = np.zeros(pr.size, dtype=np.int32)
-                    for b in sorted(set(bins_of_piece)):
-                        path = os.path.join(barcode_dir, b + ext)
-                        if path not in paths:
-                            paths.append(path)
-                            file_pos = np.concatenate([file_pos, np.zeros(1, dtype=np.int64)])
-                    index = {p_: k for k, p_ in enumerate(paths)}
-                    pf = np.fromiter((index[os.path.join(barcode_dir, b + ext)] for b in bins_of_piece), dtype=np.int32,
-                                     count=len(bins_of_piece))
-                else:
-                    if not paths:
-                        paths.append(target)
-                        file_pos = np.zeros(1, dtype=np.int64)
-                    pf = np.zeros(pr.size, dtype=np.int32)
+                # the files so far keep their places: a bin first seen in this block follows them
+                bins, pf, paths = _piece_files(piece_bins, pr.size, barcode_dir, target, fmt, gz, known=bins)
+                new = len(paths) - file_pos.size
+                file_pos = np.concatenate([file_pos, np.zeros(new, dtype=np.int64)])
+                tally = np.concatenate([tally, np.zeros((new, 2), dtype=np.int64)])
                 if pr.size:
                     t1 = time.perf_counter()
                     _emit(rs_, pr, ps_, pn_, num, pf, paths, fastq, file_pos, gz)
                     busy["write_call"] = busy.get("write_call", 0.0) + time.perf_counter() - t1
-                for k in np.unique(pf) if pr.size else []:
-                    sel = pf == k
-                    rr = np.unique(pr[sel])
-                    n0, b0 = stats.get(paths[k], (0, 0))
-                    if barcode_dir is not None:
-                        # the reference counts reads (not pieces) and their end-trimmed (or whole) lengths
-                        stats[paths[k]] = (n0 + int(rr.size), b0 + int((rs_.lengths[rr] if whole else tlen[rr]).sum()))
-                    else:
-                        stats[paths[k]] = (n0 + int(rr.size), b0 + int(pn_[sel].sum()))
+                tally += _tally(pr, pn_, pf, len(paths), read_bases)
                 t1 = time.perf_counter()
                 rs_.close()
                 busy["free"] = busy.get("free", 0.0) + time.perf_counter() - t1
@@ -675,44 +738,28 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 break
             t0 = time.perf_counter()
             R = rs.count
-            reads = None
-            if R:
-                reads = DeviceReads(torch.from_numpy(rs.arena).to(dev), torch.from_numpy(rs.offsets.copy()).to(dev),
-                                    torch.from_numpy(rs.lengths.copy()).to(dev))
+            reads = _upload(rs, pl.device)
             if matching is None:
                 check_idx = np.arange(min(R, max(0, opts.check_reads)), dtype=np.int64)
                 matching, match_idx, orientation = _find_sets(pl, panel, reads, check_idx, opts, barcode_dir)
                 res.matching_sets = [s.name for s in matching]
                 res.barcode_orientation = orientation
             ex_parts = [] if report is not None else None
-            start_trim, end_trim, ci, hits, _ = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts)
-            if hasattr(pl.aligner, "sync"):
-                pl.aligner.sync()
-            if hits is not None and hits.read.numel():
-                h = torch.stack([hits.read, hits.adapter.to(torch.int64), hits.start.to(torch.int64),
-                                 hits.end.to(torch.int64)], dim=1).cpu().numpy()
-            else:
-                h = np.zeros((0, 4), dtype=np.int64)
-            st, et = start_trim.cpu().numpy(), end_trim.cpu().numpy()
-            calls = None
+            sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts)
             if barcode_dir is not None:
-                names_all = _barcode_bin_names(pl, match_idx, orientation)
-                calls = [names_all[k] if k >= 0 else "none" for k in ci]
-                calls_all.extend(calls)
+                calls_all.extend(sc.calls)
             if report is not None:
-                hid = hits.identity.cpu().numpy() if h.shape[0] else np.zeros(0, dtype=np.float64)
-                ex = _host_explain(ex_parts, R, pl, match_idx, h, hid, names_all if barcode_dir is not None else None, None, calls)
+                ex = _host_explain(ex_parts, R, pl, match_idx, sc, None)
                 report_fh.write(report_rows(ex, [rs.name(i) for i in range(R)], rs.lengths))
                 ex_blocks.append(ex)
-            pr, ps_, pn_, num, tlen, n_split = _plan_pieces(opts, rs.lengths, st, et, h, calls, barcode_dir, discard_middle,
-                                                           matching, pl, match_idx)
+            pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
             res.middle_hit_reads += n_split
             res.n_reads += R
-            st_all.append(st); et_all.append(et)
-            bins_of_piece = [calls[r] for r in pr] if barcode_dir is not None else None
+            st_all.append(sc.st); et_all.append(sc.et)
+            piece_bins = [sc.calls[r] for r in pr] if barcode_dir is not None else None
             del reads
             busy["scan"] += time.perf_counter() - t0
-            to_write.put((rs, pr, ps_, pn_, num, bins_of_piece, tlen))
+            to_write.put((rs, pr, ps_, pn_, num, piece_bins, read_bases))
             rs = loaded.get()
     finally:
         stop.set()
@@ -747,17 +794,9 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     res.end_trim = np.concatenate(et_all) if et_all else np.zeros(0, dtype=np.int32)
     res.barcode_calls = calls_all if barcode_dir is not None else None
     # ---- what a whole-file run does after writing -------------------------------------------------------
-    if barcode_dir is not None:
-        for path in paths:
-            res.files[path] = stats.get(path, (0, 0))
-            if gz:
-                gz_finish(path)
-    elif output is not None:
-        if not paths or file_pos[0] == 0:
-            open(target, "wb").close()                              # the reference always creates the file
-        if gz:
-            gz_finish(target)
-        res.files[output] = stats.get(target, (0, 0))
+    if target != "-":
+        _finish_files(paths, gz, file_pos)
+        res.files.update(zip(paths, map(tuple, tally.tolist())))
     res.seconds = {"wall": time.perf_counter() - t_start, "load_busy": busy["load"], "scan_busy": busy["scan"], "write_busy": busy["write"],
                    "write_call_busy": busy.get("write_call", 0.0), "free_busy": busy.get("free", 0.0)}
     return res
@@ -835,7 +874,6 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
         if rs is not None:
             rs.close()
         return None
-    discard_middle = opts.discard_middle or barcode_dir is not None
     R = rs.count if rs is not None else 0
     counts = all_gather_ints([R], device if aligner is None else None)[:, 0].numpy()
     first_read, total = int(counts[:rank].sum()), int(counts.sum())
@@ -846,39 +884,16 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
     res.seconds["load"] = time.perf_counter() - t_start
     check_idx = np.arange(max(0, min(R, max(0, opts.check_reads) - first_read)), dtype=np.int64)
 
-    panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
-    params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
-                        end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
-                        adapter_threshold=opts.adapter_threshold, check_reads=opts.check_reads,
-                        scores=tuple(int(x) for x in opts.scoring_scheme))
-    pl = Pipeline(panel, params, device=device, aligner=aligner)
-    dev = pl.device
-    if aligner is None:
-        pl.aligner.lib.pc_jit_async(1)
-    coll_dev = dev if aligner is None else None
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
+    coll_dev = pl.device if aligner is None else None
     try:
         t0 = time.perf_counter()
-        reads = None
-        if R:
-            reads = DeviceReads(torch.from_numpy(rs.arena).to(dev), torch.from_numpy(rs.offsets.copy()).to(dev),
-                                torch.from_numpy(rs.lengths.copy()).to(dev))
+        reads = _upload(rs, pl.device)
         matching, match_idx, orientation = _find_sets(pl, panel, reads, check_idx, opts, barcode_dir, sharded=True)
         res.matching_sets = [s.name for s in matching]
         res.barcode_orientation = orientation
-        start_trim, end_trim, ci, hits, _ = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation)
-        if hasattr(pl.aligner, "sync"):
-            pl.aligner.sync()
-        if hits is not None and hits.read.numel():
-            h = torch.stack([hits.read, hits.adapter.to(torch.int64), hits.start.to(torch.int64),
-                             hits.end.to(torch.int64)], dim=1).cpu().numpy()
-        else:
-            h = np.zeros((0, 4), dtype=np.int64)
-        st, et = start_trim.cpu().numpy(), end_trim.cpu().numpy()
-        calls = None
-        if barcode_dir is not None:
-            names_all = _barcode_bin_names(pl, match_idx, orientation)
-            calls = [names_all[k] if k >= 0 else "none" for k in ci]
-        res.start_trim, res.end_trim, res.barcode_calls = st, et, calls          # this rank's reads
+        sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation)
+        res.start_trim, res.end_trim, res.barcode_calls = sc.st, sc.et, sc.calls          # this rank's reads
         res.first_read, res.local_reads = first_read, R
         res.seconds["scan"] = time.perf_counter() - t0
 
@@ -888,22 +903,15 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
         res.out_format = fmt
         fastq = fmt != "fasta"
         lengths = rs.lengths if R else np.zeros(0, dtype=np.int32)
-        pr, ps_, pn_, num, tlen, n_split = _plan_pieces(opts, lengths, st, et, h, calls, barcode_dir, discard_middle,
-                                                       matching, pl, match_idx)
-        tallies = all_gather_ints([n_split, int((st > 0).sum()), int((et > 0).sum())], coll_dev).sum(dim=0)
+        pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, lengths, sc, matching, pl, match_idx)
+        tallies = all_gather_ints([n_split, int((sc.st > 0).sum()), int((sc.et > 0).sum())], coll_dev).sum(dim=0)
         res.middle_hit_reads = int(tallies[0])
         res.counts = {"start_trimmed": int(tallies[1]), "end_trimmed": int(tallies[2])}
+        piece_bins = everyones = None
         if barcode_dir is not None:
-            mine = sorted({calls[r] for r in pr.tolist()})
-            bins = sorted(set().union(*all_gather_objects(mine)))
-            index = {b: k for k, b in enumerate(bins)}
-            paths = [os.path.join(barcode_dir, b + "." + fmt) for b in bins]
-            pf = np.fromiter((index[calls[r]] for r in pr.tolist()), dtype=np.int32, count=int(pr.size))
-            paths = [p + (".gz" if gz else "") for p in paths]
-        else:
-            paths = [output]
-            pf = np.zeros(pr.size, dtype=np.int32)
-        finals = paths
+            piece_bins = [sc.calls[r] for r in pr.tolist()]
+            everyones = sorted(set().union(*all_gather_objects(sorted(set(piece_bins)))))     # the same files, in the same order, on every rank
+        _, pf, paths = _piece_files(piece_bins, pr.size, barcode_dir, output, fmt, gz, known=everyones)
         nf = len(paths)
         # gz: every rank deflates its own pieces in memory first (independent members: any concatenation of them is a valid
         # file), the COMPRESSED sizes are what the ranks exchange, and each writes its image at its position
@@ -917,15 +925,8 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
                 sizes = rs.write_sizes(pr, ps_, pn_, num, pf, nf, fastq) if (R and nf) else np.zeros(nf, dtype=np.int64)
         except OSError as e:
             failed, sizes = e, np.zeros(nf, dtype=np.int64)
-        # per file: bytes, reads and bases of every rank (the reference counts reads, not pieces, and for bins their
-        # end-trimmed -- or whole -- lengths)
-        per_file = np.zeros((nf, 3), dtype=np.int64)
-        per_file[:, 0] = sizes
-        for k in range(nf):
-            sel = pf == k
-            rr = np.unique(pr[sel])
-            per_file[k, 1] = rr.size
-            per_file[k, 2] = int((lengths[rr] if opts.untrimmed else tlen[rr]).sum()) if barcode_dir is not None else int(pn_[sel].sum())
+        # per file: bytes, reads and bases of every rank
+        per_file = np.concatenate([np.asarray(sizes, dtype=np.int64).reshape(nf, 1), _tally(pr, pn_, pf, nf, read_bases)], axis=1)
         everyone = all_gather_ints(per_file.reshape(-1), coll_dev).numpy().reshape(world, nf, 3) if nf else np.zeros((world, 0, 3), dtype=np.int64)
         pos = everyone[:rank, :, 0].sum(axis=0).astype(np.int64)
         if rank == 0:
@@ -956,11 +957,9 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
                     except OSError:
                         pass
             raise failed if failed is not None else OSError("Error: could not write the output reads (another rank failed)")
-        if rank == 0 and gz:
-            for path in paths:
-                gz_finish(path)
-        for k in range(nf):
-            res.files[finals[k]] = (int(totals[k, 1]), int(totals[k, 2]))
+        if rank == 0:
+            _finish_files(paths, gz)
+        res.files.update(zip(paths, map(tuple, totals[:, 1:3].tolist())))
         dist.barrier()
         res.seconds["write"] = time.perf_counter() - t0
         res.seconds["wall"] = time.perf_counter() - t_start
@@ -996,21 +995,21 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         raise UsageError("Error: only one of the following options may be used: --output, --barcode_dir")
     if opts.untrimmed and barcode_dir is None:
         raise UsageError("Error: --untrimmed can only be used with --barcode_dir")
-    discard_middle = opts.discard_middle or barcode_dir is not None          # porechop.py:203-204
     input_path = str(input_path)
 
     import torch.distributed as dist
-    if report is not None and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1     # one process per GPU
+    if report is not None and sharded:
         raise UsageError("Error: the per-read report is not available in a sharded run (one process per GPU): run it in a single process")
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
-            and not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)):
+            and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
                                 report=report)
         if streamed is not None:
             return streamed
 
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if sharded:
         shared = run_sharded(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel)
         if shared is not None:
             return shared
@@ -1027,32 +1026,15 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     rs, check_idx, albacore = _load(input_path, opts.check_reads)
     res = RunResult(n_reads=rs.count, read_type="FASTQ" if rs.is_fastq else "FASTA")
     R_all = rs.count
-    import torch.distributed as dist
-    sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
     rank, world = (dist.get_rank(), dist.get_world_size()) if sharded else (0, 1)
     lo_r, hi_r = shard_by_bases(rs.lengths, world, rank)
     R = hi_r - lo_r                                             # reads this rank scans
     check_idx = check_idx[(check_idx >= lo_r) & (check_idx < hi_r)] - lo_r
     lap("load")
 
-    panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
-    params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
-                        end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
-                        adapter_threshold=opts.adapter_threshold, check_reads=opts.check_reads,
-                        scores=tuple(int(x) for x in opts.scoring_scheme))
-    pl = Pipeline(panel, params, device=device, aligner=aligner)
-    dev = pl.device
-    if aligner is None:
-        # a one-shot run should not wait for hiprtc: specialised kernels are compiled on a worker
-        # thread and picked up by later launches (pc_jit_async, include/porechop_amd.h)
-        pl.aligner.lib.pc_jit_async(1)
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
     try:
-        reads = None
-        if R:
-            a0 = int(rs.offsets[lo_r])
-            a1 = min(int(rs.offsets[hi_r - 1]) + int(rs.lengths[hi_r - 1]) + 64, rs.arena.size)   # >= 16 readable bytes past the end (the kernels fetch 16 columns per load)
-            reads = DeviceReads(torch.from_numpy(rs.arena[a0:a1]).to(dev), torch.from_numpy(rs.offsets[lo_r:hi_r] - a0).to(dev),
-                                torch.from_numpy(rs.lengths[lo_r:hi_r].copy()).to(dev))
+        reads = _upload(rs, pl.device, lo_r, hi_r)
         lap("upload", sync=True)
 
         # ---- phase A and the set-level rules ---------------------------------------------
@@ -1062,39 +1044,24 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         res.barcode_orientation = orientation
         lap("phase_a", sync=True)
 
-        calls = None
-        ex_parts = [] if report is not None else None
-        start_trim, end_trim, ci, hits, names = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain=ex_parts)
-        if hasattr(pl.aligner, "sync"):
-            pl.aligner.sync()
-
-        # ---- per-read results of all ranks, in read order --------------------------------
-        if hits is not None and hits.read.numel():
-            h = torch.stack([hits.read + lo_r, hits.adapter.to(torch.int64), hits.start.to(torch.int64),
-                             hits.end.to(torch.int64)], dim=1)
-        else:
-            h = torch.zeros((0, 4), dtype=torch.int64, device=dev)
-        ci_t = torch.from_numpy(ci).to(dev)
-        if sharded:
-            start_trim, end_trim, ci_t, h = (gather_in_order(x) for x in (start_trim, end_trim, ci_t, h))
+        # ---- phases B and C; the per-read results of all ranks, in read order ---------------
+        def gather(*tensors):
+            tensors = tuple(gather_in_order(x) for x in tensors)
             lap("gather", sync=True)
-            if rank != 0:
-                res.start_trim, res.end_trim = start_trim.cpu().numpy(), end_trim.cpu().numpy()
-                return res                                       # rank 0 writes
+            return tensors
+
+        ex_parts = [] if report is not None else None
+        sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, ex_parts, read_base=lo_r,
+                           gather=gather if sharded else None)
+        if rank != 0:
+            res.start_trim, res.end_trim = sc.st, sc.et
+            return res                                           # rank 0 writes
         R = R_all
-        st = start_trim.cpu().numpy()
-        et = end_trim.cpu().numpy()
-        h = h.cpu().numpy()
-        if barcode_dir is not None:
-            names_all = _barcode_bin_names(pl, match_idx, orientation)     # the same list on every rank
-            calls = [names_all[k] if k >= 0 else "none" for k in ci_t.cpu().numpy()]
-            if albacore is not None:                               # nanopore_read.py:468-473
-                calls = [c if (a is None or a == c) else "none" for c, a in zip(calls, albacore)]
-        res.start_trim, res.end_trim, res.barcode_calls = st, et, calls
+        if albacore is not None and sc.calls is not None:          # nanopore_read.py:468-473
+            sc.calls = [c if (a is None or a == c) else "none" for c, a in zip(sc.calls, albacore)]
+        res.start_trim, res.end_trim, res.barcode_calls = sc.st, sc.et, sc.calls
         if report is not None:
-            hid = hits.identity.cpu().numpy() if h.shape[0] else np.zeros(0, dtype=np.float64)
-            res.explain = _host_explain(ex_parts, R, pl, match_idx, h, hid, names_all if barcode_dir is not None else None,
-                                        albacore, calls)
+            res.explain = _host_explain(ex_parts, R, pl, match_idx, sc, albacore)
             with open(report, "w") as fh:
                 fh.write(report_header())
                 fh.write(report_rows(res.explain, [rs.name(i) for i in range(R)], rs.lengths))
@@ -1103,9 +1070,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         # ---- which pieces of which reads -------------------------------------------------
         fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
         res.out_format = fmt
-        whole = opts.untrimmed
-        pr, ps_, pn_, num, tlen, n_split = _plan_pieces(opts, rs.lengths, st, et, h, calls, barcode_dir, discard_middle,
-                                                       matching, pl, match_idx)
+        pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
         res.middle_hit_reads = n_split
 
         lap("plan_output")
@@ -1113,32 +1078,15 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         fastq = fmt != "fasta"                                      # porechop.py:667,711,727
         if barcode_dir is not None:
             os.makedirs(barcode_dir, exist_ok=True)
-            all_bins = sorted(set(calls))
-            lookup = {b: k for k, b in enumerate(all_bins)}
-            bin_of_read = np.fromiter((lookup[c] for c in calls), dtype=np.int32, count=len(calls))
-            used = np.unique(bin_of_read[pr]) if pr.size else np.zeros(0, dtype=np.int32)
-            bins = [all_bins[k] for k in used]
-            remap = np.full(len(all_bins), -1, dtype=np.int32)
-            remap[used] = np.arange(used.size, dtype=np.int32)
-            pf = remap[bin_of_read[pr]] if pr.size else np.zeros(0, dtype=np.int32)
-            paths = [os.path.join(barcode_dir, b + "." + fmt + (".gz" if gz else "")) for b in bins]
-            _emit(rs, pr, ps_, pn_, num, pf, paths, fastq, np.zeros(len(paths), dtype=np.int64), gz)
-            for k, (b, path) in enumerate(zip(bins, paths)):
-                sel = pf == k
-                # the reference counts reads (not pieces) and their end-trimmed (or whole) lengths
-                rr = np.unique(pr[sel])
-                res.files[path] = (int(rr.size), int((rs.lengths[rr] if whole else tlen[rr]).sum()))
-                if gz:
-                    gz_finish(path)
-        elif output is None:
-            rs.write(pr, ps_, pn_, num, np.zeros(pr.size, dtype=np.int32), ["-"], fastq)
-        else:
-            open(output, "wb").close()                              # the reference always creates the file
-            if pr.size:
-                _emit(rs, pr, ps_, pn_, num, np.zeros(pr.size, dtype=np.int32), [output], fastq, np.zeros(1, dtype=np.int64), gz)
-            if gz:
-                gz_finish(output)
-            res.files[output] = (int(np.unique(pr).size), int(pn_.sum()))
+        target = output if output is not None else "-"
+        _, pf, paths = _piece_files([sc.calls[r] for r in pr.tolist()] if barcode_dir is not None else None, pr.size, barcode_dir,
+                                    target, fmt, gz)
+        file_pos = np.zeros(len(paths), dtype=np.int64)
+        if pr.size:
+            _emit(rs, pr, ps_, pn_, num, pf, paths, fastq, file_pos, gz)
+        if barcode_dir is not None or output is not None:
+            _finish_files(paths, gz, file_pos)
+            res.files.update(zip(paths, map(tuple, _tally(pr, pn_, pf, len(paths), read_bases).tolist())))
         lap("write")
         return res
     finally:

@@ -112,7 +112,8 @@ def test_streamed_runs_write_the_same_files(oracle, tmp_path, monkeypatch):
     block k+1 | scan block k | write block k-1).  With blocks of a few kB: (1) the recorded runs of the reference CLI
     are still reproduced byte for byte, and (2) with a small --check_reads -- so that the first block does not
     swallow the file -- streamed and whole-file runs of the same options write identical files (bins, splits,
-    numbering, FASTA / gzip output, --untrimmed, --discard_unassigned)."""
+    numbering, FASTA / gzip output, --untrimmed, --discard_unassigned) and return the same RunResult: trims, calls, sets,
+    and reads and bases per file."""
     import hashlib
     import os
     from porechop_amd import runner
@@ -145,7 +146,7 @@ def test_streamed_runs_write_the_same_files(oracle, tmp_path, monkeypatch):
                 ("b", "bins_u", {"untrimmed": True}), ("b", "bins_d", {"discard_unassigned": True, "require_two_barcodes": True}),
                 ("o", "split.fastq", {"min_split_read_size": 100, "middle_threshold": 80.0})]
     for k, (mode, fname, extra) in enumerate(variants):
-        outs = []
+        outs, results = [], []
         for streamed in (True, False):
             monkeypatch.setenv("PC_STREAM_BLOCK_BYTES", "6000" if streamed else str(1 << 40))
             opts = runner.Options(check_reads=15, **extra)
@@ -154,12 +155,21 @@ def test_streamed_runs_write_the_same_files(oracle, tmp_path, monkeypatch):
             target = str(work / fname)
             n0 = len(seen_blocks)
             if mode == "b":
-                runner.run(inp, barcode_dir=target, options=opts, aligner=OracleAligner(oracle, opts.scoring_scheme))
+                res = runner.run(inp, barcode_dir=target, options=opts, aligner=OracleAligner(oracle, opts.scoring_scheme))
             else:
-                runner.run(inp, output=target, options=opts, aligner=OracleAligner(oracle, opts.scoring_scheme))
+                res = runner.run(inp, output=target, options=opts, aligner=OracleAligner(oracle, opts.scoring_scheme))
             assert (len(seen_blocks) - n0 > 3) == streamed
             outs.append(md5s(target))
+            results.append(res)
         assert outs[0] == outs[1] and outs[0], (fname, outs)
+        s_, w_ = results
+        for f in ("n_reads", "read_type", "out_format", "matching_sets", "barcode_orientation", "barcode_calls", "middle_hit_reads"):
+            assert getattr(s_, f) == getattr(w_, f), (fname, f, getattr(s_, f), getattr(w_, f))
+        for f in ("start_trim", "end_trim"):
+            assert getattr(s_, f).dtype == getattr(w_, f).dtype and getattr(s_, f).tolist() == getattr(w_, f).tolist(), (fname, f)
+        # (the two runs write into different directories: files by basename)
+        by_name = [{os.path.basename(p_): v for p_, v in r_.files.items()} for r_ in results]
+        assert len(by_name[0]) == len(s_.files) and by_name[0] == by_name[1] and by_name[0], (fname, by_name)
 
 
 def test_streamed_run_that_fails_midway_leaves_no_partial_output(tmp_path, oracle):
