@@ -348,6 +348,20 @@ int pc_prefilter_packed(pc_ctx *ctx, const void *d_plane, const int64_t *d_win_o
                         int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits,
                         int nadapters, uint32_t *d_mask, void *stream);
 
+/* pc_prefilter_packed for EVERY adapter list and every bound: same arguments, same mask, never PC_ERR_UNSUPPORTED_SCORES.
+ * Pieces the seed stage covers take it as above; every other piece -- parts shorter than 6 bases (--middle_threshold below
+ * about 87 for a 28-mer), more than 8 parts, an adapter with a letter other than A/C/G/T/U (taken whole) -- runs Myers'
+ * recurrence over every column of the plane (csrc/pc_prefilter.hip prefilter_packed_kernel: 64 bases per 16-byte fetch, the
+ * Eq row picked by the 2-bit code), and so does a batch whose candidate list overflowed, immediately or on the repeat call
+ * after pc_prefilter_overflowed.  Bases that were not A/C/G/T/U sit in the plane as 'A' and the exception list is NOT
+ * consulted; adapter letters that are not A/C/G/T/U are wildcards in that kernel (they match all four codes), so every
+ * column that matches in the reference's sense (equal Dna5 codes, N == N) still matches: a cleared bit is still a proof.
+ * For adapters of A/C/G/T/U over reads without exceptions the mask equals pc_prefilter_device's over the unpacked bytes
+ * bit for bit; otherwise it is a superset of it. */
+int pc_prefilter_packed_any(pc_ctx *ctx, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
+                            int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits,
+                            int nadapters, uint32_t *d_mask, void *stream);
+
 /* The seed stage sizes its verification launch from a count it reads back from the device: ONE host round trip per call.
  * pc_prefilter_defer_count(ctx, 1) removes it -- the verification is launched for the whole candidate list (threads beyond
  * the count leave at once) and the count follows to pinned host memory; after the caller's next synchronisation of the

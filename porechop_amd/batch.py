@@ -351,11 +351,13 @@ class Aligner:
               "pc_prefilter_device")
         return mask
 
-    def prefilter_mask_packed(self, plane, win_off, win_len, max_len, adapters, max_edits, stream=None):
+    def prefilter_mask_packed(self, plane, win_off, win_len, max_len, adapters, max_edits, stream=None, total=False):
         """prefilter_mask over reads held at 2 bits per base (pc_prefilter_packed): plane = the uint8 CUDA tensor of
         io.pack_reads' plane (64 readable bytes past the last base), win_off in BASES.  -> the mask, or None when this
         adapter list does not take the packed route (an adapter with a letter other than A/C/G/T/U, or one the seed stage
-        cannot cover): unpack and call prefilter_mask."""
+        cannot cover): unpack and call prefilter_mask.
+        total=True (pc_prefilter_packed_any): every list is taken -- what the seed stage cannot cover runs the exhaustive
+        kernel over the plane, adapter letters that are not bases as wildcards -- and None is never returned."""
         import torch
         assert plane.is_cuda and plane.dtype == torch.uint8 and win_off.is_cuda and win_len.is_cuda
         assert win_off.dtype == torch.int64 and win_len.dtype == torch.int32 and win_off.is_contiguous() and win_len.is_contiguous()
@@ -367,6 +369,11 @@ class Aligner:
         ad = np.ascontiguousarray(adapters, dtype=np.int32)
         ed = np.ascontiguousarray(max_edits, dtype=np.int32)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if total:
+            check(self.lib.pc_prefilter_packed_any(self._ctx, plane.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n, int(max_len),
+                                                   ad.ctypes.data, ed.ctypes.data, na, mask.data_ptr(), ctypes.c_void_p(s)),
+                  "pc_prefilter_packed_any")
+            return mask
         rc = self.lib.pc_prefilter_packed(self._ctx, plane.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n, int(max_len),
                                           ad.ctypes.data, ed.ctypes.data, na, mask.data_ptr(), ctypes.c_void_p(s))
         if rc == -2:                              # PC_ERR_UNSUPPORTED_SCORES: not a list for the packed route
@@ -459,12 +466,12 @@ class Aligner:
     def prefilter_overflowed(self):
         return bool(self.lib.pc_prefilter_overflowed(self._ctx))
 
-    def prefilter_rows(self, arena, win_off, win_len, max_len, adapters, max_edits, stream=None, packed=False):
+    def prefilter_rows(self, arena, win_off, win_len, max_len, adapters, max_edits, stream=None, packed=False, total=False):
         """The prefilter's survivors, sparsely: -> (rows int64 [R]: the windows with at least one surviving adapter, in
         increasing order; bits bool [R, len(adapters)]: which).  Everything not listed is PROVEN not to be a hit."""
         import torch
         if packed:              # arena is the 2-bit plane, win_off counts bases; None = this list does not take the packed route
-            mask = self.prefilter_mask_packed(arena, win_off, win_len, max_len, adapters, max_edits, stream)
+            mask = self.prefilter_mask_packed(arena, win_off, win_len, max_len, adapters, max_edits, stream, total=total)   # (total: never None)
             if mask is None:
                 return None
         else:

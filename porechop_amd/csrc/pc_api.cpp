@@ -1520,6 +1520,7 @@ int pc_prefilter_max_edits(int adapter_len, double threshold_percent)
 static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                           int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
                           uint32_t *d_mask, void *stream_v, int packed);
+enum { PF_BYTES = 0, PF_PLANE_SEEDS = 1, PF_PLANE_TOTAL = 2 };    // `packed` of prefilter_impl
 
 int pc_prefilter_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                         int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
@@ -1539,6 +1540,17 @@ int pc_prefilter_packed(pc_ctx *c, const void *d_plane, const int64_t *d_win_off
 {
     if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
     return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, 1);
+}
+
+// pc_prefilter_packed for EVERY adapter list and bound: what the seed stage cannot take (and a batch whose candidate list
+// overflowed) runs the exhaustive kernel over the plane, prefilter_packed_kernel; adapter letters that are not A/C/G/T/U are
+// wildcards there (pc_prefilter.hip: a cleared bit is still a proof).  Never PC_ERR_UNSUPPORTED_SCORES.
+int pc_prefilter_packed_any(pc_ctx *c, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
+                            int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
+                            uint32_t *d_mask, void *stream_v)
+{
+    if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
+    return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, PF_PLANE_TOTAL);
 }
 
 int pc_unpack_windows(pc_ctx *c, const void *d_plane, const int64_t *d_exc_pos, int64_t nexc, const int64_t *d_src_off,
@@ -1565,7 +1577,9 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     const int words = (nadapters + 31) / 32;
     std::vector<int32_t> key(adapters, adapters + nadapters);
     key.insert(key.end(), max_edits, max_edits + nadapters);
-    key.push_back(packed ? 1 : 0);                               // (the seed tables differ: q-gram orientation and base codes)
+    // (the seed tables differ between bytes and plane: q-gram orientation and base codes; the exhaustive kernel's between
+    // the two routes over the plane: [256][P] rows per group, never launched, or [4][P] with wildcards)
+    key.push_back(packed);
     if (key != c->pf_key) {
         // the cached seed / table state is rebuilt member by member below: until ALL of it is in place (the key is set last)
         // no key may name it -- a failed upload half-way must not leave the old key over mixed tables
@@ -1602,10 +1616,11 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
         std::vector<pc_ctx::PfLaunch> launches;
         std::vector<uint32_t> tables;
         std::vector<int32_t> meta;
+        const size_t rows = packed == PF_PLANE_TOTAL ? 4 : 256;      // Eq rows per group: one per 2-bit code / per byte value
         auto add_groups = [&](size_t first, size_t count, int P) {
             const int groups = (int)((count + P - 1) / P);
             pc_ctx::PfLaunch L{P, groups, tables.size(), meta.size()};
-            tables.resize(tables.size() + (size_t)groups * 256 * P, 0xFFFFFFFFu);           // unused slots: all wildcards
+            tables.resize(tables.size() + (size_t)groups * rows * P, 0xFFFFFFFFu);          // unused slots: all wildcards
             meta.resize(meta.size() + (size_t)groups * P * 4, 0);
             for (size_t i = 0; i < count; ++i) {
                 const Piece &pc = pieces[first + i];
@@ -1619,7 +1634,13 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
                         if (dna5((unsigned char)ad[pc.begin + r]) == code) e |= 1u << (32 - pc.len + r);
                     eq_of_code[code] = e;
                 }
-                for (int b = 0; b < 256; ++b) tables[L.table_off + (g * 256 + b) * P + slot] = eq_of_code[dna5((unsigned char)b)];
+                if (packed == PF_PLANE_TOTAL) {
+                    // the plane holds codes 0..3 only, a read's non-base among them as 0: an adapter letter that is not a
+                    // base (Dna5 code 4) matches all four, so that no match of the byte route (N == N) is lost
+                    for (size_t code = 0; code < 4; ++code) tables[L.table_off + (g * 4 + code) * P + slot] = eq_of_code[code] | (eq_of_code[4] & ~wild);
+                } else {
+                    for (int b = 0; b < 256; ++b) tables[L.table_off + (g * 256 + b) * P + slot] = eq_of_code[dna5((unsigned char)b)];
+                }
                 int32_t *mt = &meta[L.meta_off + (g * P + slot) * 4];
                 mt[0] = pc.len; mt[1] = pc.k; mt[2] = pc.word; mt[3] = (int32_t)pc.bit;
             }
@@ -1713,7 +1734,7 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
                 rest_piece.push_back(i);
             }
         }
-        if (packed && !rest_piece.empty()) return PC_ERR_UNSUPPORTED_SCORES;   // only the seed stage reads the plane
+        if (packed == PF_PLANE_SEEDS && !rest_piece.empty()) return PC_ERR_UNSUPPORTED_SCORES;   // this route has the seed stage only
         c->sd_nq = 0;
         int cls_of_q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int q = 8; q >= 6; --q) if (have_q[q]) { cls_of_q[q] = c->sd_nq; c->sd_q[c->sd_nq++] = q; }
@@ -1806,7 +1827,7 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     }
     HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)nwindows * words * 4, stream));
     if (c->pf_launches.empty() || max_len == 0) return PC_OK;
-    if (packed && (c->sd_nq < 1 || !c->pf_rest_launches.empty())) return PC_ERR_UNSUPPORTED_SCORES;
+    if (packed == PF_PLANE_SEEDS && (c->sd_nq < 1 || !c->pf_rest_launches.empty())) return PC_ERR_UNSUPPORTED_SCORES;
     // column chunks: enough (window, chunk) units to fill the chip several times over, chunks no shorter than 512
     // columns (the warm-up before a chunk is the longest piece + its edit bound: ~35 columns)
     const int64_t target = (int64_t)c->ncu * 2048 * 6;
@@ -1826,7 +1847,8 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     auto exhaustive = [&](const std::vector<pc_ctx::PfLaunch> &ls) -> int {
         for (const pc_ctx::PfLaunch &L : ls) {
             a.tables = c->d_pf_tables.as<uint32_t>() + L.table_off; a.piece_meta = c->d_pf_meta.as<int32_t>() + L.meta_off;
-            if (pck::launch_prefilter(a, L.P, L.groups, stream)) return PC_ERR_NO_DEVICE;
+            if (packed == PF_PLANE_TOTAL ? pck::launch_prefilter_packed(a, L.P, L.groups, stream) : pck::launch_prefilter(a, L.P, L.groups, stream))
+                return PC_ERR_NO_DEVICE;
         }
         return PC_OK;
     };
@@ -1860,7 +1882,7 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
         ScopedTimer ts(c, stream, 5, nwindows);     // the scan alone (pairs = windows)
         if (packed ? pck::launch_seed_scan_packed(sa, stream) : pck::launch_seed_scan(sa, stream)) return PC_ERR_NO_DEVICE;
     }
-    if (!packed && (rc = exhaustive(c->pf_rest_launches))) return rc;          // independent of the candidate count
+    if (packed != PF_PLANE_SEEDS && (rc = exhaustive(c->pf_rest_launches))) return rc;     // independent of the candidate count
     c->pf_deferred_cap = 0;
     if (c->pf_defer_count) {
         // No host round trip: the verify kernels read the count on the device (threads beyond it leave at once) and are
@@ -1889,8 +1911,8 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
         if (!told) fprintf(stderr, "porechop_amd: %llu seed candidates for a list of %lld: this batch is filtered by the exhaustive kernel\n",
                            found, (long long)cap);
         told = true;
-        if (packed) {
-            // no exhaustive kernel over the plane: nothing is excluded for this batch (every pair goes to the DP -- exact, only slower)
+        if (packed == PF_PLANE_SEEDS) {
+            // this route has no exhaustive kernel: nothing is excluded for this batch (every pair goes to the DP -- exact, only slower)
             HIP_TRY(hipMemsetAsync(d_mask, 0xFF, (size_t)nwindows * words * 4, stream));
             return PC_OK;
         }

@@ -204,6 +204,9 @@ int launch_seed_verify(const SeedVerifyArgs &a, int64_t ncand, void *stream);
 // adapters made of A/C/G/T (the only ones this route takes), so every pair it clears is still proven.
 int launch_seed_scan_packed(const SeedScanArgs &a, void *stream);
 int launch_seed_verify_packed(const SeedVerifyArgs &a, int64_t ncand, void *stream);
+// The exhaustive kernel over the plane (prefilter_packed_kernel): PrefilterArgs with `arena` = the plane, win_off in BASES and
+// `tables` = [group][4 codes][pieces_per_lane] Eq words, every adapter position that is not A/C/G/T/U set for all four codes.
+int launch_prefilter_packed(const PrefilterArgs &a, int pieces_per_lane, int ngroups, void *stream);
 // Windows of the plane as bytes ('A' 'C' 'G' 'T', 'N' at the listed exceptions), window i to dst + dst_off[i], padded with
 // `pad` up to dst_off[i + 1]; src_off counts bases and is ascending.
 int launch_unpack_windows(const void *plane, const int64_t *exc_pos, int64_t nexc, const int64_t *src_off, const int32_t *len,

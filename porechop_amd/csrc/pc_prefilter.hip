@@ -605,6 +605,162 @@ __global__ __launch_bounds__(256) void seed_verify_packed_kernel(SeedVerifyArgs 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The exhaustive kernel over the plane: prefilter_kernel<P> with its columns taken from reads held at 2 bits per base, for
+// every piece the seed stage cannot take (parts shorter than six bases, more than eight parts, a letter that is not a base)
+// and for a batch whose candidate list overflowed.  Same lanes, same units (window, chunk) in chunk-major order, same
+// warm-up, same recurrence, same piece metadata and mask; what differs is where a column comes from:
+//   - win_off counts BASES: base i sits in bits 2 (i % 16) of dword i / 16 of the plane;
+//   - a lane fetches ALIGNED 16-byte blocks, 64 bases each: it starts `skip` (0..63) bases before its first column, at the
+//     block boundary below it, and sits those out; its last block ends at most 15 bytes past the byte of its last base (the
+//     plane is 16-byte aligned and readable 64 bytes past its last base);
+//   - the Eq row of a column is picked by the 2-bit code itself: the group's table is [4][P] words (16 P bytes of LDS
+//     instead of 4 KB P), a row's byte offset is one shift and one and of the fetched dword, and the 64 lanes of a wave read
+//     at most four different rows (no bank conflicts).
+// EXACTNESS.  A base of the read that was not A/C/G/T/U sits in the plane as code 0 and no exception list is consulted.  The
+// host therefore makes every adapter position that is not A/C/G/T/U a WILDCARD row: its Eq bit is set for all four codes.
+// Every column that matches in the reference's sense (equal Dna5 codes, N == N) still matches -- a base against the same
+// base as before, an adapter N against whatever code the read's N became -- so the edit distance over the plane is never
+// larger than the true one, and a cleared bit remains a proof.  For adapters made of A/C/G/T/U over reads without
+// exceptions no row is a wildcard and no code stands for another letter: the mask is prefilter_kernel's bit for bit.
+// ---------------------------------------------------------------------------------------------------------
+// the P Eq words of base t (a constant once the caller's loop is unrolled) of the dword wd: row `code` of the [4][P] table,
+// byte offset code * 4 P
+template <int P>
+__device__ __forceinline__ void load_row_code(const uint32_t *tab, uint32_t wd, int t, uint32_t (&e)[P])
+{
+    constexpr int S = P == 8 ? 5 : P == 4 ? 4 : P == 2 ? 3 : 2;      // log2(4 P)
+    const uint32_t off = (2 * t >= S ? wd >> (2 * t - S) : wd << (S - 2 * t)) & (3u << S);
+    const uint32_t *row = (const uint32_t *)((const char *)tab + off);
+    if constexpr (P >= 4) {
+#pragma unroll
+        for (int i = 0; i < P; i += 4) {
+            const uint4 v = *(const uint4 *)(row + i);
+            e[i] = v.x; e[i + 1] = v.y; e[i + 2] = v.z; e[i + 3] = v.w;
+        }
+    } else if constexpr (P == 2) {
+        const uint2 v = *(const uint2 *)row;
+        e[0] = v.x; e[1] = v.y;
+    } else {
+        e[0] = row[0];
+    }
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void prefilter_packed_kernel(PrefilterArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t tab[4 * P];
+    const int group = blockIdx.y;
+    if (threadIdx.x < 4 * P) tab[threadIdx.x] = a.tables[(size_t)group * 4 * P + threadIdx.x];     // [code][piece]
+    __syncthreads();
+    const int32_t *meta = a.piece_meta + (size_t)group * P * 4;      // m, k, mask word, mask bit
+
+    // unit = (window, chunk), chunk-major: a wave holds 64 consecutive windows at one chunk index
+    const int64_t wblocks = (a.nwindows + 255) / 256;
+    const int chunk = (int)(blockIdx.x / wblocks);
+    const int64_t w = (int64_t)(blockIdx.x % wblocks) * 256 + threadIdx.x;
+    // Columns are counted from the 64-base block boundary below the lane's first one: the chunk is [skip, n).
+    int n = 0, skip = 0;
+    const uint32_t *p = (const uint32_t *)a.arena;
+    if (w < a.nwindows) {
+        const int len = a.win_len[w];
+        if (chunk == 0 && len > a.max_len) atomicAdd(a.err, 1u);      // columns beyond chunks * chunk_len would go unscanned
+        const int c0 = chunk * a.chunk_len;
+        if (c0 < len) {
+            const int start = c0 > a.warm ? c0 - a.warm : 0;
+            const int end = (c0 + a.chunk_len < len) ? c0 + a.chunk_len : len;
+            const int64_t b = a.win_off[w] + start;                   // base index of the first column
+            skip = (int)(b & 63);
+            p += (b - skip) >> 4;
+            n = end - start + skip;
+        }
+    }
+    const int nmax = __builtin_amdgcn_readfirstlane(wave_max(n));
+    if (nmax == 0) return;
+    // shortest chunk among the lanes that have one (lanes past the end of their read sit the whole launch out)
+    const int nmin = __builtin_amdgcn_readfirstlane(wave_min(n > 0 ? n : 0x7FFFFFFF));
+    const int any_skip = __builtin_amdgcn_readfirstlane(wave_max(skip));
+    const int min_skip = __builtin_amdgcn_readfirstlane(wave_min(n > 0 ? skip : 64));
+    if (n <= 0) return;
+
+    uint32_t pv[P], mv[P], sc[P], mn[P];
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const int m = meta[i * 4 + 0];                // 0: unused slot of the group (Eq table all ones, score 0)
+        pv[i] = m >= 32 ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> m);
+        if (m == 0) pv[i] = 0;
+        mv[i] = 0;
+        sc[i] = (uint32_t)m;
+        mn[i] = m == 0 ? 0x7FFFFFFFu : (uint32_t)m;
+    }
+
+    // A block is worked through a dword (16 columns) at a time by ONE loop body, the block's dwords moving down through
+    // w0: the unrolled body of all 64 columns would be four times the byte kernel's (12 VALU x P per column) and outgrow
+    // the instruction cache.
+    // ---- blocks in which some lane sits columns out: column by column; dwords no lane has a column in are passed over ----
+    auto masked_block = [&](int j0) {
+        u32x4 blk = {0, 0, 0, 0};
+        if (j0 < n) blk = *(const u32x4 *)(p + (j0 >> 4));
+        uint32_t w0 = blk.x, w1 = blk.y, w2 = blk.z, w3 = blk.w;
+#pragma unroll 1
+        for (int d0 = j0; d0 < j0 + 64; d0 += 16) {
+            if (d0 < nmax && d0 + 16 > min_skip) {    // (wave-uniform)
+#pragma unroll
+                for (int t = 0; t < 16; ++t) {
+                    if (d0 + t >= skip && d0 + t < n) {
+                        uint32_t e[P];
+                        load_row_code<P>(tab, w0, t, e);
+#pragma unroll
+                        for (int i = 0; i < P; ++i) {
+                            sc[i] = myers_step(e[i], pv[i], mv[i], sc[i]);
+                            mn[i] = sc[i] < mn[i] ? sc[i] : mn[i];
+                        }
+                    }
+                }
+            }
+            w0 = w1; w1 = w2; w2 = w3;
+        }
+    };
+    const int first = any_skip ? 64 : 0;
+    if (any_skip) masked_block(0);
+    // ---- 64-column blocks every active lane of the wave has: no masking, next block's bases in flight ----------------
+    const int full = nmin & ~63;
+    u32x4 cur = {0, 0, 0, 0};
+    if (full > first) cur = *(const u32x4 *)(p + (first >> 4));
+    for (int j0 = first; j0 < full; j0 += 64) {
+        u32x4 nxt = cur;
+        if (j0 + 64 < full) nxt = *(const u32x4 *)(p + ((j0 + 64) >> 4));
+        uint32_t w0 = cur.x, w1 = cur.y, w2 = cur.z, w3 = cur.w;
+#pragma unroll 1
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int t = 0; t < 16; t += 2) {
+                uint32_t e0[P], e1[P];
+                load_row_code<P>(tab, w0, t, e0);
+                load_row_code<P>(tab, w0, t + 1, e1);
+#pragma unroll
+                for (int i = 0; i < P; ++i) {
+                    const uint32_t s1 = myers_step(e0[i], pv[i], mv[i], sc[i]);
+                    const uint32_t s2 = myers_step(e1[i], pv[i], mv[i], s1);
+                    const uint32_t lo = s1 < s2 ? s1 : s2;
+                    mn[i] = lo < mn[i] ? lo : mn[i];
+                    sc[i] = s2;
+                }
+            }
+            w0 = w1; w1 = w2; w2 = w3;
+        }
+        cur = nxt;
+    }
+    // ---- the rest (chunks of unequal length in one wave, the last < 64 columns): lanes sit out column by column.
+    // A lane fetches a block only when it has a column in it or behind it (j0 < n): never beyond the block of its last base.
+    for (int j0 = full > first ? full : first; j0 < nmax; j0 += 64) masked_block(j0);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+        const int m = meta[i * 4 + 0], k = meta[i * 4 + 1];
+        if (m > 0 && (int)mn[i] <= k) atomicOr(a.mask + w * a.words + meta[i * 4 + 2], (uint32_t)meta[i * 4 + 3]);
+    }
+}
+
 // ---- windows of the plane as bytes: one workgroup per window ---------------------------------------------------------
 __global__ __launch_bounds__(256) void unpack_windows_kernel(const uint32_t *plane, const int64_t *src_off, const int32_t *len,
                                                              uint8_t *dst, const int64_t *dst_off, int pad)
@@ -637,6 +793,24 @@ __global__ __launch_bounds__(256) void unpack_windows_exceptions_kernel(const in
 }
 
 }  // namespace
+
+int launch_prefilter_packed(const PrefilterArgs &a, int pieces_per_lane, int ngroups, void *stream)
+{
+    if (a.nwindows <= 0 || ngroups <= 0) return 0;
+    const int64_t wblocks = (a.nwindows + 255) / 256;
+    const int64_t gx = wblocks * a.chunks;
+    if (gx > 0x7FFFFFFFll || ngroups > 65535) return -1;
+    const dim3 grid((unsigned)gx, (unsigned)ngroups), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (pieces_per_lane) {
+        case 1: hipLaunchKernelGGL(prefilter_packed_kernel<1>, grid, block, 0, s, a); break;
+        case 2: hipLaunchKernelGGL(prefilter_packed_kernel<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(prefilter_packed_kernel<4>, grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL(prefilter_packed_kernel<8>, grid, block, 0, s, a); break;
+        default: return -1;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 int launch_seed_scan_packed(const SeedScanArgs &a, void *stream)
 {

@@ -50,6 +50,9 @@ class ScanParams:
     adapter_threshold: float = 90.0
     check_reads: int = 10000
     scores: Tuple[int, int, int, int] = (3, -6, -5, -2)
+    # packed-only reads (DeviceReads.packed_only): the prefilter takes EVERY middle-adapter list over the plane
+    # (pc_prefilter_packed_any) instead of unpacking all reads for a list the seed stage cannot cover
+    packed_total: bool = False
 
 
 @dataclass
@@ -971,8 +974,9 @@ class Pipeline:
             return sb, torch.cat([sel for _, sel in cmeta]), torch.cat(outs)
         got = None
         if packed_reads is not None and packed_reads.arena is None:
+            kw = {"total": True} if self.p.packed_total else {}       # (only then: aligners without the keyword keep working)
             got = self.aligner.prefilter_rows(packed_reads.plane, pf_off, pf_len, max_len, [aidx[a] for a in a_list], [ks[a] for a in a_list],
-                                              packed=True)
+                                              packed=True, **kw)
             if got is None:
                 arena = packed_reads.materialize(self.aligner)
                 self.stats["packed_route_refused"] = self.stats.get("packed_route_refused", 0) + 1
