@@ -25,6 +25,7 @@
 #include "pc_slow.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
+#include "pc_prefilter_plan.h"
 
 #define PC_VERSION "porechop_amd 0.1 (gfx950)"
 
@@ -137,18 +138,15 @@ struct pc_ctx {
     DevBuf d_units;              // unit_prefix tables of the launches whose windows are cut into more than kMaxChunks chunks
     int len_hint = 0;            // pc_set_length_hint
     bool int16_only = false;     // pc_set_int16_only: never use the packed-fp16 kernel variants
-    // pc_prefilter_device: Eq tables + piece metadata of the last (adapter list, edit bounds), kept on the device
-    DevBuf d_pf_tables, d_pf_meta;
-    std::vector<int32_t> pf_key;             // adapters..., max_edits... of the cached tables
-    struct PfLaunch { int P, groups; size_t table_off, meta_off; };     // one kernel launch: `groups` groups of P pieces
-    std::vector<PfLaunch> pf_launches;       // the exhaustive kernel's launches over ALL pieces (fallback, PC_PF_NO_SEEDS=1)
-    std::vector<PfLaunch> pf_rest_launches;  // ... over the pieces the seed stage cannot take
-    int pf_warm = 0;
+    // the prefilter: the plan (pc_prefilter_plan.h) of the last (adapter list, edit bounds, route), its tables on the device
+    struct PfCache {
+        std::vector<int32_t> key;            // adapters..., max_edits..., route; empty: the device holds no plan
+        pcp::Plan plan;
+    } pf;
+    DevBuf d_pf_tables, d_pf_meta;           // exhaustive kernel: Eq tables + piece metadata
     // seed stage (pc_prefilter.hip seed_scan_kernel / seed_verify_kernel): bitmaps, q-gram -> entry ranges, entries,
     // the seeded pieces' metadata and Eq words; candidate list and its counter
     DevBuf d_sd_bitmaps, d_sd_first, d_sd_entries, d_sd_meta, d_sd_eq, d_sd_cand, d_sd_count;
-    int sd_nq = 0, sd_q[3] = {6, 6, 6}, sd_first_off[3] = {0, 0, 0}, sd_npieces = 0;
-    double sd_rate = 0.0;                    // expected candidates per read column
     unsigned long long *h_sd_count = nullptr;   // pinned host copy of the candidate count
     bool pf_defer_count = false;                // pc_prefilter_defer_count: no host round trip inside the prefilter
     int64_t pf_deferred_cap = 0;                // > 0: the last prefilter call left its count check to pc_prefilter_overflowed
@@ -179,16 +177,7 @@ namespace {
 
 int drift_period(const pc_ctx *c);
 
-int dna5(unsigned char c)
-{
-    switch (c) {
-        case 'A': case 'a': return 0;
-        case 'C': case 'c': return 1;
-        case 'G': case 'g': return 2;
-        case 'T': case 't': case 'U': case 'u': return 3;
-        default: return 4;
-    }
-}
+using pcp::dna5;
 
 #define HIP_TRY(x)                                                                              \
     do {                                                                                        \
@@ -273,7 +262,7 @@ int upload_panel(pc_ctx *c)
     HIP_TRY(hipMemcpy(c->d_ad_window.p, c->ad_window.data(), c->ad_window.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_ad_span.p, c->ad_span.data(), c->ad_span.size() * 4, hipMemcpyHostToDevice));
     c->panel_dirty = false;
-    c->pf_key.clear();
+    c->pf.key.clear();
     c->tiles_uploaded = false;
     c->last_max_len = -1;
     return PC_OK;
@@ -1501,72 +1490,40 @@ int pc_unpack_device(pc_ctx *c, const void *d_packed, int64_t nbases, const int6
     return pck::launch_unpack(d_packed, nbases, d_exc_pos, nexc, d_arena, pad_bytes, stream) ? PC_ERR_NO_DEVICE : PC_OK;
 }
 
-int pc_prefilter_max_edits(int adapter_len, double threshold_percent)
+int pc_prefilter_max_edits(int adapter_len, double threshold_percent) { return pcp::max_edits(adapter_len, threshold_percent); }
+
+// ---- the exact prefilter: one plan (pc_prefilter_plan.h) cached on the device, and the launches over it -------------------------
+namespace {
+
+static_assert(pcp::kBitmapWords == pck::kSeedBitmapWords, "the plan lays the seed bitmaps out as the scan kernels read them");
+
+int upload_plan(pc_ctx *c, const pcp::Plan &p, hipStream_t stream)
 {
-    // A hit has full-adapter identity 100 M / L >= threshold after the reference's %f rounding (six decimals;
-    // alignment.cpp:113-121 -> nanopore_read.py:476-491), L = alignment columns from the adapter's first to its
-    // last base, M <= adapter_len of them matches.  With tau = (threshold - 1e-6) / 100:  M >= tau L,  so the
-    // e = L - M non-matching columns -- each one unit-cost edit between the adapter and the read bases under its
-    // span -- number at most M (1 - tau) / tau <= adapter_len (1 - tau) / tau.
-    if (adapter_len <= 0) return -1;
-    const double tau = (threshold_percent - 1e-6) / 100.0;
-    if (!(tau > 0.0)) return adapter_len;                 // everything is a hit: nothing can be excluded
-    if (tau >= 1.0) return 0;
-    const double e = (double)adapter_len * (1.0 - tau) / tau;
-    const int k = (int)floor(e + 1e-9);                   // + 1e-9: never round a bound DOWN across an integer
-    return k > adapter_len ? adapter_len : k;
+    int rc;
+    if (p.nq > 0) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        if ((rc = c->d_sd_bitmaps.ensure(p.bitmaps.size() * 4)) || (rc = c->d_sd_first.ensure(p.first.size() * 4)) ||
+            (rc = c->d_sd_entries.ensure(p.entries.size() * 4)) || (rc = c->d_sd_meta.ensure(p.piece_meta.size() * 4)) ||
+            (rc = c->d_sd_eq.ensure(p.piece_eq.size() * 4)) || (rc = c->d_sd_count.ensure(64)))
+            return rc;
+        HIP_TRY(hipMemcpy(c->d_sd_bitmaps.p, p.bitmaps.data(), p.bitmaps.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_sd_first.p, p.first.data(), p.first.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_sd_entries.p, p.entries.data(), p.entries.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_sd_meta.p, p.piece_meta.data(), p.piece_meta.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_sd_eq.p, p.piece_eq.data(), p.piece_eq.size() * 4, hipMemcpyHostToDevice));
+        if (!c->h_sd_count) HIP_TRY(hipHostMalloc((void **)&c->h_sd_count, 64, hipHostMallocDefault));
+    }
+    // the tables of the previous list may still be read by a launch in flight on the caller's stream
+    HIP_TRY(hipStreamSynchronize(stream));
+    if ((rc = c->d_pf_tables.ensure(p.tables.size() * 4)) || (rc = c->d_pf_meta.ensure(p.meta.size() * 4))) return rc;
+    HIP_TRY(hipMemcpy(c->d_pf_tables.p, p.tables.data(), p.tables.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_pf_meta.p, p.meta.data(), p.meta.size() * 4, hipMemcpyHostToDevice));
+    return PC_OK;
 }
 
-static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                          int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
-                          uint32_t *d_mask, void *stream_v, int packed);
-enum { PF_BYTES = 0, PF_PLANE_SEEDS = 1, PF_PLANE_TOTAL = 2 };    // `packed` of prefilter_impl
-
-int pc_prefilter_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                        int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
-                        uint32_t *d_mask, void *stream_v)
-{
-    return prefilter_impl(c, d_arena, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, 0);
-}
-
-// The same decision over reads held at 2 bits per base (pc_pack_reads' plane; d_win_off counts BASES; the plane must be
-// 16-byte aligned and readable 64 bytes past its last base).  Only the seed stage exists for this form: every adapter must be
-// made of A/C/G/T(U) and seedable (parts of >= 6 bases, <= 7 edits) -- else PC_ERR_UNSUPPORTED_SCORES, and the caller unpacks
-// the reads and takes pc_prefilter_device.  Bases that were not A/C/G/T/U are seen as 'A': against such adapters that can only
-// add survivors, never remove one, so a cleared bit is still a proof.
-int pc_prefilter_packed(pc_ctx *c, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
-                        int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
-                        uint32_t *d_mask, void *stream_v)
-{
-    if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
-    return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, 1);
-}
-
-// pc_prefilter_packed for EVERY adapter list and bound: what the seed stage cannot take (and a batch whose candidate list
-// overflowed) runs the exhaustive kernel over the plane, prefilter_packed_kernel; adapter letters that are not A/C/G/T/U are
-// wildcards there (pc_prefilter.hip: a cleared bit is still a proof).  Never PC_ERR_UNSUPPORTED_SCORES.
-int pc_prefilter_packed_any(pc_ctx *c, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
-                            int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
-                            uint32_t *d_mask, void *stream_v)
-{
-    if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
-    return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, PF_PLANE_TOTAL);
-}
-
-int pc_unpack_windows(pc_ctx *c, const void *d_plane, const int64_t *d_exc_pos, int64_t nexc, const int64_t *d_src_off,
-                      const int32_t *d_len, int64_t n, void *d_dst, const int64_t *d_dst_off, int pad, void *stream_v)
-{
-    if (!c || n < 0 || nexc < 0) return PC_ERR_BAD_ARG;
-    if (n == 0) return PC_OK;
-    if (!d_plane || !d_src_off || !d_len || !d_dst || !d_dst_off || (nexc && !d_exc_pos) || ((uintptr_t)d_plane & 3u)) return PC_ERR_BAD_ARG;
-    (void)hipSetDevice(c->device);
-    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
-    return pck::launch_unpack_windows(d_plane, d_exc_pos, nexc, d_src_off, d_len, n, (uint8_t *)d_dst, d_dst_off, pad, stream) ? PC_ERR_NO_DEVICE : PC_OK;
-}
-
-static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                          int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
-                          uint32_t *d_mask, void *stream_v, int packed)
+int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                   int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
+                   uint32_t *d_mask, void *stream_v, pcp::Route route)
 {
     if (!c || nwindows < 0 || nadapters < 0 || max_len < 0) return PC_ERR_BAD_ARG;
     if (nwindows == 0 || nadapters == 0) return PC_OK;
@@ -1575,259 +1532,31 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     (void)hipSetDevice(c->device);
     hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
     const int words = (nadapters + 31) / 32;
+    const bool plane = route != pcp::Route::Bytes;
     std::vector<int32_t> key(adapters, adapters + nadapters);
     key.insert(key.end(), max_edits, max_edits + nadapters);
-    // (the seed tables differ between bytes and plane: q-gram orientation and base codes; the exhaustive kernel's between
-    // the two routes over the plane: [256][P] rows per group, never launched, or [4][P] with wildcards)
-    key.push_back(packed);
-    if (key != c->pf_key) {
-        // the cached seed / table state is rebuilt member by member below: until ALL of it is in place (the key is set last)
-        // no key may name it -- a failed upload half-way must not leave the old key over mixed tables
-        c->pf_key.clear();
-        // Pieces.  An adapter of at most 32 bases is one piece with its own bound.  A longer one that allows at most 8
-        // edits is represented by its FIRST 32 BASES with the same bound (within k edits of a substring, so is every
-        // substring of it: still a proof, and a 32-mer within <= 8 edits of random text is rare).  Beyond that it is cut
-        // into p = ceil(m / 32) pieces of nearly equal length, one of which lies within floor(k / p) (pigeonhole).
-        struct Piece { int adapter, begin, len, k, word; uint32_t bit; };
-        std::vector<Piece> pieces;
-        int warm = 0;
-        for (int j = 0; j < nadapters; ++j) {
-            const int ai = adapters[j];
-            if (ai < 0 || ai >= (int)c->adapters.size()) return PC_ERR_BAD_ARG;
-            const int m = (int)c->adapters[ai].size();
-            if (m <= 0) continue;                                     // an empty adapter never hits (failure record)
-            const int k = max_edits[j] < 0 ? m : max_edits[j];        // < 0: do not filter this adapter
-            if (m > 32 && k <= 8) {
-                pieces.push_back({ai, 0, 32, k, j / 32, 1u << (j % 32)});
-                warm = std::max(warm, 32 + k);
-                continue;
-            }
-            const int np = (m + 31) / 32;
-            int pos = 0;
-            for (int q = 0; q < np; ++q) {
-                const int len = m / np + (q < m % np ? 1 : 0);
-                pieces.push_back({ai, pos, len, k / np, j / 32, 1u << (j % 32)});
-                warm = std::max(warm, len + k / np);
-                pos += len;
-            }
-        }
-        // Launches: groups of 8 pieces per lane, the remainder r as one smaller group where an unused slot would cost
-        // more than a second pass over the reads (r = 5 -> 4 + 1, r = 6 -> 4 + 2; r = 3 -> 4, r = 7 -> 8 with a slot idle).
-        std::vector<pc_ctx::PfLaunch> launches;
-        std::vector<uint32_t> tables;
-        std::vector<int32_t> meta;
-        const size_t rows = packed == PF_PLANE_TOTAL ? 4 : 256;      // Eq rows per group: one per 2-bit code / per byte value
-        auto add_groups = [&](size_t first, size_t count, int P) {
-            const int groups = (int)((count + P - 1) / P);
-            pc_ctx::PfLaunch L{P, groups, tables.size(), meta.size()};
-            tables.resize(tables.size() + (size_t)groups * rows * P, 0xFFFFFFFFu);          // unused slots: all wildcards
-            meta.resize(meta.size() + (size_t)groups * P * 4, 0);
-            for (size_t i = 0; i < count; ++i) {
-                const Piece &pc = pieces[first + i];
-                const size_t g = i / P, slot = i % P;
-                const std::string &ad = c->adapters[pc.adapter];
-                const uint32_t wild = pc.len >= 32 ? 0u : (0xFFFFFFFFu >> pc.len);     // the bits below the piece
-                uint32_t eq_of_code[5];
-                for (int code = 0; code < 5; ++code) {
-                    uint32_t e = wild;
-                    for (int r = 0; r < pc.len; ++r)
-                        if (dna5((unsigned char)ad[pc.begin + r]) == code) e |= 1u << (32 - pc.len + r);
-                    eq_of_code[code] = e;
-                }
-                if (packed == PF_PLANE_TOTAL) {
-                    // the plane holds codes 0..3 only, a read's non-base among them as 0: an adapter letter that is not a
-                    // base (Dna5 code 4) matches all four, so that no match of the byte route (N == N) is lost
-                    for (size_t code = 0; code < 4; ++code) tables[L.table_off + (g * 4 + code) * P + slot] = eq_of_code[code] | (eq_of_code[4] & ~wild);
-                } else {
-                    for (int b = 0; b < 256; ++b) tables[L.table_off + (g * 256 + b) * P + slot] = eq_of_code[dna5((unsigned char)b)];
-                }
-                int32_t *mt = &meta[L.meta_off + (g * P + slot) * 4];
-                mt[0] = pc.len; mt[1] = pc.k; mt[2] = pc.word; mt[3] = (int32_t)pc.bit;
-            }
-            launches.push_back(L);
-        };
-        {
-            const size_t n = pieces.size(), n8 = n / 8 * 8, r = n - n8;
-            if (n8) add_groups(0, n8, 8);
-            switch (r) {
-                case 0: break;
-                case 1: add_groups(n8, 1, 1); break;
-                case 2: add_groups(n8, 2, 2); break;
-                case 3: case 4: add_groups(n8, r, 4); break;
-                case 5: add_groups(n8, 4, 4); add_groups(n8 + 4, 1, 1); break;
-                case 6: add_groups(n8, 4, 4); add_groups(n8 + 4, 2, 2); break;
-                default: add_groups(n8, r, 8); break;
-            }
-        }
-        const std::vector<pc_ctx::PfLaunch> all_launches = launches;
-        // ---- seed stage: which pieces it can take, and its tables ---------------------------------------------
-        // A piece of len bases with bound k is cut into k + 1 parts of floor/ceil(len / (k + 1)) bases; it is seeded
-        // when those parts are at least 6 bases long, k + 1 <= 8, and every seed is made of A/C/G/T.  Its seed length is
-        // min(8, floor(len / (k + 1))); up to three different lengths (6, 7, 8) each get their own bitmap.
-        struct Seed { int cls; uint32_t gram; int piece, off; };
-        std::vector<Seed> seeds;
-        std::vector<int> seeded_piece;            // indices into `pieces`
-        std::vector<size_t> rest_piece;
-        bool have_q[9] = {false, false, false, false, false, false, false, false, false};
-        static const bool no_seeds = [] { const char *e = getenv("PC_PF_NO_SEEDS"); return e && *e && *e != '0'; }();
-        // ONE seed length for all pieces -- the shortest any seeded piece needs: a longer part's seed is its first q bases, which an
-        // occurrence that leaves the part untouched contains just the same.  The scan then probes ONE bitmap per read base instead
-        // of one per seed length (its LDS probes and its 4 VALU operations per base and length were what bound it: DESIGN.md
-        // section 4); the price is a few more candidates for the verifier (an 8-base seed cut to 7 is found four times as often).
-        // PC_PF_MULTI_Q=1: a bitmap per seed length, as before.
-        // ... which pays for a handful of adapters (the headline's four: 9.2e-4 candidates per base instead of 7.3e-4) and not for
-        // a barcode panel (196 sequences, mostly 24-mers with 8-base seeds: 3.7e-2 instead of 9e-3 -- the verifier and the
-        // scan's own emit path then cost three times what the second probe did): one length only while the expected
-        // candidate rate stays below 2e-3 per base or within 1.5 x of the per-length rate.  PC_PF_MULTI_Q=1 / PC_PF_SINGLE_Q=1 force.
-        static const bool force_multi = [] { const char *e = getenv("PC_PF_MULTI_Q"); return e && *e && *e != '0'; }();
-        static const bool force_single = [] { const char *e = getenv("PC_PF_SINGLE_Q"); return e && *e && *e != '0'; }();
-        int q_common = 8;
-        for (const Piece &pc : pieces) {
-            const int parts = pc.k + 1;
-            const int q = std::min(8, pc.len / std::max(1, parts));
-            if (pc.k >= 0 && pc.k < pc.len && parts <= 8 && q >= 6) q_common = std::min(q_common, q);
-        }
-        double rate_multi = 0.0, rate_single = 0.0;
-        for (const Piece &pc : pieces) {
-            const int parts = pc.k + 1;
-            const int q = std::min(8, pc.len / std::max(1, parts));
-            if (pc.k >= 0 && pc.k < pc.len && parts <= 8 && q >= 6) {
-                rate_multi += (double)parts / (double)(1u << (2 * q));
-                rate_single += (double)parts / (double)(1u << (2 * q_common));
-            }
-        }
-        const bool multi_q = force_multi || (!force_single && rate_single > 2e-3 && rate_single > 1.5 * rate_multi);
-        for (size_t i = 0; i < pieces.size(); ++i) {
-            const Piece &pc = pieces[i];
-            const int parts = pc.k + 1;
-            int q = std::min(8, pc.len / std::max(1, parts));
-            bool ok = !no_seeds && pc.k >= 0 && pc.k < pc.len && parts <= 8 && q >= 6;
-            if (ok && !multi_q) q = q_common;
-            std::vector<Seed> mine;
-            if (ok) {
-                const std::string &ad = c->adapters[pc.adapter];
-                int pos = 0;
-                for (int t = 0; t < parts && ok; ++t) {
-                    const int plen = pc.len / parts + (t < pc.len % parts ? 1 : 0);
-                    uint32_t gram = 0;
-                    for (int r = 0; r < q; ++r) {
-                        const unsigned char ch = (unsigned char)ad[pc.begin + pos + r];
-                        if (dna5(ch) > 3) { ok = false; break; }
-                        // byte route: the seed scan's code of a base is bits 1-2 of its ASCII byte (A 0, C 1, T/U 2, G 3; either
-                        // case), first base in the HIGHEST bits; packed route: the plane's Dna ordinals, first base in the LOWEST
-                        if (packed) gram |= (uint32_t)dna5(ch) << (2 * r);
-                        else gram = (gram << 2) | (((uint32_t)ch >> 1) & 3u);
-                    }
-                    mine.push_back({q, gram, (int)seeded_piece.size(), pos});
-                    pos += plen;
-                }
-            }
-            if (ok && packed) {
-                const std::string &ad = c->adapters[pc.adapter];
-                for (char ch : ad) if (dna5((unsigned char)ch) > 3) ok = false;      // (an 'N' of the adapter would match the read's 'N')
-            }
-            if (ok) {
-                have_q[q] = true;
-                seeded_piece.push_back((int)i);
-                seeds.insert(seeds.end(), mine.begin(), mine.end());
-            } else {
-                rest_piece.push_back(i);
-            }
-        }
-        if (packed == PF_PLANE_SEEDS && !rest_piece.empty()) return PC_ERR_UNSUPPORTED_SCORES;   // this route has the seed stage only
-        c->sd_nq = 0;
-        int cls_of_q[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int q = 8; q >= 6; --q) if (have_q[q]) { cls_of_q[q] = c->sd_nq; c->sd_q[c->sd_nq++] = q; }
-        for (int t = c->sd_nq; t < 3; ++t) c->sd_q[t] = 6;
-        c->sd_npieces = (int)seeded_piece.size();
-        c->sd_rate = 0.0;
-        std::vector<pc_ctx::PfLaunch> rest_launches;
-        if (c->sd_nq > 0) {
-            std::vector<uint32_t> bitmaps(pck::kSeedBitmapWords, 0u);
-            const int bm_off[3] = {0, (1 << 16) / 32, (1 << 16) / 32 + (1 << 14) / 32};
-            for (Seed &sd : seeds) sd.cls = cls_of_q[sd.cls];
-            std::stable_sort(seeds.begin(), seeds.end(), [](const Seed &x, const Seed &y) { return x.cls != y.cls ? x.cls < y.cls : x.gram < y.gram; });
-            std::vector<uint32_t> first;
-            std::vector<int32_t> entries(seeds.size() * 4 + 4, 0);
-            size_t e = 0;
-            for (int cl = 0; cl < c->sd_nq; ++cl) {
-                const uint32_t ngram = 1u << (2 * c->sd_q[cl]);
-                c->sd_first_off[cl] = (int)first.size();
-                first.resize(first.size() + ngram + 1, 0u);
-                uint32_t *f = first.data() + c->sd_first_off[cl];
-                for (uint32_t g = 0; g < ngram; ++g) {
-                    f[g] = (uint32_t)e;
-                    while (e < seeds.size() && seeds[e].cls == cl && seeds[e].gram == g) {
-                        entries[e * 4] = seeds[e].piece; entries[e * 4 + 1] = seeds[e].off;
-                        bitmaps[bm_off[cl] + (g >> 5)] |= 1u << (g & 31);
-                        ++e;
-                    }
-                }
-                f[ngram] = (uint32_t)e;
-                c->sd_rate += (double)(f[ngram] - f[0]) / (double)ngram;
-            }
-            std::vector<int32_t> smeta((size_t)c->sd_npieces * 4 + 4, 0);
-            std::vector<uint32_t> seq((size_t)c->sd_npieces * 8 + 8, 0u);
-            for (int i = 0; i < c->sd_npieces; ++i) {
-                const Piece &pc = pieces[seeded_piece[i]];
-                smeta[i * 4] = pc.len; smeta[i * 4 + 1] = pc.k; smeta[i * 4 + 2] = pc.word; smeta[i * 4 + 3] = (int32_t)pc.bit;
-                const std::string &ad = c->adapters[pc.adapter];
-                const uint32_t wild = pc.len >= 32 ? 0u : (0xFFFFFFFFu >> pc.len);
-                for (int code = 0; code < 5; ++code) {
-                    uint32_t eq = wild;
-                    for (int r = 0; r < pc.len; ++r)
-                        if (dna5((unsigned char)ad[pc.begin + r]) == code) eq |= 1u << (32 - pc.len + r);
-                    seq[i * 8 + code] = eq;
-                }
-            }
-            // the rest (long pieces with large bounds, tiny adapters, seeds with an N) keeps the exhaustive kernel:
-            // its groups are appended to the same tables
-            launches.clear();
-            const std::vector<Piece> all = pieces;
-            pieces.clear();
-            for (size_t i : rest_piece) pieces.push_back(all[i]);
-            {
-                const size_t n = pieces.size(), n8 = n / 8 * 8, r = n - n8;
-                if (n8) add_groups(0, n8, 8);
-                switch (r) {
-                    case 0: break;
-                    case 1: add_groups(n8, 1, 1); break;
-                    case 2: add_groups(n8, 2, 2); break;
-                    case 3: case 4: add_groups(n8, r, 4); break;
-                    case 5: add_groups(n8, 4, 4); add_groups(n8 + 4, 1, 1); break;
-                    case 6: add_groups(n8, 4, 4); add_groups(n8 + 4, 2, 2); break;
-                    default: add_groups(n8, r, 8); break;
-                }
-            }
-            rest_launches = launches;
-            pieces = all;
-            HIP_TRY(hipStreamSynchronize(stream));
-            int rc2;
-            if ((rc2 = c->d_sd_bitmaps.ensure(bitmaps.size() * 4)) || (rc2 = c->d_sd_first.ensure(first.size() * 4)) ||
-                (rc2 = c->d_sd_entries.ensure(entries.size() * 4)) || (rc2 = c->d_sd_meta.ensure(smeta.size() * 4)) ||
-                (rc2 = c->d_sd_eq.ensure(seq.size() * 4)) || (rc2 = c->d_sd_count.ensure(64)))
-                return rc2;
-            HIP_TRY(hipMemcpy(c->d_sd_bitmaps.p, bitmaps.data(), bitmaps.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->d_sd_first.p, first.data(), first.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->d_sd_entries.p, entries.data(), entries.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->d_sd_meta.p, smeta.data(), smeta.size() * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(c->d_sd_eq.p, seq.data(), seq.size() * 4, hipMemcpyHostToDevice));
-            if (!c->h_sd_count) HIP_TRY(hipHostMalloc((void **)&c->h_sd_count, 64, hipHostMallocDefault));
-        }
-        launches = all_launches;
-        if (tables.empty()) { tables.assign(4, 0); meta.assign(4, 0); }
-
-        // the tables of the previous list may still be read by a launch in flight on the caller's stream
-        HIP_TRY(hipStreamSynchronize(stream));
-        int rc;
-        if ((rc = c->d_pf_tables.ensure(tables.size() * 4)) || (rc = c->d_pf_meta.ensure(meta.size() * 4))) return rc;
-        HIP_TRY(hipMemcpy(c->d_pf_tables.p, tables.data(), tables.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_pf_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice));
-        c->pf_key = key; c->pf_launches = launches; c->pf_rest_launches = rest_launches; c->pf_warm = warm;
+    key.push_back((int32_t)route);
+    if (key != c->pf.key) {
+        // PC_PF_NO_SEEDS=1: exhaustive kernel only; PC_PF_MULTI_Q=1 / PC_PF_SINGLE_Q=1 force the seed-length choice (read once per process)
+        static const pcp::Options options = [] {
+            auto on = [](const char *name) { const char *e = getenv(name); return e && *e && *e != '0'; };
+            pcp::Options o;
+            o.no_seeds = on("PC_PF_NO_SEEDS"); o.force_multi_q = on("PC_PF_MULTI_Q"); o.force_single_q = on("PC_PF_SINGLE_Q");
+            return o;
+        }();
+        pcp::Plan fresh;
+        if (pcp::build(c->adapters, adapters, max_edits, nadapters, route, options, fresh)) return PC_ERR_BAD_ARG;
+        if (route == pcp::Route::PlaneSeeds && !fresh.launches.empty() && !fresh.seeds_only) return PC_ERR_UNSUPPORTED_SCORES;
+        c->pf.key.clear();                    // from here on the device's tables are no longer the cached plan's
+        const int rc = upload_plan(c, fresh, stream);
+        if (rc) return rc;
+        c->pf.plan = std::move(fresh);
+        c->pf.key = std::move(key);
     }
+    const pcp::Plan &plan = c->pf.plan;
     HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)nwindows * words * 4, stream));
-    if (c->pf_launches.empty() || max_len == 0) return PC_OK;
-    if (packed == PF_PLANE_SEEDS && (c->sd_nq < 1 || !c->pf_rest_launches.empty())) return PC_ERR_UNSUPPORTED_SCORES;
+    if (plan.launches.empty() || max_len == 0) return PC_OK;
+    if (route == pcp::Route::PlaneSeeds && !plan.seeds_only) return PC_ERR_UNSUPPORTED_SCORES;    // this route has the seed stage only
     // column chunks: enough (window, chunk) units to fill the chip several times over, chunks no shorter than 512
     // columns (the warm-up before a chunk is the longest piece + its edit bound: ~35 columns)
     const int64_t target = (int64_t)c->ncu * 2048 * 6;
@@ -1841,30 +1570,26 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     pck::PrefilterArgs a;
     memset(&a, 0, sizeof a);
     a.arena = (const uint8_t *)d_arena; a.win_off = d_win_off; a.win_len = d_win_len; a.nwindows = nwindows;
-    a.chunks = (int32_t)chunks; a.chunk_len = chunk_len; a.warm = c->pf_warm;
+    a.chunks = (int32_t)chunks; a.chunk_len = chunk_len; a.warm = plan.warm;
     a.mask = d_mask; a.words = words;
     a.max_len = max_len; a.err = c->d_err.as<uint32_t>();
-    auto exhaustive = [&](const std::vector<pc_ctx::PfLaunch> &ls) -> int {
-        for (const pc_ctx::PfLaunch &L : ls) {
+    auto exhaustive = [&](const std::vector<pcp::Launch> &ls) -> int {
+        for (const pcp::Launch &L : ls) {
             a.tables = c->d_pf_tables.as<uint32_t>() + L.table_off; a.piece_meta = c->d_pf_meta.as<int32_t>() + L.meta_off;
-            if (packed == PF_PLANE_TOTAL ? pck::launch_prefilter_packed(a, L.P, L.groups, stream) : pck::launch_prefilter(a, L.P, L.groups, stream))
+            if (route == pcp::Route::PlaneTotal ? pck::launch_prefilter_packed(a, L.P, L.groups, stream) : pck::launch_prefilter(a, L.P, L.groups, stream))
                 return PC_ERR_NO_DEVICE;
         }
         return PC_OK;
     };
     ScopedTimer tm(c, stream, 4, nwindows * nadapters);              // the launches of one call are timed as ONE region
-    if (c->sd_nq == 0) return exhaustive(c->pf_launches);
+    if (plan.nq == 0) return exhaustive(plan.launches);
     // ---- seed stage: one pass over the reads finds the exact seeds, the finds are verified; the pieces without
     // seeds run the exhaustive kernel.  The candidate list is sized from the seeds' expected rate on random sequence
     // (x2 + slack, at most a sixteenth of the columns); a batch that overflows it -- low-complexity reads against a
     // low-complexity seed -- is redone by the exhaustive kernel: never much slower than that, never inexact.
-    double columns = 0.0;
-    {
-        const double typ = (c->len_hint > 0 && c->len_hint < max_len) ? (double)c->len_hint : (double)max_len;
-        columns = (double)nwindows * typ;
-    }
+    const double columns = (double)nwindows * ((c->len_hint > 0 && c->len_hint < max_len) ? (double)c->len_hint : (double)max_len);
     static const int64_t cap_env = [] { const char *e = getenv("PC_PF_SEED_CAP"); return e ? (int64_t)atoll(e) : (int64_t)0; }();
-    int64_t cap = (int64_t)std::min(columns * c->sd_rate * 2.0 + 1e6, std::max(4e6, columns / 16.0));
+    int64_t cap = (int64_t)std::min(columns * plan.rate * 2.0 + 1e6, std::max(4e6, columns / 16.0));
     if (cap_env > 0) cap = cap_env;
     int rc = c->d_sd_cand.ensure((size_t)cap * 8 + 64);
     if (rc) return rc;
@@ -1872,32 +1597,35 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
     pck::SeedScanArgs sa;
     memset(&sa, 0, sizeof sa);
     sa.arena = a.arena; sa.win_off = d_win_off; sa.win_len = d_win_len; sa.nwindows = nwindows;
-    sa.chunks = a.chunks; sa.chunk_len = a.chunk_len; sa.warm = c->sd_q[0] - 1;
-    sa.nq = c->sd_nq;
-    for (int t = 0; t < 3; ++t) sa.q[t] = c->sd_q[t];
+    sa.chunks = a.chunks; sa.chunk_len = a.chunk_len; sa.warm = plan.q[0] - 1;
+    sa.nq = plan.nq;
+    for (int t = 0; t < 3; ++t) sa.q[t] = plan.q[t];
     sa.bitmaps = c->d_sd_bitmaps.as<uint32_t>();
     sa.cand = c->d_sd_cand.as<uint32_t>(); sa.count = c->d_sd_count.as<unsigned long long>(); sa.cap = cap;
     sa.max_len = max_len; sa.err = c->d_err.as<uint32_t>();
     {
         ScopedTimer ts(c, stream, 5, nwindows);     // the scan alone (pairs = windows)
-        if (packed ? pck::launch_seed_scan_packed(sa, stream) : pck::launch_seed_scan(sa, stream)) return PC_ERR_NO_DEVICE;
+        if (plane ? pck::launch_seed_scan_packed(sa, stream) : pck::launch_seed_scan(sa, stream)) return PC_ERR_NO_DEVICE;
     }
-    if (packed != PF_PLANE_SEEDS && (rc = exhaustive(c->pf_rest_launches))) return rc;     // independent of the candidate count
+    if (route != pcp::Route::PlaneSeeds && (rc = exhaustive(plan.rest_launches))) return rc;     // independent of the candidate count
+    auto verify = [&](int64_t ncand) -> int {
+        pck::SeedVerifyArgs va;
+        memset(&va, 0, sizeof va);
+        va.arena = a.arena; va.win_off = d_win_off; va.win_len = d_win_len;
+        va.cand = c->d_sd_cand.as<uint32_t>(); va.count = c->d_sd_count.as<unsigned long long>(); va.cap = cap;
+        for (int t = 0; t < 3; ++t) { va.q[t] = plan.q[t]; va.first_off[t] = plan.first_off[t]; }
+        va.first = c->d_sd_first.as<uint32_t>(); va.entries = c->d_sd_entries.as<int32_t>();
+        va.piece_meta = c->d_sd_meta.as<int32_t>(); va.piece_eq = c->d_sd_eq.as<uint32_t>(); va.npieces = plan.npieces;
+        va.mask = d_mask; va.words = words;
+        return (plane ? pck::launch_seed_verify_packed(va, ncand, stream) : pck::launch_seed_verify(va, ncand, stream)) ? PC_ERR_NO_DEVICE : PC_OK;
+    };
     c->pf_deferred_cap = 0;
     if (c->pf_defer_count) {
         // No host round trip: the verify kernels read the count on the device (threads beyond it leave at once) and are
         // launched for the whole list; the count travels to pinned host memory behind them, and the caller -- who
         // synchronises anyway to size the DP over the survivors -- asks pc_prefilter_overflowed afterwards (an overflowed
         // list is the rare case: the caller then repeats the call with the count read here, below).
-        pck::SeedVerifyArgs va;
-        memset(&va, 0, sizeof va);
-        va.arena = a.arena; va.win_off = d_win_off; va.win_len = d_win_len;
-        va.cand = c->d_sd_cand.as<uint32_t>(); va.count = c->d_sd_count.as<unsigned long long>(); va.cap = cap;
-        for (int t = 0; t < 3; ++t) { va.q[t] = c->sd_q[t]; va.first_off[t] = c->sd_first_off[t]; }
-        va.first = c->d_sd_first.as<uint32_t>(); va.entries = c->d_sd_entries.as<int32_t>();
-        va.piece_meta = c->d_sd_meta.as<int32_t>(); va.piece_eq = c->d_sd_eq.as<uint32_t>(); va.npieces = c->sd_npieces;
-        va.mask = d_mask; va.words = words;
-        if (packed ? pck::launch_seed_verify_packed(va, cap, stream) : pck::launch_seed_verify(va, cap, stream)) return PC_ERR_NO_DEVICE;
+        if ((rc = verify(cap))) return rc;
         *c->h_sd_count = 0;
         HIP_TRY(hipMemcpyAsync(c->h_sd_count, c->d_sd_count.p, 8, hipMemcpyDeviceToHost, stream));
         c->pf_deferred_cap = cap;
@@ -1911,25 +1639,59 @@ static int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_o
         if (!told) fprintf(stderr, "porechop_amd: %llu seed candidates for a list of %lld: this batch is filtered by the exhaustive kernel\n",
                            found, (long long)cap);
         told = true;
-        if (packed == PF_PLANE_SEEDS) {
+        if (route == pcp::Route::PlaneSeeds) {
             // this route has no exhaustive kernel: nothing is excluded for this batch (every pair goes to the DP -- exact, only slower)
             HIP_TRY(hipMemsetAsync(d_mask, 0xFF, (size_t)nwindows * words * 4, stream));
             return PC_OK;
         }
         HIP_TRY(hipMemsetAsync(d_mask, 0, (size_t)nwindows * words * 4, stream));
-        return exhaustive(c->pf_launches);
+        return exhaustive(plan.launches);
     }
-    pck::SeedVerifyArgs va;
-    memset(&va, 0, sizeof va);
-    va.arena = a.arena; va.win_off = d_win_off; va.win_len = d_win_len;
-    va.cand = c->d_sd_cand.as<uint32_t>(); va.count = c->d_sd_count.as<unsigned long long>(); va.cap = cap;
-    for (int t = 0; t < 3; ++t) { va.q[t] = c->sd_q[t]; va.first_off[t] = c->sd_first_off[t]; }
-    va.first = c->d_sd_first.as<uint32_t>(); va.entries = c->d_sd_entries.as<int32_t>();
-    va.piece_meta = c->d_sd_meta.as<int32_t>(); va.piece_eq = c->d_sd_eq.as<uint32_t>(); va.npieces = c->sd_npieces;
-    va.mask = d_mask; va.words = words;
-    if (packed ? pck::launch_seed_verify_packed(va, (int64_t)found, stream) : pck::launch_seed_verify(va, (int64_t)found, stream)) return PC_ERR_NO_DEVICE;
-    return PC_OK;
+    return verify((int64_t)found);
+}
 
+}  // namespace
+
+int pc_prefilter_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                        int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
+                        uint32_t *d_mask, void *stream_v)
+{
+    return prefilter_impl(c, d_arena, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, pcp::Route::Bytes);
+}
+
+// The same decision over reads held at 2 bits per base (pc_pack_reads' plane; d_win_off counts BASES; the plane must be
+// 16-byte aligned and readable 64 bytes past its last base).  Only the seed stage exists for this form: every adapter must be
+// made of A/C/G/T(U) and seedable (parts of >= 6 bases, <= 7 edits) -- else PC_ERR_UNSUPPORTED_SCORES, and the caller unpacks
+// the reads and takes pc_prefilter_device.  Bases that were not A/C/G/T/U are seen as 'A': against such adapters that can only
+// add survivors, never remove one, so a cleared bit is still a proof.
+int pc_prefilter_packed(pc_ctx *c, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
+                        int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
+                        uint32_t *d_mask, void *stream_v)
+{
+    if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
+    return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, pcp::Route::PlaneSeeds);
+}
+
+// pc_prefilter_packed for EVERY adapter list and bound: what the seed stage cannot take (and a batch whose candidate list
+// overflowed) runs the exhaustive kernel over the plane, prefilter_packed_kernel; adapter letters that are not A/C/G/T/U are
+// wildcards there (pc_prefilter.hip: a cleared bit is still a proof).  Never PC_ERR_UNSUPPORTED_SCORES.
+int pc_prefilter_packed_any(pc_ctx *c, const void *d_plane, const int64_t *d_win_off, const int32_t *d_win_len,
+                            int64_t nwindows, int max_len, const int32_t *adapters, const int32_t *max_edits, int nadapters,
+                            uint32_t *d_mask, void *stream_v)
+{
+    if (((uintptr_t)d_plane & 15u) != 0) return PC_ERR_BAD_ARG;
+    return prefilter_impl(c, d_plane, d_win_off, d_win_len, nwindows, max_len, adapters, max_edits, nadapters, d_mask, stream_v, pcp::Route::PlaneTotal);
+}
+
+int pc_unpack_windows(pc_ctx *c, const void *d_plane, const int64_t *d_exc_pos, int64_t nexc, const int64_t *d_src_off,
+                      const int32_t *d_len, int64_t n, void *d_dst, const int64_t *d_dst_off, int pad, void *stream_v)
+{
+    if (!c || n < 0 || nexc < 0) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_plane || !d_src_off || !d_len || !d_dst || !d_dst_off || (nexc && !d_exc_pos) || ((uintptr_t)d_plane & 3u)) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    return pck::launch_unpack_windows(d_plane, d_exc_pos, nexc, d_src_off, d_len, n, (uint8_t *)d_dst, d_dst_off, pad, stream) ? PC_ERR_NO_DEVICE : PC_OK;
 }
 
 int pc_prefilter_defer_count(pc_ctx *c, int enabled)
