@@ -389,6 +389,28 @@ int pc_prefilter_overflowed(pc_ctx *ctx);
 int pc_unpack_windows(pc_ctx *ctx, const void *d_plane, const int64_t *d_exc_pos, int64_t nexc, const int64_t *d_src_off,
                       const int32_t *d_len, int64_t n, void *d_dst, const int64_t *d_dst_off, int pad, void *stream);
 
+/* Adapter discovery: the k-mer census of a set of windows (csrc/pc_discover.hip).  For every position p of every window
+ * with p + k <= d_win_len[i], d_counts[code] += 1, where code holds the k bases from p on at 2 bits each, the FIRST base
+ * in the highest bits, in SeqAn's Dna order: A 0, C 1, G 2, T 3, U as T, either case -- the byte -> code table of the
+ * scans (porechop/include/seqan/basic/alphabet_residue_tabs.h:113-140).  A k-mer that covers any other byte ('N', '-',
+ * IUPAC codes: all Dna5 'N') is not counted.  d_counts is the caller's dense uint32[4^k] table (4 <= k <= 13, else
+ * PC_ERR_BAD_ARG and nothing is launched; 268 MB at k = 13).  The call only ADDS: one table takes block after block of a
+ * streamed file; the caller zeroes it before the first.  Windows are described as for every scan (d_win_off int64 byte
+ * offsets into d_arena, d_win_len int32); they may start at any byte, overlap, repeat, and be shorter than k (such a
+ * window adds nothing); n = 0 is a no-op.  The arena is read as aligned dwords: only dwords that hold a byte of a window,
+ * so d_arena need only sit in an allocation that starts and ends on a 4-byte boundary.  Counters wrap at 2^32.
+ * Asynchronous on `stream`. */
+int pc_kmer_count(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len, int64_t n, int k,
+                  uint32_t *d_counts, void *stream);
+
+/* The entries of such a table with d_counts[code] >= min_count, as a list: entry i = (d_codes[i], d_cnt[i]), in no
+ * particular order, at most `cap` of them (cap >= 0; d_codes / d_cnt may be NULL when cap is 0).  *d_found (device memory,
+ * set by the call) = the number of qualifying entries WHETHER OR NOT they fitted: d_found[0] > cap means the list is
+ * incomplete -- call again with room for d_found[0] entries.  The call itself makes no host round trip; the caller
+ * reads d_found after synchronising the stream.  k as for pc_kmer_count.  Asynchronous on `stream`. */
+int pc_kmer_select(pc_ctx *ctx, const uint32_t *d_counts, int k, uint32_t min_count, int32_t *d_codes, uint32_t *d_cnt,
+                   int64_t cap, int64_t *d_found, void *stream);
+
 /* Debug builds of the 16-bit kernels (PC_CHECK_RANGE=1: packed-fp16 traced kernel, row classes 24/28/30/40;
  * PC_JIT_CHECK_RANGE=1: the run-time specialised score kernel) record the extremes of every DP value they
  * hold, in the kernel's own offset coordinates; this returns them since the last call and resets.  The

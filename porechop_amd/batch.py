@@ -491,6 +491,54 @@ class Aligner:
         out[:, rows] = bits.t()
         return out
 
+    # ---- adapter discovery: the k-mer census (pc_discover.hip) --------------------------------------------------------
+    def kmer_count(self, arena, win_off, win_len, k, counts=None, stream=None):
+        """counts[code] += 1 for every k-mer of the n windows (pc_kmer_count: 2 bits per base, first base highest, A C G T/U
+        = 0 1 2 3, k-mers over any other byte skipped).  arena uint8, win_off int64[n], win_len int32[n]: CUDA tensors;
+        counts: the int32 CUDA tensor [4^k] to add to (its bits are the library's uint32 counters), or None for a zeroed
+        one.  -> counts.  Asynchronous."""
+        import torch
+        k = int(k)
+        assert arena.is_cuda and arena.dtype == torch.uint8 and win_off.dtype == torch.int64 and win_len.dtype == torch.int32
+        assert win_off.is_contiguous() and win_len.is_contiguous() and win_off.shape[0] == win_len.shape[0]
+        if counts is None and 4 <= k <= 13:
+            counts = torch.zeros(1 << (2 * k), dtype=torch.int32, device=arena.device)
+        if counts is not None:
+            assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous() and int(counts.numel()) == 1 << (2 * k)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.pc_kmer_count(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), int(win_off.shape[0]), k,
+                                     None if counts is None else counts.data_ptr(), ctypes.c_void_p(s)), "pc_kmer_count")
+        return counts
+
+    def kmer_select(self, counts, k, min_count, cap, stream=None):
+        """The raw pc_kmer_select: -> (codes int32[cap], cnt int32[cap], found int64[1]) on the device.  The first
+        min(found, cap) entries are table entries with count >= min_count, in no particular order; found counts all of them."""
+        import torch
+        cap = int(cap)
+        codes = torch.empty(cap, dtype=torch.int32, device=counts.device)
+        cnt = torch.empty(cap, dtype=torch.int32, device=counts.device)
+        found = torch.empty(1, dtype=torch.int64, device=counts.device)
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous()
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.pc_kmer_select(self._ctx, counts.data_ptr(), int(k), int(min_count), codes.data_ptr() if cap else None,
+                                      cnt.data_ptr() if cap else None, cap, found.data_ptr(), ctypes.c_void_p(s)), "pc_kmer_select")
+        return codes, cnt, found
+
+    def kmer_candidates(self, counts, k, min_count, cap=1 << 16):
+        """The k-mers seen at least min_count times -> (codes int64[m], counts int64[m]) as numpy arrays, sorted by count
+        descending, then code ascending.  `cap` sizes the first list; an overflow is retried with the size the cursor reported."""
+        assert int(counts.numel()) == 1 << (2 * int(k))
+        while True:
+            codes, cnt, found = self.kmer_select(counts, k, min_count, cap)
+            m = int(found.item())                           # (synchronises)
+            if m <= cap:
+                break
+            cap = m
+        codes = codes[:m].cpu().numpy().astype(np.int64)
+        cnt = cnt[:m].cpu().numpy().view(np.uint32).astype(np.int64)
+        order = np.lexsort((codes, -cnt))
+        return codes[order], cnt[order]
+
     def debug_value_range(self):
         """(lo, hi) of the DP values the range-checking kernel builds have held since the last call."""
         lo, hi = ctypes.c_int32(), ctypes.c_int32()

@@ -1455,6 +1455,28 @@ int pc_middle_hits(pc_ctx *c, const int32_t *d_records, int64_t n, double thresh
     return pck::launch_middle_hits(d_records, n, threshold, d_full, d_hit, stream) ? PC_ERR_NO_DEVICE : PC_OK;
 }
 
+// ---- adapter discovery: the k-mer census and its candidate list (pc_discover.hip) ---------------------------------------------
+int pc_kmer_count(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len, int64_t n, int k, uint32_t *d_counts,
+                  void *stream_v)
+{
+    if (!c || k < 4 || k > 13 || n < 0) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !d_counts) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    return pck::launch_kmer_count((const uint8_t *)d_arena, d_win_off, d_win_len, n, k, d_counts, stream) ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
+int pc_kmer_select(pc_ctx *c, const uint32_t *d_counts, int k, uint32_t min_count, int32_t *d_codes, uint32_t *d_cnt, int64_t cap,
+                   int64_t *d_found, void *stream_v)
+{
+    if (!c || k < 4 || k > 13 || cap < 0 || !d_counts || !d_found || (cap > 0 && (!d_codes || !d_cnt))) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipMemsetAsync(d_found, 0, 8, stream));
+    return pck::launch_kmer_select(d_counts, k, min_count, d_codes, d_cnt, cap, (unsigned long long *)d_found, stream) ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
 int pc_group_survivors(pc_ctx *c, const int32_t *d_mask, int64_t n, int words, const int32_t *d_gmask, int ngroups, uint8_t *d_cand,
                        int64_t *d_counts, void *stream_v)
 {

@@ -308,6 +308,12 @@ int launch_round_consume(const double *full_all, const int32_t *rec_all, const i
 int launch_plan(const PlanArgs &a, void *stream);
 int trace_words_per_col(int rows);   // NW
 
+// the k-mer census of adapter discovery (pc_discover.hip): counts[code] += 1 for every k-mer of every window that holds
+// bases only (4 <= k <= 13, checked by the caller); the qualifying entries of such a table as a capped list
+int launch_kmer_count(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len, int64_t n, int k, uint32_t *counts, void *stream);
+int launch_kmer_select(const uint32_t *counts, int k, uint32_t min_count, int32_t *codes, uint32_t *cnt, int64_t cap,
+                       unsigned long long *found, void *stream);
+
 // 2-bit plane (+ exception positions) -> bytes 'A','C','G','T' / 'N', followed by `pad` bytes of 'N' (pc_reduce.hip)
 int launch_unpack(const void *packed, int64_t nbases, const int64_t *exc_pos, int64_t nexc, void *arena, int pad, void *stream);
 
