@@ -334,10 +334,13 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
         const int window = std::max(c->ad_window[ad], adb >= 0 ? c->ad_window[adb] : 0);
         const bool two_pass_job = (mode == PC_MODE_TWO_PASS) || (mode == PC_MODE_SCORE) || (mode == PC_MODE_TRACE_AT) ||
                                   (mode == PC_MODE_AUTO && max_len > 2 * window + 64);
-        // A dual tile runs both halves with the longer adapter's rows and saves nothing but the second
-        // read stream -- which matters for whole reads (8 kB per window), not for 150-byte end windows:
-        // there, two adapters of different row classes cost fewer rows as two single-adapter jobs
-        // (same tile count, same output layout).
+        // A dual tile runs both halves with the longer adapter's rows and saves the second read stream and
+        // the second byte -> row lookup per column.  For whole reads that is worth more than the padding
+        // rows -- measured on the headline's four middle adapters, 1 M x 8 kb reads: (33 | 30) + (28 | 22)
+        // dual 74.6 ms of pc_spec_score per step, the four adapters alone with two streams per lane 81.3 ms,
+        // where dropping the 9 padded rows of 122 could have saved 5.5 ms (profiles/score_layout_ab.txt) --
+        // so two-pass jobs stay dual.  For 150-byte end windows two adapters of different row classes cost
+        // fewer rows as two single-adapter jobs (same tile count, same output layout).
         bool pa_ = false, pb_ = false;
         static const bool no_split = [] { const char *e = getenv("PC_NO_SPLIT_DUAL"); return e && *e && *e != '0'; }();
         const bool split_dual = adb >= 0 && !two_pass_job && !no_drift && !no_split &&

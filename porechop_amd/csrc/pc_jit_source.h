@@ -121,21 +121,22 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
     // packed terms, 1-4 KB instead of a row per byte value -- LDS no longer limits the waves per CU --
     // and the two bytes of a column reach their row through two small byte -> row-offset tables
     __shared__ uint4 s_tab[25 * K / 4];
-    __shared__ unsigned short lut_lo[256], lut_hi[256];      // row offsets in uint4 units
+    // (all three tables hold row offsets in BYTES, at most 24 * 16 * K / 4 < 2^16: a row's address is one add)
+    __shared__ unsigned short lut_lo[256], lut_hi[256];
 #if PC_DUAL
     // two DIFFERENT adapters only ever share a tile whose halves read the same windows (pc_api.cpp
     // build_tiles): one byte stream per lane, and the byte -> table row lookup is a single read
-    __shared__ unsigned short lut_one[256];
+    __shared__ unsigned short lut_one[256];                  // byte offset of row code * 6
 #endif
     const int lane = threadIdx.x;
     for (int i = lane; i < 25 * K / 4; i += 64) s_tab[i] = ((const uint4 *)a.s_table)[i];
     for (int c = lane; c < 256; c += 64) {
         const int code = (c == 'A' || c == 'a') ? 0 : (c == 'C' || c == 'c') ? 1 : (c == 'G' || c == 'g') ? 2
                        : (c == 'T' || c == 't' || c == 'U' || c == 'u') ? 3 : 4;
-        lut_lo[c] = (unsigned short)(code * 5 * (K / 4));
-        lut_hi[c] = (unsigned short)(code * (K / 4));
+        lut_lo[c] = (unsigned short)(code * 5 * (K / 4) * 16);
+        lut_hi[c] = (unsigned short)(code * (K / 4) * 16);
 #if PC_DUAL
-        lut_one[c] = (unsigned short)(code * 6 * (K / 4));
+        lut_one[c] = (unsigned short)(code * 6 * (K / 4) * 16);
 #endif
     }
     __syncthreads();
@@ -275,9 +276,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #endif
         auto fetch_S = [&](u32 (&S)[K], u32 bl, u32 bh) {
 #if PC_DUAL
-            const uint4 *row = s_tab + (u32)lut_one[bl];
+            const uint4 *row = (const uint4 *)((const char *)s_tab + (u32)lut_one[bl]);
 #else
-            const uint4 *row = s_tab + ((u32)lut_lo[bl] + (u32)lut_hi[one_stream ? bl : bh]);
+            const uint4 *row = (const uint4 *)((const char *)s_tab + ((u32)lut_lo[bl] + (u32)lut_hi[one_stream ? bl : bh]));
 #endif
 #pragma clang loop unroll(full)
             for (int q = 0; q < K / 4; ++q) { const uint4 v = row[q]; S[4*q] = v.x; S[4*q+1] = v.y; S[4*q+2] = v.z; S[4*q+3] = v.w; }
@@ -360,13 +361,18 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                     u32 mn, vs0, vs1;
                     if (r + 1 + KP < R) {
                         const int q = r + KP;
+                        // row q's diagonal is T[q - 1] = T[r + 1], which this statement also produces (its last instruction,
+                        // after the read): ONE in-out operand, so the register is updated in place.  As a separate input
+                        // beside an early-clobber output it cost a copy per row pair -- and the first column's copies were
+                        // hoisted above the branch, into the block-resolved path (profiles/score_block_audit.txt)
+                        static_assert(KP == 2, "the tied operand below is T[q - 1] = T[r + 1]");
                         asm volatile(
-                            PC_ROW_FULL("%[vprev]", "%[tup]", "%[d0]", "%[s0]", "%[u0]", "%[t0]", "%[dhr0]", "%[ur0]", "%[tn0]", "%[dhq0]", "%[vs0]")
+                            PC_ROW_FULL("%[vprev]", "%[tup]", "%[tn1]", "%[s0]", "%[u0]", "%[t0]", "%[dhr0]", "%[ur0]", "%[tn0]", "%[dhq0]", "%[vs0]")
                             PC_ROW_FULL("%[vs0]", "%[tn0]", "%[t0]", "%[s1]", "%[u1]", "%[t1]", "%[dhr1]", "%[ur1]", "%[tn1]", "%[dhq1]", "%[vs1]")
                             : [mn] "=&v"(mn), [vs0] "=&v"(vs0), [vs1] "=&v"(vs1),
-                              [u0] "+v"(U[q]), [u1] "+v"(U[q + 1]), [tn0] "=&v"(T[r]), [tn1] "=&v"(T[r + 1]),
+                              [u0] "+v"(U[q]), [u1] "+v"(U[q + 1]), [tn0] "=&v"(T[r]), [tn1] "+v"(T[r + 1]),
                               [dhq0] "=&v"(dh[q]), [dhq1] "=&v"(dh[q + 1])
-                            : [vprev] "v"(Vprev), [tup] "v"(Tup), [oe] "s"(OE2), [d0] "v"(T[q - 1]),
+                            : [vprev] "v"(Vprev), [tup] "v"(Tup), [oe] "s"(OE2),
                               [t0] "v"(T[q]), [t1] "v"(T[q + 1]), [s0] "v"(S[COMBO[q]]), [s1] "v"(S[COMBO[q + 1]]),
                               [dhr0] "v"(dh[r]), [dhr1] "v"(dh[r + 1]), [ur0] "v"(U[r]), [ur1] "v"(U[r + 1]));
                         PC_NOTE_V(dh[r]) PC_NOTE_V(dh[r + 1]) PC_NOTE_V(vs0) PC_NOTE_V(vs1)
@@ -659,7 +665,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 const u32 *srow = (const u32 *)s_tab;
                 const int bl = ev_lo ? w_lo[n_lo - 1] : 0;
                 const int bh = one_stream ? bl : (ev_hi ? w_hi[n_hi - 1] : 0);
-                const u32 rowbase = 4 * ((u32)lut_lo[bl] + (u32)lut_hi[bh]);
+                const u32 rowbase = ((u32)lut_lo[bl] + (u32)lut_hi[bh]) / 4;
 #pragma unroll 1
                 for (int r = 0; r < R; ++r) {
                     const uint2 ol = ev_lo ? fin[r * 64 + lane] : make_uint2(0u, 0u);
