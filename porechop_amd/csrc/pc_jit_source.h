@@ -13,11 +13,13 @@
 //     renormalisation, C a centring constant; T = M + gap_open is kept one step ahead,
 //     T~ = T + (rho + jj + 1) * eps - C.  A gap extension moves one row or one column and costs
 //     -eps, so in these coordinates it is free:
-//         H~(rho,j) = max(H~(rho,j-1), T~(rho,j-1))          (no  H + e)
+//         H~(rho,j) = max(H~(rho,j-1), T~(rho,j-1))          (no  H + e;  U[rho] holds H~(rho,j-1) entering column j --
+//                                                             except on the fp16 fast path, point 3)
 //         V~(rho,j) = max(V~(rho-1,j), T~(rho-1,j))          (no  V + e)
 //         d~        = T~(rho-1,j-1) + S~,   S~ = sub - open + eps   (folded into the table)
 //         M~        = max3(d~, H~, V~);     T~ = M~ + (open + eps)
-//     5 packed ops per cell pair with fp16's 3-input max (v_pk_maximum3_f16), 6 with int16.  The
+//     5 packed ops per cell pair with fp16's 3-input max (v_pk_maximum3_f16), 6 with int16: the ONE-column path of both
+//     lane types and the int16 column pair.  The packed-fp16 column pair (point 3) needs 4.75.  The
 //     values are the same integers as the reference's, only offset by a known amount, so results
 //     are bit-identical: row 0 (M = 0) becomes the per-column scalar `top`, the tracked last-row
 //     score is T~(R,j) - top(j) = M(R,j) + R*eps, compared with strict '>' like dp_scout.h.
@@ -25,8 +27,24 @@
 //     (2R+1 ops per PC_KREN columns).  PC_KREN and C are chosen by the host so that every value
 //     ever formed is an integer fp16 (|v| <= 2048) or int16 represents exactly (pc_jit.cpp).
 //
-//  3. Two columns per wave, skewed by three rows (column2 below): two independent dependency chains
-//     interleaved instruction by instruction instead of one chain padded with wait states.
+//  3. Two columns per wave (column2 below, the block-resolved fast path): two dependency chains, column j and
+//     column j+1 behind it, interleaved instruction by instruction instead of one chain padded with wait states.
+//     Packed fp16: blocked 2 x 2, 19 ops per two rows and two columns = 4.75 per cell pair.  max is associative
+//     and idempotent and the 3-input max costs one op, so H is materialised only every second column and V only
+//     every second row:
+//         Vb     = max3(Vb of the pair above, T~(e-2,.), T~(e-1,.))       V~ of the even row e of a row pair (e, o)
+//         M(e,j)   = max3(d, U[e], Vb)                       M(o,j)   = max(max3(d, U[o], Vb), T~(e,j))
+//         M(e,j+1) = max(max3(d', U[e], T~(e,j)), Vb')       M(o,j+1) = max3(max3(d', U[o], T~(o,j)), Vb', T~(e,j+1))
+//         U[.]   = max3(U[.], T~(.,j), T~(.,j+1))                         once per column pair
+//     11 maxima + 8 adds.  On this path U[rho] is ONE COLUMN AHEAD: it holds H~(rho, j) of the coming column j,
+//     where the one-column path keeps H~(rho, j-1).  Entering the fast path converts, U = max(U, T), once per
+//     entry; leaving it needs nothing, because the one-column path forms max(U, T), which is then U itself (the
+//     same holds for the parked last-column state and for the renormalisation, which shifts T and U alike).
+//     Every value formed is a maximum of values the five-op recurrence forms: same results, same range proof.
+//     Chain B runs one row pair behind chain A; column j lives in registers of its own (X[]) for the two
+//     statements until B has used it, so that every loop-carried T[r] keeps its register (see column2).
+//     Packed int16 has no 3-input max: its column pair keeps six ops per cell pair, U = H~(rho, j-1), and the
+//     skew of three rows.
 //
 // Padding rows (shorter adapter of a pair) use a letter whose substitution score is 0, which
 // keeps M = 0 like row 0.  The kernel is score-only (pass 1 of the whole-read scan) and
@@ -416,6 +434,187 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
             return cand;
         };
 
+#if PC_F16
+        // Two columns at once, blocked 2 x 2: 19 packed ops per two rows and two columns instead of 20.
+        // max is associative and idempotent and v_pk_maximum3_f16 takes three inputs for the price of one op,
+        // so H is materialised only every second column and V only every second row:
+        //   * U[r] holds H~(rho, j) of the coming EVEN column j (the one-column path: H~(rho, j-1)), and is
+        //     brought up to date once per column pair, U = max3(U, T(., j), T(., j+1));
+        //   * Vb is the V~ of the even row of a row pair, Vb = max3(Vb of the pair above, T(e-2, .), T(e-1, .)).
+        // Per row pair (e, o) and column pair (j, j+1), chain A = column j, chain B = column j+1:
+        //   A  Vb = max3(Vb, T(e-2,j), T(e-1,j))        M(e,j)   = max3(d, U[e], Vb)
+        //                                               M(o,j)   = max(max3(d, U[o], Vb), T(e,j))
+        //   B  Vb' = max3(Vb', T(e-2,j+1), T(e-1,j+1))  M(e,j+1) = max(max3(d', U[e], T(e,j)), Vb')
+        //                                               M(o,j+1) = max3(max3(d', U[o], T(o,j)), Vb', T(e,j+1))
+        //      U[e] = max3(U[e], T(e,j), T(e,j+1));  U[o] likewise
+        // 11 maxima + 4 d + 4 T = 19 ops; the dependent chain per row pair and column is 5 ops (Vb, M, T, M, T).
+        // Every value formed is a maximum of values the one-column recurrence forms, so results and the range
+        // proof (pc_bounds.h spec_plan) are unchanged.  An odd last row runs as an even-type row on its own.
+        //
+        // Chain B runs ONE row pair behind chain A.  Each asm statement carries a row pair of A and the pair
+        // above it of B, interleaved instruction by instruction so that no op reads the result of the op
+        // before it: no s_nop in the steady state.  Registers: the U update reads T(., j) and T(., j+1)
+        // together, so column j cannot be formed in place.  A writes it to X[] -- short-lived, a row's X dies
+        // two statements later -- and T[r] goes T(r, j-1) -> d'(r) -> T(r, j+1) in ONE register: B forms
+        // its diagonal term for row r in T[r] as soon as A has read the old value (an in-out operand, read
+        // by A's d and then written), and its new T in place of that term.  Every loop-carried value thus
+        // keeps its register from column pair to column pair and the allocator has nothing to rotate.
+        // Only for blocks in which every stream of the tile tracks the columns and none ends (the caller's
+        // fast path, which converts U on entry).
+        auto column2 = [&](const u32 (&S1)[K], const u32 (&S2)[K], u32 &c1, u32 &c2) {
+            constexpr int NU = (R + 1) / 2;                                    // units: row pairs, then an odd last row alone
+            const u32 topA = pk_add(top, EPS2), topB = pk_add(topA, EPS2);     // T~(0,j), T~(0,j+1)
+            u32 X[R], dA[R];                                                   // column j; chain A's d of the rows in flight
+#define PC_M3 "v_pk_maximum3_f16"
+#define PC_NOP "s_nop 0\n\t"
+            // chain A: Vb, M(e), d(e+2), T(e), x(o), M(o), T(o), d(e+3)       (ta0 / ta1 = X[e] / X[o]; to1 / ta2 = T(o, j-1) / T(e+2, j-1);
+            // beside chain B, T(o, j-1) is B's in-out operand db3: PC_A7I)
+#define PC_A1 PC_M3 " %[va], %[vpa], %[tf], %[tg]\n\t"
+#define PC_A2 PC_M3 " %[ta0], %[da0], %[ua0], %[va]\n\t"
+#define PC_A7 PC_ADD " %[da2], %[to1], %[sa2]\n\t"
+#define PC_A7I PC_ADD " %[da2], %[db3], %[sa2]\n\t"
+#define PC_A3 PC_ADD " %[ta0], %[ta0], %[oe]\n\t"
+#define PC_A4 PC_M3 " %[ta1], %[da1], %[ua1], %[va]\n\t"
+#define PC_A5 PC_MAX " %[ta1], %[ta1], %[ta0]\n\t"
+#define PC_A6 PC_ADD " %[ta1], %[ta1], %[oe]\n\t"
+#define PC_A8 PC_ADD " %[da3], %[ta2], %[sa3]\n\t"
+            // chain B: Vb', y(e), M(e), T(e), z(o), M(o), T(o), U[e], U[o], d'(e+2), d'(e+3)   (tb0 / tb1 = T[e] / T[o], which enter as
+            // d'(e) / d'(o); tf / tg = X[e] / X[o]; db2 / db3 = T[e+2] / T[e+3])
+#define PC_B1 PC_M3 " %[vb], %[vpb], %[tbm2], %[tbm1]\n\t"
+#define PC_B2 PC_M3 " %[tb0], %[tb0], %[ub0], %[tf]\n\t"
+#define PC_B3 PC_MAX " %[tb0], %[tb0], %[vb]\n\t"
+#define PC_B4 PC_ADD " %[tb0], %[tb0], %[oe]\n\t"
+#define PC_B5 PC_M3 " %[tb1], %[tb1], %[ub1], %[tg]\n\t"
+#define PC_B6 PC_M3 " %[tb1], %[tb1], %[vb], %[tb0]\n\t"
+#define PC_B7 PC_ADD " %[tb1], %[tb1], %[oe]\n\t"
+#define PC_B8 PC_M3 " %[ub0], %[ub0], %[tf], %[tb0]\n\t"
+#define PC_B9 PC_M3 " %[ub1], %[ub1], %[tg], %[tb1]\n\t"
+#define PC_B10 PC_ADD " %[db2], %[tg], %[sb2]\n\t"
+            // a pair of A with the pair above it of B; D2 / D3: A's look-ahead terms d(e+2) / d(e+3), where those rows exist
+            // (B's d'(e+3) reads the T(e+2, j) = ta0 that A forms in this statement)
+#define PC_AB(D2, D3)                                                                  \
+    PC_A1 PC_B1 PC_A2 PC_B2 D2 PC_B3 PC_A3 PC_B4 PC_A4 PC_B5 PC_A5 PC_B6 PC_A6 PC_B8  \
+    D3 PC_B7 PC_B10 PC_ADD " %[db3], %[ta0], %[sb3]\n\t" PC_B9
+            // the odd last row of A with the last pair of B
+#define PC_AB_ODD                                                                      \
+    PC_A1 PC_B1 PC_A2 PC_B2 PC_B5 PC_B3 PC_A3 PC_B4 PC_B10 PC_B6 PC_B8 PC_B7 PC_NOP PC_B9
+            // one chain on its own: A's first unit, B's last
+#define PC_A_PAIR(D2, D3) D2 PC_A1 D3 PC_A2 PC_A4 PC_A3 PC_NOP PC_A5 PC_NOP PC_A6
+#define PC_A_ODD PC_A1 PC_NOP PC_A2 PC_NOP PC_A3
+#define PC_B_PAIR PC_B2 PC_B1 PC_B5 PC_B3 PC_NOP PC_B4 PC_NOP PC_B6 PC_B8 PC_B7 PC_NOP PC_B9
+#define PC_B_ODD PC_B2 PC_B1 PC_NOP PC_B3 PC_NOP PC_B4 PC_NOP PC_B8
+            auto dterm = [&](u32 &d, u32 diag, u32 s) { asm volatile(PC_ADD " %[d], %[g], %[s]" : [d] "=v"(d) : [g] "v"(diag), [s] "v"(s)); };
+            u32 VbA = NEG2, VbB = NEG2;
+            // ---- chain A alone: its first unit (rows 0 and 1); T(-2, .) = -infinity, T(-1, .) = the top row
+            dterm(dA[0], top, S1[COMBO[0]]);
+            if constexpr (R > 1) dterm(dA[1], T[0], S1[COMBO[1]]);
+            {
+                u32 va;
+                if constexpr (R >= 4) {
+                    asm volatile(PC_A_PAIR(PC_A7, PC_A8)
+                                 : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1]), [da2] "=&v"(dA[2]), [da3] "=&v"(dA[3])
+                                 : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
+                                   [ua0] "v"(U[0]), [ua1] "v"(U[1]), [to1] "v"(T[1]), [sa2] "v"(S1[COMBO[2]]), [sa3] "v"(S1[COMBO[3]]), [ta2] "v"(T[2]));
+                } else if constexpr (R == 3) {
+                    asm volatile(PC_A_PAIR(PC_A7, PC_NOP)
+                                 : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1]), [da2] "=&v"(dA[2])
+                                 : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
+                                   [ua0] "v"(U[0]), [ua1] "v"(U[1]), [to1] "v"(T[1]), [sa2] "v"(S1[COMBO[2]]));
+                } else if constexpr (R == 2) {
+                    asm volatile(PC_A_PAIR("", PC_NOP)
+                                 : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1])
+                                 : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
+                                   [ua0] "v"(U[0]), [ua1] "v"(U[1]));
+                } else {
+                    asm volatile(PC_A_ODD
+                                 : [va] "=&v"(va), [ta0] "=&v"(X[0])
+                                 : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [ua0] "v"(U[0]));
+                }
+                VbA = va;
+            }
+            // ---- chain B starts: its rows 0 and 1 read column j's top row and T(0), which A has produced
+            // (its d' go where the rows' old T was: in-out, so that the register stays the row's)
+            auto dterm_b = [&](u32 &t, u32 diag, u32 s) { asm volatile(PC_ADD " %[t], %[g], %[s]" : [t] "+v"(t) : [g] "v"(diag), [s] "v"(s)); };
+            dterm_b(T[0], topA, S2[COMBO[0]]);
+            if constexpr (R > 1) dterm_b(T[1], X[0], S2[COMBO[1]]);
+#pragma clang loop unroll(full)
+            for (int u = 1; u < NU; ++u) {
+                const int e = 2 * u, f = e - 2;                                // A: rows e, e+1; B: rows f, f+1
+                const u32 tbm2 = f ? T[f - 2] : NEG2, tbm1 = f ? T[f - 1] : topB;
+                u32 va, vb;
+#define PC_AB_OUT  [va] "=&v"(va), [vb] "=&v"(vb), [ta0] "=&v"(X[e]), [tb0] "+v"(T[f]), [tb1] "+v"(T[f + 1]), \
+                   [ub0] "+v"(U[f]), [ub1] "+v"(U[f + 1]), [db2] "+v"(T[e])
+#define PC_AB_IN   [vpa] "v"(VbA), [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [tg] "v"(X[f + 1]), \
+                   [oe] "s"(OE2), [da0] "v"(dA[e]), [ua0] "v"(U[e]), [sb2] "v"(S2[COMBO[f + 2]])
+                if (e + 3 < R) {
+                    asm volatile(PC_AB(PC_A7I, PC_A8)
+                                 : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1]), [da2] "=&v"(dA[e + 2]), [da3] "=&v"(dA[e + 3])
+                                 : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]),
+                                   [sa2] "v"(S1[COMBO[e + 2]]), [sa3] "v"(S1[COMBO[e + 3]]), [ta2] "v"(T[e + 2]));
+                } else if (e + 2 < R) {
+                    asm volatile(PC_AB(PC_A7I, "")
+                                 : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1]), [da2] "=&v"(dA[e + 2])
+                                 : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]),
+                                   [sa2] "v"(S1[COMBO[e + 2]]));
+                } else if (e + 1 < R) {
+                    asm volatile(PC_AB(PC_NOP, "")
+                                 : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1])
+                                 : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]));
+                } else {
+                    asm volatile(PC_AB_ODD : PC_AB_OUT : PC_AB_IN);
+                }
+#undef PC_AB_OUT
+#undef PC_AB_IN
+                VbA = va; VbB = vb;
+            }
+            c1 = pk_sub(X[R - 1], topA);               // column j's last row
+            // ---- chain B alone: its last unit
+            {
+                constexpr int f = 2 * (NU - 1);
+                const u32 tbm2 = f ? T[f - 2] : NEG2, tbm1 = f ? T[f - 1] : topB;
+                u32 vb;
+                if constexpr (f + 1 < R) {
+                    asm volatile(PC_B_PAIR
+                                 : [vb] "=&v"(vb), [tb0] "+v"(T[f]), [tb1] "+v"(T[f + 1]), [ub0] "+v"(U[f]), [ub1] "+v"(U[f + 1])
+                                 : [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [tg] "v"(X[f + 1]), [oe] "s"(OE2));
+                } else {
+                    asm volatile(PC_B_ODD
+                                 : [vb] "=&v"(vb), [tb0] "+v"(T[f]), [ub0] "+v"(U[f])
+                                 : [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [oe] "s"(OE2));
+                }
+            }
+            c2 = pk_sub(T[R - 1], topB);
+            top = topB;
+#undef PC_M3
+#undef PC_NOP
+#undef PC_A1
+#undef PC_A2
+#undef PC_A3
+#undef PC_A4
+#undef PC_A5
+#undef PC_A6
+#undef PC_A7
+#undef PC_A7I
+#undef PC_A8
+#undef PC_B1
+#undef PC_B2
+#undef PC_B3
+#undef PC_B4
+#undef PC_B5
+#undef PC_B6
+#undef PC_B7
+#undef PC_B8
+#undef PC_B9
+#undef PC_B10
+#undef PC_AB
+#undef PC_AB_ODD
+#undef PC_A_PAIR
+#undef PC_A_ODD
+#undef PC_B_PAIR
+#undef PC_B_ODD
+        };
+#else
+        // int16 lanes have no packed 3-input max: the cross-check kernel keeps six ops per cell pair and U = H~(rho, j-1).
         // Two columns at once, SKEWED: chain A walks column j, chain B column j+1 three rows behind,
         // on the same T/U registers (B reads what A has just produced and overwrites it in turn).
         // Each asm statement carries one row of A and one row of B interleaved instruction by
@@ -433,33 +632,6 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                              : [dq] "=&v"(dh[q]), [uq] "+v"(U[q])
                              : [diag] "v"(diag), [s] "v"(S[COMBO[q]]), [tq] "v"(T[q]));
             };
-#if PC_F16
-#define PC_ONE_FULL                                                                    \
-    PC_MAX " %[uq], %[uq], %[tq]\n\t"                                                  \
-    PC_MAX " %[vs], %[vp], %[tu]\n\t"                                                  \
-    PC_ADD " %[dq], %[dg], %[s]\n\t"                                                   \
-    "v_pk_maximum3_f16 %[mn], %[dr], %[ur], %[vs]\n\t" "s_nop 0\n\t"                   \
-    PC_ADD " %[tn], %[mn], %[oe]"
-#define PC_ONE_TAIL                                                                    \
-    "s_nop 0\n\t"                                                                      \
-    PC_MAX " %[vs], %[vp], %[tu]\n\t" "s_nop 0\n\t"                                    \
-    "v_pk_maximum3_f16 %[mn], %[dr], %[ur], %[vs]\n\t" "s_nop 0\n\t"                   \
-    PC_ADD " %[tn], %[mn], %[oe]"
-#define PC_PAIR_FULL                                                                   \
-    PC_MAX " %[uqa], %[uqa], %[tqa]\n\t"  PC_MAX " %[uqb], %[uqb], %[tqb]\n\t"         \
-    PC_MAX " %[vsa], %[vpa], %[tua]\n\t"  PC_MAX " %[vsb], %[vpb], %[tub]\n\t"         \
-    PC_ADD " %[dqa], %[dga], %[sa]\n\t"   PC_ADD " %[dqb], %[dgb], %[sb]\n\t"          \
-    "v_pk_maximum3_f16 %[mna], %[dra], %[ura], %[vsa]\n\t"                             \
-    "v_pk_maximum3_f16 %[mnb], %[drb], %[urb], %[vsb]\n\t"                             \
-    PC_ADD " %[tna], %[mna], %[oe]\n\t"   PC_ADD " %[tnb], %[mnb], %[oe]"
-#define PC_PAIR_ATAIL                                                                  \
-    PC_MAX " %[uqb], %[uqb], %[tqb]\n\t"                                               \
-    PC_MAX " %[vsa], %[vpa], %[tua]\n\t"  PC_MAX " %[vsb], %[vpb], %[tub]\n\t"         \
-    PC_ADD " %[dqb], %[dgb], %[sb]\n\t"                                                \
-    "v_pk_maximum3_f16 %[mna], %[dra], %[ura], %[vsa]\n\t"                             \
-    "v_pk_maximum3_f16 %[mnb], %[drb], %[urb], %[vsb]\n\t"                             \
-    PC_ADD " %[tna], %[mna], %[oe]\n\t"   PC_ADD " %[tnb], %[mnb], %[oe]"
-#else
 #define PC_ONE_FULL                                                                    \
     PC_MAX " %[mn], %[dr], %[ur]\n\t"                                                  \
     PC_MAX " %[uq], %[uq], %[tq]\n\t"                                                  \
@@ -486,7 +658,6 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
     PC_ADD " %[dqb], %[dgb], %[sb]\n\t"                                                \
     PC_MAX " %[mna], %[mna], %[vsa]\n\t"  PC_MAX " %[mnb], %[mnb], %[vsb]\n\t"         \
     PC_ADD " %[tna], %[mna], %[oe]\n\t"   PC_ADD " %[tnb], %[mnb], %[oe]"
-#endif
             // one row of one chain on its own (prologue of A, epilogue of B)
             auto row_alone = [&](u32 (&dh)[R], const u32 (&S)[K], int rr, u32 &Vprev, u32 &Tup) {
                 u32 mn, vs;
@@ -546,6 +717,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #undef PC_PAIR_FULL
 #undef PC_PAIR_ATAIL
         };
+#endif
 #if PC_CHECK_RANGE
         auto note_range = [&]() {
 #pragma clang loop unroll(full)
@@ -558,6 +730,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         u32 SA[K], SB[K], SC[K], SD[K];
         fetch_S(SA, cur_lo & 0xFF, cur_hi & 0xFF);
         int jj = 0;                                           // columns since the last renormalisation
+        bool u_ahead = false;                                 // wave-uniform, packed fp16 only: U[] already holds the coming column's H (column2)
         for (int j0 = 1; j0 <= nmax; j0 += 4) {
             // the dword this block hands on at its end is the one two blocks ahead (0-based column j0 + 7); when
             // that opens a new 16-column block, the old one is used up -- its last dword is already in nxt -- and
@@ -576,6 +749,13 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
             }
             if (!PC_CHECK_RANGE && j0 > tfmax && j0 + 3 < nmin) {
                 u32 c0, c1, c2, c3;
+#if PC_F16
+                if (!u_ahead) {                                   // entering from the one-column path: U = H~(rho, j0 - 1) -> H~(rho, j0)
+#pragma clang loop unroll(full)
+                    for (int r = 0; r < R; ++r) U[r] = pk_maxq(U[r], T[r]);
+                    u_ahead = true;
+                }
+#endif
                 fetch_S(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
                 fetch_S(SC, (cur_lo >> 16) & 0xFF, (cur_hi >> 16) & 0xFF);
                 fetch_S(SD, cur_lo >> 24, cur_hi >> 24);
@@ -615,6 +795,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #define PC_NOTE
 #endif
                 if (packed_ahead) unpack_best();
+                u_ahead = false;                                  // (nothing to convert: the column computes max(U, T), which is U)
                 // (a tile whose streams all end in column nmax computes no column beyond it: T[] then IS the last column)
                 const int last = uniform_fin ? nmax : 0x7FFFFFFF;
                 fetch_S(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
