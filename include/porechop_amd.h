@@ -132,6 +132,26 @@ int pc_scan_device(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off,
                    const int32_t *job_adapter_b, const int64_t *job_start, int njobs, int max_len,
                    int mode, int32_t *d_out, void *stream);
 
+/* pc_scan_device in PC_MODE_TWO_PASS with a score floor per job (host arrays of njobs entries; job_floor_b, for the jobs'
+ * second adapters, may be NULL when job_adapter_b is): a caller that only wants the alignments whose score can reach some
+ * bound -- Pipeline.phase_c keeps a middle hit only if its full-adapter identity reaches --middle_threshold, which needs
+ * a score of at least Pipeline.identity_score_bound -- says so, and the library decides between its two passes: a pair
+ * whose best score of the first pass is below its job's floor is not traced.  Its record is "no alignment": field 0 is
+ * -1, the others 0.  Every other pair gets exactly the record pc_scan_device writes.  The second pass then costs what the
+ * remaining pairs cost (they are taken first, tile by tile; tiles of skipped pairs only end at once); no host round trip and
+ * no further score pass is added, only the three small launches that order the pairs.  INT32_MIN = no floor for that job; both arrays NULL, or every entry INT32_MIN, is
+ * pc_scan_device itself.  Any other mode with a floor array is PC_ERR_BAD_ARG.  The floor is per call, not context state.
+ * It is ignored -- every pair traced -- for jobs on the plain-int32 kernel and for a launch group of more than 256
+ * (job, adapter) segments. */
+int pc_scan_device_floored(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off,
+                           const int32_t *d_win_len, int64_t nwindows, const int32_t *job_adapter,
+                           const int32_t *job_adapter_b, const int64_t *job_start, int njobs, int max_len,
+                           int mode, int32_t *d_out, void *stream, const int32_t *job_floor,
+                           const int32_t *job_floor_b);
+
+/* Pairs pc_scan_device_floored left untraced: in the last floored call of this context, and in all of them.  Waits for `stream`.  Either pointer may be NULL. */
+int pc_floor_skipped(pc_ctx *ctx, void *stream, int64_t *last_call, int64_t *total);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,

@@ -11,6 +11,7 @@ from ._lib import check, load_library
 
 RESULT_INTS = 8      # readStart, readEnd, adapterStart, adapterEnd, rawScore, matches, alignedLen, fullLen
 MODE_AUTO, MODE_TRACE, MODE_TWO_PASS, MODE_SCORE, MODE_TRACE_AT = 0, 1, 2, 3, 4
+NO_FLOOR = -2 ** 31  # scan_device(floors=...): this job has no score floor (INT32_MIN)
 DEFAULT_SCORES = (3, -6, -5, -2)   # porechop/porechop.py:145
 INT_MIN = -2147483648
 
@@ -119,11 +120,13 @@ class Aligner:
 
     # ---- device buffers (torch tensors on the GPU) --------------------------------------
     def scan_device(self, arena, win_off, win_len, job_adapter, job_start, max_len, out,
-                    mode=MODE_AUTO, stream=None, job_adapter_b=None):
+                    mode=MODE_AUTO, stream=None, job_adapter_b=None, floors=None, floors_b=None):
         """arena uint8[*], win_off int64[n], win_len int32[n]: CUDA(HIP) tensors describing n windows.
         job_adapter int32[k], job_start int64[k+1] (window ranges), optional job_adapter_b int32[k]
         (-1 = none): host numpy.  out int32[total,8] with total = sum n_k * (1 or 2), job order,
-        adapter A's records before adapter B's.  Asynchronous; call sync()."""
+        adapter A's records before adapter B's.  Asynchronous; call sync().
+        floors / floors_b int32[k] (MODE_TWO_PASS only; NO_FLOOR = none): a pair whose best score is below its job's floor is
+        not traced and gets the record (-1, 0, ..., 0) (pc_scan_device_floored); every other record is unchanged."""
         import torch
         assert arena.is_cuda and win_off.is_cuda and win_len.is_cuda and out.is_cuda
         assert win_off.dtype == torch.int64 and win_len.dtype == torch.int32 and out.dtype == torch.int32
@@ -134,11 +137,32 @@ class Aligner:
             jb = np.ascontiguousarray(job_adapter_b, dtype=np.int32)
         n = win_off.shape[0]
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if floors is not None or floors_b is not None:
+            fa = np.ascontiguousarray(floors if floors is not None else np.full(len(job_adapter), NO_FLOOR), dtype=np.int32)
+            fb = None if jb is None else np.ascontiguousarray(floors_b if floors_b is not None else np.full(len(job_adapter), NO_FLOOR),
+                                                              dtype=np.int32)
+            assert fa.shape[0] == len(job_adapter) and (fb is None or fb.shape[0] == len(job_adapter))
+            check(self.lib.pc_scan_device_floored(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
+                                                  job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None,
+                                                  job_start.ctypes.data, len(job_adapter),
+                                                  int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s),
+                                                  fa.ctypes.data, fb.ctypes.data if fb is not None else None),
+                  "pc_scan_device_floored")
+            return
         check(self.lib.pc_scan_device(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
                                       job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None,
                                       job_start.ctypes.data, len(job_adapter),
                                       int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s)),
               "pc_scan_device")
+
+    def floor_skipped(self, stream=None):
+        """-> (pairs the last floored scan left untraced, those of all floored scans of this context) (pc_floor_skipped;
+        waits for the stream)."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        last, total = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self.lib.pc_floor_skipped(self._ctx, ctypes.c_void_p(s), ctypes.byref(last), ctypes.byref(total)), "pc_floor_skipped")
+        return int(last.value), int(total.value)
 
     def set_length_hint(self, typical_len):
         """Typical window length of the following whole-read scans (0 = about uniform): load balancing of the

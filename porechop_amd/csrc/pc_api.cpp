@@ -76,6 +76,9 @@ struct Group {            // tiles that run in one launch
     // single-pass groups (end windows): the segments -- runs of output slots with one adapter -- and their pieces, for the
     // two-pass end scan's ordering by end column (pck::launch_bucket_pairs); offsets into the slot's bucket table
     size_t seg_begin = 0, nseg = 0, blk_begin = 0, nblk = 0;
+    // two-pass groups of a PC_MODE_TWO_PASS call have them too: the second pass of a floored call puts the pairs below their
+    // job's score floor behind the others of their segment.  seg_job[s] = 2 * job + (0: its first adapter, 1: its second)
+    std::vector<int32_t> seg_job;
 };
 
 inline int64_t run_tiles(const pck::TileRun &r) { return r.dual ? (r.n + 63) / 64 : (r.n + 127) / 128; }
@@ -290,6 +293,7 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
     std::map<std::pair<int, int>, std::vector<pck::TileRun>> by_group;   // (rows*2+pad, two_pass) -> runs
     std::map<std::pair<int, int>, int> group_window;
     std::vector<pc_ctx::SlowJob> slow;
+    std::map<int64_t, int32_t> job_of_first;
     int64_t out_pos = 0;
     for (int k = 0; k < njobs; ++k) {
         const int ad = job_adapter[k], adb = jb[k];
@@ -345,6 +349,8 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
         static const bool no_split = [] { const char *e = getenv("PC_NO_SPLIT_DUAL"); return e && *e && *e != '0'; }();
         const bool split_dual = adb >= 0 && !two_pass_job && !no_drift && !no_split &&
                                 pck::pick_rows(m, m, &pa_) != pck::pick_rows(mb, mb, &pb_);
+        job_of_first[out_pos] = 2 * k;                         // (first record of a segment -> whose it is)
+        if (adb >= 0) job_of_first[out_pos + n] = 2 * k + 1;
         if (adb >= 0 && !split_dual) {
             // both halves of a lane scan the same 64 windows: adapter A's records first, then B's
             int rows;
@@ -436,13 +442,14 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
         g.tile_count = (size_t)t;
         g.runs.swap(kv.second);
         ntiles += g.tile_count;
-        if ((!g.two_pass || mode == PC_MODE_TRACE_AT) && g.rows > 0) {
+        if (((!g.two_pass || mode == PC_MODE_TRACE_AT) && g.rows > 0) || (g.two_pass && mode == PC_MODE_TWO_PASS)) {
             g.seg_begin = seg_first.size(); g.blk_begin = bblocks.size();
             for (const pck::TileRun &r : g.runs) {
                 for (int half = 0; half < (r.dual ? 2 : 1); ++half) {
                     const int64_t first = r.out0 + (half ? r.n : 0);
                     const int32_t sgm = (int32_t)(seg_first.size() - g.seg_begin);
                     seg_first.push_back(first);
+                    g.seg_job.push_back(job_of_first.at(first));
                     for (int64_t at = 0; at < r.n; at += pck::kBucketBlock)
                         bblocks.push_back(pck::BucketBlock{first + at, (int32_t)std::min<int64_t>(pck::kBucketBlock, r.n - at), sgm});
                 }
@@ -496,6 +503,9 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
 }
 
 constexpr int kMaxChunks = 64, kMaxChunksLong = 2048;
+// pairs below their score floor, as two 64-bit counters behind the error words of d_err (bytes 0..23): those of the last floored
+// call, and all since the context was made (pc_floor_skipped)
+constexpr size_t kFloorCounterAt = 32;
 
 // Columns the register variants' drifting coordinates (pc_kernels.hip, column_step) can run before
 // int16 needs a renormalisation: values drift up by eps = -gap_extend per column on top of a true
@@ -839,9 +849,47 @@ int pc_set_adapters(pc_ctx *c, const char *const *seqs, int n)
     return upload_panel(c);
 }
 
+static int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                       int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                       const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                       const int32_t *job_floor, const int32_t *job_floor_b);
+
 int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                    int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
                    const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v)
+{
+    return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
+                       stream_v, nullptr, nullptr);
+}
+
+int pc_scan_device_floored(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                           int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                           const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                           const int32_t *job_floor, const int32_t *job_floor_b)
+{
+    if ((job_floor || job_floor_b) && mode != PC_MODE_TWO_PASS) return PC_ERR_BAD_ARG;     // floors sit between the two passes
+    if (job_floor_b && !job_adapter_b) return PC_ERR_BAD_ARG;
+    return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
+                       stream_v, job_floor, job_floor_b);
+}
+
+int pc_floor_skipped(pc_ctx *c, void *stream_v, int64_t *last_call, int64_t *total)
+{
+    if (!c || (!last_call && !total)) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned long long v[2] = {0, 0};
+    HIP_TRY(hipMemcpy(v, (char *)c->d_err.p + kFloorCounterAt, 16, hipMemcpyDeviceToHost));
+    if (last_call) *last_call = (int64_t)v[0];
+    if (total) *total = (int64_t)v[1];
+    return PC_OK;
+}
+
+static int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                       int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                       const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                       const int32_t *job_floor, const int32_t *job_floor_b)
 {
     if (!c || nwindows < 0 || njobs < 0 || max_len < 0) return PC_ERR_BAD_ARG;
     if (nwindows == 0 || njobs == 0) return PC_OK;
@@ -944,13 +992,37 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         pcb::F16Plan fp;
         return !no_end_order && mode == PC_MODE_TRACE_AT && g.two_pass && g.rows > 0 && g.nseg > 0 && trace16_plan(c, g.rows, g.max_window + 1, &fp);
     };
-    bool any_ordered = false;
+    // A floored PC_MODE_TWO_PASS call (pc_scan_device_floored): between the passes the pairs whose best score is below their job's
+    // floor are answered by the planner ("no alignment") and put behind the others of their segment, by the same bucket pass, so
+    // that pass 2 costs what the remaining pairs cost: its tiles hold them densely and the tiles behind them end at once.  The
+    // first pass then leaves score records in d_out -- the specialised kernel writes them itself where a window is one unit --
+    // which is where the bucket pass and the planner read the end cells, as in PC_MODE_TRACE_AT.  A group none of whose jobs
+    // has a floor (INT32_MIN) runs exactly as in an unfloored call.
+    auto seg_floor_of = [&](const Group &g, size_t s) -> int32_t {
+        const int32_t sj = g.seg_job[s];
+        const int32_t *f = (sj & 1) ? job_floor_b : job_floor;
+        return f ? f[sj >> 1] : INT32_MIN;
+    };
+    auto floored = [&](const Group &g) -> bool {
+        if (!(job_floor || job_floor_b) || mode != PC_MODE_TWO_PASS || !g.two_pass || g.nseg == 0 || g.nseg > (size_t)pck::kFloorSegments ||
+            g.seg_job.size() != g.nseg)
+            return false;
+        for (size_t s = 0; s < g.nseg; ++s) if (seg_floor_of(g, s) != INT32_MIN) return true;
+        return false;
+    };
+    bool any_ordered = false, any_floored = false;
     size_t ordered_segments = 0;         // segments up to the last one of an ordered group: the stride of the bucket counters
-    for (const Group &g : c->groups)
-        if (ordered_trace_at(g)) { any_ordered = true; ordered_segments = std::max(ordered_segments, g.seg_begin + g.nseg); }
-    if (any_ordered) {
-        if ((rc = c->d_perm.ensure((size_t)npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * ordered_segments * pck::kBuckets * 4 + 256))) return rc;
+    for (const Group &g : c->groups) {
+        const bool fl = floored(g);
+        any_floored |= fl;
+        if (fl || ordered_trace_at(g)) { any_ordered = true; ordered_segments = std::max(ordered_segments, g.seg_begin + g.nseg); }
     }
+    if (any_ordered) {
+        if ((rc = c->d_perm.ensure((size_t)npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * ordered_segments * pck::kBucketSlots * 4 + 256))) return rc;
+        // (the counts and cursors of every ordered group of the call, zeroed by one fill: each group has its own rows)
+        HIP_TRY(hipMemsetAsync(c->d_bucket_cnt.p, 0, 2 * ordered_segments * pck::kBucketSlots * 4, stream));
+    }
+    if (any_floored) HIP_TRY(hipMemsetAsync((char *)c->d_err.p + kFloorCounterAt, 0, 8, stream));    // this call's counter
     if (any_two) {                       // (an ordered group is a two-pass group)
         const size_t n = (size_t)npairs;
         if ((rc = c->d_k1.ensure(k1_ints * 4 + 256)) || (rc = c->d_woff2.ensure(n * 8)) || (rc = c->d_wlen2.ensure(n * 4)) ||
@@ -1012,6 +1084,7 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             a.slab = nullptr; a.slab_cols = 0; a.slab_stride = 0;
             a.ad_span = c->d_ad_span.as<int32_t>();
             const size_t gi = (size_t)(&g - &c->groups[0]);
+            const bool fl = floored(g);
             // A score-only call over short windows (phase B's pruning pass: ~100 launches of 150-column windows, one per
             // adapter pair) cannot cut its tails into column chunks, and every launch would end with a round of tiles that
             // fills a fraction of the chip (15 625 tiles on 3072 resident waves: 15 % of the launch).  Its launches
@@ -1067,7 +1140,7 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
                     sa.err = a.err;
                     sa.work_counter = c->d_work.as<uint32_t>() + score_launch_no++;
                     // a score-only request over whole windows: the kernel writes the records itself (no planner launch)
-                    sa.rec_out = (mode == PC_MODE_SCORE && L.chunks == 1) ? d_out : nullptr;
+                    sa.rec_out = ((mode == PC_MODE_SCORE || fl) && L.chunks == 1) ? d_out : nullptr;
                     sa.unit_prefix = unit_prefix;
                     if (pcj::launch(L.spec, sa, grid, stream_k)) return PC_ERR_NO_DEVICE;
                 } else {
@@ -1100,7 +1173,7 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             }
             a.chunks = 1;
             pl.ad_window = c->d_ad_window.as<int32_t>();
-            pl.score_out = (mode == PC_MODE_SCORE) ? d_out : nullptr;
+            pl.score_out = (mode == PC_MODE_SCORE || fl) ? d_out : nullptr;
             {   // end-aligned windows only for the packed-fp16 traced kernel (it is the one that knows lead-ins)
                 pcb::F16Plan fp_;
                 pl.end_align = trace16_plan(c, g.rows, g.max_window + 1, &fp_) ? 1 : 0;
@@ -1109,24 +1182,32 @@ int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             {
                 ScopedTimer tm(c, stream, 1, np);
                 for (const ScoreLaunch &L : score_plan[gi]) {
-                    if (mode == PC_MODE_SCORE && L.chunks == 1 && L.spec) continue;      // records written by the kernel itself
+                    if ((mode == PC_MODE_SCORE || fl) && L.chunks == 1 && L.spec) continue;      // records written by the kernel itself
                     pl.k1 = c->d_k1.as<int32_t>() + L.k1_ints;
                     pl.tiles = a.tiles + L.begin; pl.ntiles = (int32_t)L.count; pl.chunks = L.chunks;
                     pl.chunk_len = (max_len + L.chunks - 1) / L.chunks;
                     if ((rc = pck::launch_plan(pl, stream))) return PC_ERR_NO_DEVICE;
                 }
-                if (mode == PC_MODE_TRACE_AT) {         // the caller's score records, read before pass 2 overwrites them
-                    pl.k1 = nullptr; pl.end_records = d_out; pl.window_cap = std::max(1, max_len);
+                if (mode == PC_MODE_TRACE_AT || fl) {   // the score records (the caller's / pass 1's), read before pass 2 overwrites them
+                    pl.k1 = nullptr; pl.end_records = d_out; pl.score_out = nullptr;
+                    if (mode == PC_MODE_TRACE_AT) pl.window_cap = std::max(1, max_len);
                     pl.tiles = a.tiles; pl.ntiles = (int32_t)g.tile_count; pl.chunks = 1;
-                    if (ordered_trace_at(g)) {
+                    if (fl || ordered_trace_at(g)) {
                         pck::BucketArgs b;
                         memset(&b, 0, sizeof b);
                         b.records = d_out;
+                        if (fl) {
+                            b.mark = d_out;
+                            for (size_t s = 0; s < g.nseg; ++s) b.seg_floor[s] = seg_floor_of(g, s);
+                            b.skipped = (unsigned long long *)((char *)c->d_err.p + kFloorCounterAt);
+                            pl.floor_out = d_out;
+                            a.skip_marked = 1;
+                        }
                         b.seg_first = (const int64_t *)c->d_bucket_slot[c->slot].p + g.seg_begin; b.nsegments = (int32_t)g.nseg;
                         b.blocks = (const pck::BucketBlock *)((const char *)c->d_bucket_slot[c->slot].p + c->bucket_blocks_at) + g.blk_begin;
                         b.nblocks = (int32_t)g.nblk;
-                        b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBuckets;
-                        b.cursors = c->d_bucket_cnt.as<uint32_t>() + (ordered_segments + g.seg_begin) * pck::kBuckets;
+                        b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBucketSlots;
+                        b.cursors = c->d_bucket_cnt.as<uint32_t>() + (ordered_segments + g.seg_begin) * pck::kBucketSlots;
                         b.perm = c->d_perm.as<int64_t>();
                         if (pck::launch_bucket_pairs(b, stream)) return PC_ERR_NO_DEVICE;
                         pl.perm = b.perm; a.perm = b.perm;

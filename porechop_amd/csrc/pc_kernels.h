@@ -68,6 +68,8 @@ struct ScanArgs {
                                      // launch order -- longest tiles first -- instead of a fixed stride; null = fixed stride
     const int32_t *unit_prefix;      // score pass: [ntiles + 1] or null -- tile t owns units [unit_prefix[t], unit_prefix[t + 1]): only
                                      // the chunks that hold columns of its longest window (launch_unit_prefix)
+    int32_t skip_marked;             // traced pass 2 of a floored call: a pair whose force_row is kSkipRow has its record already
+                                     // (plan_kernel) and is not there for the kernel; a tile of such pairs only is left at once
 };
 // unit_prefix of a chunked score pass: one wave per tile takes the tile's longest window, a block scans the counts
 int launch_unit_prefix(const Tile *tiles, int ntiles, const int32_t *win_len, int chunk_len, int32_t *real, int32_t *prefix, void *stream);
@@ -93,6 +95,9 @@ struct PlanArgs {
                                                         // ([npairs][8], indexed like k1 by output slot) instead of a score pass
     int32_t window_cap;                                 // > 0: no traced window longer than this (PC_MODE_TRACE_AT: the caller's max_len --
                                                         // a window that holds its read's column 0 needs no warm-up before it)
+    int32_t *floor_out;                                 // a floored call: the output records -- a pair whose end record is marked
+                                                        // kBelowFloor gets the "no alignment" record (-1, 0, ...) here, a pass-2
+                                                        // window of no columns and force_row kSkipRow; null: no pair is marked
     uint32_t *err;
 };
 
@@ -287,14 +292,25 @@ int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream);   // pa
 // perm[segment's slots] = the segment's pairs, bucket (J / kBucketWidth, capped) by bucket; within a bucket in no particular
 // order.  records: the score records (-2, J, I, 0, score, ...) indexed by pair.  blocks: the segments cut into pieces of at most
 // kBucketBlock slots, {first slot, count, segment}; counts / cursors: [nsegments][kBuckets] scratch.
+// Score floors (the second pass of a floored PC_MODE_TWO_PASS call): seg_floor[segment] is the score below which a pair of that
+// segment is proven irrelevant to the caller.  Such pairs go into one more bucket BEHIND all others -- the tiles of pass 2 then
+// hold the pairs that are traced densely, and the tiles behind them hold nothing -- and their records are marked (field 0 =
+// kBelowFloor) for plan_kernel, which answers them itself.  The floors travel in the kernel arguments: no upload per call.
 constexpr int kBuckets = 12, kBucketWidth = 14, kBucketBlock = 2048;
+constexpr int kBucketSlots = kBuckets + 1;             // + the bucket of the pairs below their floor
+constexpr int kFloorSegments = 256;                    // segments a floored group may have (more: the group is traced in full)
+constexpr int kBelowFloor = -3;                        // field 0 of a score record whose pair is below its floor
+constexpr int kSkipRow = -2;                           // force_row of such a pair in pass 2: not there for the traced kernels
 struct BucketBlock { int64_t first; int32_t count, segment; };
 struct BucketArgs {
     const int32_t *records;
     const BucketBlock *blocks; int32_t nblocks;
     const int64_t *seg_first; int32_t nsegments;       // [nsegments] first slot of each segment
-    uint32_t *counts, *cursors;                        // [nsegments][kBuckets]; zeroed by the launcher
+    uint32_t *counts, *cursors;                        // [nsegments][kBucketSlots]; zeroed by the caller
     int64_t *perm;
+    int32_t *mark;                                     // null, or the records again: pairs below seg_floor are marked there
+    unsigned long long *skipped;                       // with mark: [2] += the pairs marked (this call's counter, the running one)
+    int32_t seg_floor[kFloorSegments];                 // read only when mark is set
 };
 int launch_bucket_pairs(const BucketArgs &a, void *stream);
 

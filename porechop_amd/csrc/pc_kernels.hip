@@ -353,6 +353,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
             if (lane == 0) atomicAdd(a.err, 1u);
             continue;
         }
+        // ---- this lane's two pairs (output slots; the traced pass 2 of a floored call takes them through a.perm and leaves
+        // out the pairs below their floor, as trace16_kernel does) -------------------------
+        bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
+        int64_t p_lo = tile.out_lo + lane, p_hi = tile.out_hi + lane;
+        if constexpr (TRACE) {
+            if (a.perm && have_lo) p_lo = a.perm[p_lo];
+            if (a.perm && have_hi) p_hi = a.perm[p_hi];
+            if (a.skip_marked) {
+                have_lo = have_lo && a.force_row[p_lo] != kSkipRow;
+                have_hi = have_hi && a.force_row[p_hi] != kSkipRow;
+                if (!__any(have_lo || have_hi)) continue;
+            }
+        }
 
         // ---- per-row adapter constants -> LDS (-> SGPRs for the exact variants) -----------
         __syncthreads();
@@ -381,11 +394,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
             }
         }
 
-        // ---- this lane's two pairs -----------------------------------------------------
-        const int64_t p_lo = tile.out_lo + lane, p_hi = tile.out_hi + lane;            // output slots
         const int64_t wi_lo = a.win_by_out ? p_lo : tile.win_lo + lane;                  // window slots
         const int64_t wi_hi = a.win_by_out ? p_hi : tile.win_hi + lane;
-        const bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
         const bool one_stream = !a.win_by_out && tile.win_lo == tile.win_hi;             // same windows, two adapters
         const uint8_t *w_lo = a.arena + (have_lo ? a.win_off[wi_lo] : 0);
         const uint8_t *w_hi = a.arena + (have_hi ? a.win_off[wi_hi] : 0);
@@ -765,6 +775,19 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
             if (lane == 0) atomicAdd(a.err, 1u);
             continue;
         }
+        // ---- this lane's two pairs -----------------------------------------------------
+        // (a.perm: PC_MODE_TRACE_AT takes the pairs of a segment in the order of their end columns --
+        // slot s of the tile holds pair perm[s] of the same segment)
+        bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
+        const int64_t p_lo = (a.perm && have_lo) ? a.perm[tile.out_lo + lane] : tile.out_lo + lane;
+        const int64_t p_hi = (a.perm && have_hi) ? a.perm[tile.out_hi + lane] : tile.out_hi + lane;
+        if (a.skip_marked) {
+            // a floored call: the pairs below their floor have their records (plan_kernel) and lie behind the others of
+            // their segment -- a tile of such pairs only touches neither its table nor its slab
+            have_lo = have_lo && a.force_row[p_lo] != kSkipRow;
+            have_hi = have_hi && a.force_row[p_hi] != kSkipRow;
+            if (!__any(have_lo || have_hi)) continue;
+        }
         int tab_max = 0, tab_min = 0;                             // CHECK: extremes of the table terms this lane wrote
         // ---- substitution table of this adapter pair: s_tab[(c_lo*5 + c_hi)][row] = packed
         // (sub_lo - open + eps | sub_hi - open + eps); a padding row scores 0, which keeps its
@@ -788,12 +811,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
         }
         __syncthreads();
 
-        // ---- this lane's two pairs -----------------------------------------------------
-        // (a.perm: PC_MODE_TRACE_AT takes the pairs of a segment in the order of their end columns --
-        // slot s of the tile holds pair perm[s] of the same segment)
-        const bool have_lo = lane < tile.count_lo, have_hi = lane < tile.count_hi;
-        const int64_t p_lo = (a.perm && have_lo) ? a.perm[tile.out_lo + lane] : tile.out_lo + lane;
-        const int64_t p_hi = (a.perm && have_hi) ? a.perm[tile.out_hi + lane] : tile.out_hi + lane;
         const int64_t wi_lo = a.win_by_out ? p_lo : tile.win_lo + lane;
         const int64_t wi_hi = a.win_by_out ? p_hi : tile.win_hi + lane;
         const bool one_stream = !a.win_by_out && tile.win_lo == tile.win_hi;
@@ -1159,7 +1176,9 @@ __global__ void plan_kernel(PlanArgs a)
     if (threadIdx.x == 0) tile_len = 0;
     __syncthreads();
     int score = 0, I = 0, J = 0;
-    if (have) {
+    // a pair the bucket pass found below its job's score floor: proven irrelevant to the caller, answered here
+    const bool skip = have && a.end_records && a.floor_out && a.end_records[p * TRACE_OUT_INTS] == kBelowFloor;
+    if (have && !skip) {
         // merge the per-chunk maxima in the reference's visiting order (strict '>', earlier chunk wins)
         int nch = a.chunks > 1 ? a.chunks : 1;
         if (nch > 1 && a.chunk_len > 0) {             // the chunks that hold columns of this window (chunk 0 always)
@@ -1207,6 +1226,16 @@ __global__ void plan_kernel(PlanArgs a)
     }
     __syncthreads();
     if (!have) return;
+    if (skip) {
+        // the "no alignment" record, a pass-2 window of no columns, no traced columns; kSkipRow keeps the traced kernels off the pair
+        int4 *o = (int4 *)(a.floor_out + p * TRACE_OUT_INTS);
+        o[0] = make_int4(-1, 0, 0, 0);
+        o[1] = make_int4(0, 0, 0, 0);
+        a.win_off2[p] = a.win_off[w]; a.win_len2[p] = 0; a.col02[p] = 0; a.ntot2[p] = a.win_len[w];
+        a.force_row2[p] = kSkipRow; a.force_score2[p] = 0;
+        if (a.trace_cols2) a.trace_cols2[p] = 0;
+        return;
+    }
     int c0 = J - window;
     if (a.end_align && J > 0) {             // (J == 0: the end cell is the corner (m, 0) -- nothing to run, nothing to align)
         c0 = J - tile_len;
@@ -1341,23 +1370,24 @@ int launch_score(const ScanArgs &a, int rows, bool pad, int grid, void *stream) 
 // Pairs of a segment by end column (see BucketArgs).  Three small launches: per-(segment, bucket) counts, their prefix, the
 // scatter.  A block takes one piece of one segment: LDS histogram, then one atomic per non-empty bucket.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int bucket_of(const int32_t *records, int64_t pair)
+__device__ __forceinline__ int bucket_of(const BucketArgs &a, int64_t pair, int segment)
 {
-    const int2 v = *(const int2 *)(records + pair * TRACE_OUT_INTS);        // (flag, J)
+    const int2 v = *(const int2 *)(a.records + pair * TRACE_OUT_INTS);      // (flag, J)
     if (v.x != -2 || v.y < 0) return kBuckets - 1;                          // not a score record: among the longest
+    if (a.mark && a.records[pair * TRACE_OUT_INTS + 4] < a.seg_floor[segment]) return kBuckets;   // below its floor: behind all others
     const int b = v.y / kBucketWidth;
     return b < kBuckets ? b : kBuckets - 1;
 }
 
 __global__ __launch_bounds__(256) void bucket_count_kernel(BucketArgs a)
 {
-    __shared__ unsigned hist[kBuckets];
+    __shared__ unsigned hist[kBucketSlots];
     const BucketBlock blk = a.blocks[blockIdx.x];
-    if (threadIdx.x < kBuckets) hist[threadIdx.x] = 0;
+    if (threadIdx.x < kBucketSlots) hist[threadIdx.x] = 0;
     __syncthreads();
-    for (int i = threadIdx.x; i < blk.count; i += 256) atomicAdd(&hist[bucket_of(a.records, blk.first + i)], 1u);
+    for (int i = threadIdx.x; i < blk.count; i += 256) atomicAdd(&hist[bucket_of(a, blk.first + i, blk.segment)], 1u);
     __syncthreads();
-    if (threadIdx.x < kBuckets && hist[threadIdx.x]) atomicAdd(a.counts + (int64_t)blk.segment * kBuckets + threadIdx.x, hist[threadIdx.x]);
+    if (threadIdx.x < kBucketSlots && hist[threadIdx.x]) atomicAdd(a.counts + (int64_t)blk.segment * kBucketSlots + threadIdx.x, hist[threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void bucket_prefix_kernel(BucketArgs a)
@@ -1365,31 +1395,34 @@ __global__ __launch_bounds__(256) void bucket_prefix_kernel(BucketArgs a)
     const int sgm = blockIdx.x * 256 + threadIdx.x;
     if (sgm >= a.nsegments) return;
     unsigned acc = 0;
-    for (int b = 0; b < kBuckets; ++b) {        // counts -> first position of the bucket within its segment
-        const unsigned c = a.counts[(int64_t)sgm * kBuckets + b];
-        a.counts[(int64_t)sgm * kBuckets + b] = acc;
+    for (int b = 0; b < kBucketSlots; ++b) {    // counts -> first position of the bucket within its segment
+        const unsigned c = a.counts[(int64_t)sgm * kBucketSlots + b];
+        a.counts[(int64_t)sgm * kBucketSlots + b] = acc;
         acc += c;
     }
 }
 
 __global__ __launch_bounds__(256) void bucket_scatter_kernel(BucketArgs a)
 {
-    __shared__ unsigned hist[kBuckets], base[kBuckets];
+    __shared__ unsigned hist[kBucketSlots], base[kBucketSlots];
     const BucketBlock blk = a.blocks[blockIdx.x];
-    if (threadIdx.x < kBuckets) hist[threadIdx.x] = 0;
+    if (threadIdx.x < kBucketSlots) hist[threadIdx.x] = 0;
     __syncthreads();
     int mine[kBucketBlock / 256];
 #pragma unroll
     for (int k = 0; k < kBucketBlock / 256; ++k) {
         const int i = threadIdx.x + 256 * k;
-        mine[k] = i < blk.count ? bucket_of(a.records, blk.first + i) : -1;
+        mine[k] = i < blk.count ? bucket_of(a, blk.first + i, blk.segment) : -1;
         if (mine[k] >= 0) atomicAdd(&hist[mine[k]], 1u);
     }
     __syncthreads();
-    if (threadIdx.x < kBuckets) {
+    if (threadIdx.x < kBucketSlots) {
         const unsigned h = hist[threadIdx.x];
-        base[threadIdx.x] = a.counts[(int64_t)blk.segment * kBuckets + threadIdx.x] +
-                            (h ? atomicAdd(a.cursors + (int64_t)blk.segment * kBuckets + threadIdx.x, h) : 0u);
+        base[threadIdx.x] = a.counts[(int64_t)blk.segment * kBucketSlots + threadIdx.x] +
+                            (h ? atomicAdd(a.cursors + (int64_t)blk.segment * kBucketSlots + threadIdx.x, h) : 0u);
+        // the pairs left untraced are counted here, one atomic per piece of a segment (per tile in plan_kernel it was 31 000
+        // atomics on one address per 2 M pairs: 0.2 ms)
+        if (threadIdx.x == kBuckets && h && a.mark) { atomicAdd(a.skipped, (unsigned long long)h); atomicAdd(a.skipped + 1, (unsigned long long)h); }
         hist[threadIdx.x] = 0;
     }
     __syncthreads();
@@ -1398,16 +1431,18 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(BucketArgs a)
     for (int k = 0; k < kBucketBlock / 256; ++k) {
         if (mine[k] < 0) continue;
         const unsigned r = atomicAdd(&hist[mine[k]], 1u);
-        a.perm[seg0 + base[mine[k]] + r] = blk.first + threadIdx.x + 256 * k;
+        const int64_t pair = blk.first + threadIdx.x + 256 * k;
+        a.perm[seg0 + base[mine[k]] + r] = pair;
+        // (every pair is looked at by this one thread, and only after it took the pair's bucket from the record)
+        if (mine[k] == kBuckets) a.mark[pair * TRACE_OUT_INTS] = kBelowFloor;
     }
 }
 
 int launch_bucket_pairs(const BucketArgs &a, void *stream)
 {
     if (a.nblocks <= 0 || a.nsegments <= 0) return 0;
+    if (a.mark && a.nsegments > kFloorSegments) return -1;
     hipStream_t s = (hipStream_t)stream;
-    const size_t bytes = (size_t)a.nsegments * kBuckets * 4;
-    if (hipMemsetAsync(a.counts, 0, bytes, s) != hipSuccess || hipMemsetAsync(a.cursors, 0, bytes, s) != hipSuccess) return -2;
     hipLaunchKernelGGL(bucket_count_kernel, dim3((unsigned)a.nblocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bucket_prefix_kernel, dim3((unsigned)((a.nsegments + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bucket_scatter_kernel, dim3((unsigned)a.nblocks), dim3(256), 0, s, a);

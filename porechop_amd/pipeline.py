@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from .batch import MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, Aligner, RESULT_INTS
+from .batch import MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS
 
 # phase B is pruned (exactly: see "Exact pruning of phase B" below) from this many (sequence, side) jobs on; measured on
 # MI355X, 1 M reads: 198 jobs 192 -> 122 ms; with the 4-6 jobs of a run without barcodes tracing everything is faster
@@ -238,6 +238,7 @@ class Pipeline:
             self.aligner = aligner
             self.aligner.set_adapters(self.seqs)
         self.stats = {"pairs_end": 0, "pairs_middle": 0, "cells_end": 0, "cells_middle": 0}
+        self._floor_seen = 0          # the aligner's total of pairs left untraced by a score floor, as of the last phase_c
         self._consts = {}
 
     def _const(self, values, dtype=torch.int64):
@@ -302,8 +303,11 @@ class Pipeline:
         """The bytes the end windows index: the read arena, or -- packed-only reads -- the copies of the end windows."""
         return reads.arena if reads.arena is not None else reads.ends[0]
 
-    def _scan_jobs(self, arena, jobs, mode, max_len, with_layout=False, sort_lengths=False, typ_len=0, fuse=True):
+    def _scan_jobs(self, arena, jobs, mode, max_len, with_layout=False, sort_lengths=False, typ_len=0, fuse=True, floors=None):
         """jobs: list of (adapter_index, win_off int64[n], win_len int32[n]) -> list of [n,8] views.
+
+        floors (MODE_TWO_PASS): one score per job -- a pair whose best score is below it is not traced and gets the
+        "no alignment" record (-1, 0, ..., 0), decided in the library between its two passes (Aligner.scan_device).
 
         Jobs that scan the very same windows (same tensors) are fused two adapters at a time
         (similar lengths together), so each window is streamed from HBM once per adapter PAIR.
@@ -367,10 +371,14 @@ class Pipeline:
         out = torch.empty((int(ostarts[-1]), RESULT_INTS), dtype=torch.int32, device=self.device)
         if starts[-1] > 0:
             self.aligner.set_length_hint(typ_len if sort_lengths else 0)
+            fl = {}
+            if floors is not None:
+                fl = dict(floors=np.array([floors[a] for a, _ in fused], dtype=np.int32),
+                          floors_b=np.array([floors[b] if b is not None else NO_FLOOR for _, b in fused], dtype=np.int32))
             self.aligner.scan_device(arena, woff, wlen, np.array([jobs[a][0] for a, _ in fused], dtype=np.int32),
                                      starts, max_len, out, mode,
                                      job_adapter_b=np.array([jobs[b][0] if b is not None else -1 for _, b in fused],
-                                                            dtype=np.int32))
+                                                            dtype=np.int32), **fl)
         res = [None] * len(jobs)
         rec_off = [0] * len(jobs)
         for k, (a, b) in enumerate(fused):
@@ -1045,7 +1053,9 @@ class Pipeline:
         traceback only for pairs whose score can still mean an identity >= --middle_threshold
         (identity_score_bound) -- everything else is PROVEN not to be a hit, which is all the
         reference does with those alignments.  Hits, masks and splits are identical; the records of
-        the proven non-hits are simply not produced (an option: the default computes them all).
+        the proven non-hits are simply not produced.  (An option: it costs a second score pass and a host round
+        trip.  The default applies the same bound inside the library instead, between the two passes of its one
+        scan -- pc_scan_device_floored: pairs below it are not traced and come back as "no alignment".)
 
         prefilter=True: the same, with the proof coming from the exact bit-parallel prefilter instead of the
         score pass (pc_prefilter_device: Myers' bit-vector edit distance, one lane per read chunk and adapter; the
@@ -1112,6 +1122,15 @@ class Pipeline:
         # ---- round 0: all adapters x all reads, unmasked -------------------------------------
         jobs0 = [(ai, loff, llen, h) for ai, h in zip(aidx, hint)]
         bounds = [self.identity_score_bound(len(self.seqs[ai]), p.middle_threshold) for ai in aidx] if prove else None
+        # The default route hands the same bound down as a score floor per job: the library decides between its two passes which
+        # pairs can still be hits and traces only those (pc_scan_device_floored); the others get the "no alignment" record, which
+        # is "not a hit" below.  PC_NO_PASS2_FLOOR=1: every pair traced.
+        floors = None
+        if not prove and not prefilter and fused and hasattr(al, "floor_skipped") and self.packed_kernels() \
+                and os.environ.get("PC_NO_PASS2_FLOOR", "0") in ("", "0"):
+            floors = [self.identity_score_bound(len(self.seqs[ai]), p.middle_threshold) for ai in aidx]
+            if any(b is None for b in floors):
+                floors = None
         sparse0 = None
         if prefilter:
             ks = [self.aligner.max_edits(len(self.seqs[ai]), p.middle_threshold) for ai in aidx]
@@ -1138,7 +1157,7 @@ class Pipeline:
             fulls = torch.stack([torch.nan_to_num(identity_of(rec), nan=0.0) for rec in outs])
             self.stats["pairs_middle_traced_after_proof"] = self.stats.get("pairs_middle_traced_after_proof", 0) + int(counts.sum())
         else:
-            outs = self._scan_jobs(reads.arena, jobs0, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len)
+            outs = self._scan_jobs(reads.arena, jobs0, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len, floors=floors)
             if fused:
                 fulls, hit0_f = al.middle_hits(torch.stack(outs), p.middle_threshold)          # [A, L] each
             else:
@@ -1257,7 +1276,7 @@ class Pipeline:
                     outs_r[rb, rw] = rr
                 else:
                     outs_r = self._scan_jobs(dirty, [(aidx[a], o_act, l_act, hint[a]) for a in range(a0, A)], MODE_TWO_PASS, dmax,
-                                             sort_lengths=ragged, typ_len=dtyp)
+                                             sort_lengths=ragged, typ_len=dtyp, floors=floors[a0:] if floors is not None else None)
                 scheduled = (A - a0) * int(act.numel())
                 if not torch.is_tensor(outs_r):
                     outs_r = torch.stack(outs_r)                     # [A - a0, active, 8]
@@ -1266,6 +1285,12 @@ class Pipeline:
                 full_all[a0:, act] = al.middle_hits(outs_r.contiguous(), p.middle_threshold)[0] if fused else torch.nan_to_num(identity_of(outs_r), nan=0.0)
         self.stats["pairs_middle"] += n_align
         self.stats["pairs_middle_speculative"] = self.stats.get("pairs_middle_speculative", 0) + n_spec
+        if floors is not None:
+            # (the context's running total, read once per call where the device has just been waited for -- the last round's
+            # statistics above, or the dirty-read count -- so the 16-byte copy waits for nothing)
+            total = al.floor_skipped()[1]
+            self.stats["pairs_middle_skipped_by_floor"] = self.stats.get("pairs_middle_skipped_by_floor", 0) + total - self._floor_seen
+            self._floor_seen = total
         if not H_read:
             empty.rounds, empty.alignments = rounds, n_align
             return empty
