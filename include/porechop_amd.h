@@ -152,6 +152,35 @@ int pc_scan_device_floored(pc_ctx *ctx, const void *d_arena, const int64_t *d_wi
 /* Pairs pc_scan_device_floored left untraced: in the last floored call of this context, and in all of them.  Waits for `stream`.  Either pointer may be NULL. */
 int pc_floor_skipped(pc_ctx *ctx, void *stream, int64_t *last_call, int64_t *total);
 
+/* Alignment PATHS: pair p aligns window [d_win_off[p], + d_win_len[p]) of the arena with adapter d_adapter_idx[p] of the
+ * context's table and gets its record (d_records[p][8]), a head (d_heads[p][4]) and the operations of its path
+ * (d_ops[p][ops_pitch_words]).  All pointers but `ctx` are device memory; d_records and d_heads are 16-byte aligned.
+ *   * The scheme is the context's; any scheme the plain-int32 arithmetic holds (pc_set_scores' condition, over windows of
+ *     max_len bases) is taken, the ones the packed kernels refuse included.  n == 0 is fine.
+ *   * Windows may overlap, repeat, start at any byte and be empty; only bytes inside a window are read.  max_len bounds
+ *     every d_win_len[p].
+ *   * ops_pitch_words >= ceil((max_len + longest adapter of the table) / 16), else PC_ERR_BAD_ARG before anything is
+ *     launched.  A table holding an adapter above 128 bases is PC_ERR_BAD_ARG as well.
+ *   * The adapter indices live on the device and the call makes no host round trip: an index outside the table (like a
+ *     window longer than max_len) is caught by the kernel, which writes nothing for that pair, and surfaces as
+ *     PC_ERR_INTERNAL at pc_sync.  Callers that hold the indices on the host check them there.
+ *   * The records are exactly those pc_scan_device / pc_align_batch_host give for the same pairs.
+ *   * head = {path_len, read_first, adapter_first, opens}: steps of the path, read bases before its first cell, adapter
+ *     bases before it (one of the two is 0), gap steps that opened their gap.
+ *   * Operations are two bits each: 0 '=' diagonal over equal Dna5 codes (N == N is equal), 1 'X' diagonal over unequal
+ *     ones, 2 'I' read base against a gap, 3 'D' adapter base against a gap.  They come in TRACEBACK order, from the end
+ *     cell to the path's first cell, sixteen to a dword, the first in the lowest bits; words behind the last operation are
+ *     not written.  pc_path_cigar turns them around.
+ *   * The trace lives in a scratch buffer of the context; a call is cut into consecutive launches, in stream order on
+ *     `stream`, whose scratch stays under 256 MB each (PC_PATHS_SCRATCH_MB, read per call) but which never hold fewer than
+ *     64 pairs.  Asynchronous; an inconsistency surfaces as PC_ERR_INTERNAL at pc_sync, as for the scans. */
+int pc_align_paths(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                   const int32_t *d_adapter_idx, int64_t n, int max_len, int32_t *d_records, int32_t *d_heads,
+                   uint32_t *d_ops, int64_t ops_pitch_words, void *stream);
+/* Host: (ops, path_len) of one pair -> the forward run-length string ("17=1X4=2I6="), NUL-terminated when it fits in
+ * buflen.  -> the length it needs, without the NUL. */
+int pc_path_cigar(const uint32_t *ops, int path_len, char *buf, size_t buflen);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,

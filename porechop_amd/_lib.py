@@ -25,6 +25,7 @@ EXPORTS = [
     "pc_gz_sized_size", "pc_gz_sized_find_record", "pc_readset_load_gz_range",
     "pc_kmer_count", "pc_kmer_select",
     "pc_scan_device_floored", "pc_floor_skipped",
+    "pc_align_paths", "pc_path_cigar",
 ]
 
 
@@ -80,6 +81,10 @@ def load_library():
     L.pc_scan_device_floored.restype = c_int
     L.pc_floor_skipped.argtypes = [c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     L.pc_floor_skipped.restype = c_int
+    L.pc_align_paths.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp]
+    L.pc_align_paths.restype = c_int
+    L.pc_path_cigar.argtypes = [c_vp, c_int, c_vp, ctypes.c_size_t]
+    L.pc_path_cigar.restype = c_int
     L.pc_sync.argtypes = [c_vp, c_vp]
     L.pc_sync.restype = c_int
     L.pc_copy_windows.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_int, c_vp]

@@ -58,12 +58,86 @@ def records_to_fields(recs):
     return full, aligned, read_start, read_end
 
 
+OP_LETTERS = "=XID"  # pc_align_paths' two-bit operations: equal, unequal, read base over a gap, adapter base over a gap
+
+
+def decode_paths(heads, ops):
+    """heads int[n, 4] and ops [n, pitch] (32-bit words of either signedness) as align_paths returns them, on the host
+    -> n FORWARD operation strings ("===X=I=="): the words hold the steps in traceback order, sixteen to a word, the
+    first in the lowest bits."""
+    heads = np.asarray(heads).reshape(-1, 4)
+    ops = np.ascontiguousarray(np.asarray(ops)).astype(np.int64) & 0xFFFFFFFF
+    ops = ops.reshape(heads.shape[0], -1) if heads.shape[0] else ops.reshape(0, 0)
+    out = []
+    for h, row in zip(heads, ops):
+        L = int(h[0])
+        if L < 0 or L > 16 * row.shape[0]:
+            raise ValueError("a path of %d steps does not fit %d words" % (L, row.shape[0]))
+        k = np.arange(L)
+        codes = (row[k // 16] >> (2 * (k % 16))) & 3
+        out.append("".join(OP_LETTERS[c] for c in codes[::-1]))
+    return out
+
+
+def cigar(opstring):
+    """"===X=I==" -> "3=1X1=1I2=" (an empty path: "")."""
+    out, i = [], 0
+    while i < len(opstring):
+        j = i
+        while j < len(opstring) and opstring[j] == opstring[i]:
+            j += 1
+        if opstring[i] not in OP_LETTERS:
+            raise ValueError("not a path operation: %r" % opstring[i])
+        out.append("%d%s" % (j - i, opstring[i]))
+        i = j
+    return "".join(out)
+
+
+def expand_cigar(text):
+    """The inverse of cigar()."""
+    out, run = [], ""
+    for ch in text:
+        if ch.isdigit():
+            run += ch
+        else:
+            if ch not in OP_LETTERS or not run:
+                raise ValueError("not a run-length path: %r" % text)
+            out.append(ch * int(run))
+            run = ""
+    if run:
+        raise ValueError("not a run-length path: %r" % text)
+    return "".join(out)
+
+
+def render_alignment(read, adapter, head, opstring):
+    """Three lines over the path's columns: the read's bases, a '|' under every '=', the adapter's bases; '-' where a
+    row has a gap.  head = (path_len, read_first, adapter_first, opens) as align_paths returns it."""
+    read = read.decode() if isinstance(read, bytes) else read
+    adapter = adapter.decode() if isinstance(adapter, bytes) else adapter
+    j, i = int(head[1]), int(head[2])
+    top, mid, bot = [], [], []
+    for op in opstring:
+        if op in "=X":
+            top.append(read[j]); bot.append(adapter[i]); mid.append("|" if op == "=" else " ")
+            j += 1; i += 1
+        elif op == "I":
+            top.append(read[j]); bot.append("-"); mid.append(" ")
+            j += 1
+        elif op == "D":
+            top.append("-"); bot.append(adapter[i]); mid.append(" ")
+            i += 1
+        else:
+            raise ValueError("not a path operation: %r" % op)
+    return "\n".join(("".join(top), "".join(mid), "".join(bot)))
+
+
 class Aligner:
     """One GPU context: a scoring scheme + an adapter panel + scratch buffers."""
     fast_prefilter = True      # prefilter_rows is the device's exact prefilter (callers may put it in front of the middle scan)
     score_end_cell = True      # MODE_SCORE records carry the reference's end cell (row, column) besides the score
     reduce_takes_mask = True   # phase_b_reduce(traced_mask=...): pairs whose bit is clear are skipped without a load
     trace_at = True            # MODE_TRACE_AT: the traced record of a pair whose MODE_SCORE record (its end cell) is known
+    paths = True               # align_paths / align_pairs_paths: records with the alignment's path (pc_align_paths)
 
     def __init__(self, adapters, scores=DEFAULT_SCORES, device=-1):
         self.lib = load_library()
@@ -154,6 +228,59 @@ class Aligner:
                                       job_start.ctypes.data, len(job_adapter),
                                       int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s)),
               "pc_scan_device")
+
+    # ---- alignment paths (pc_paths.hip) ---------------------------------------------------------------------------------
+    def longest_adapter(self):
+        return max([len(a) for a in self.adapters] or [0])
+
+    def align_paths(self, arena, win_off, win_len, adapter_idx, max_len=None, stream=None):
+        """The alignments of n (window, adapter) pairs WITH their paths (pc_align_paths).  arena uint8[*], win_off int64[n],
+        win_len int32[n], adapter_idx int32[n]: CUDA tensors; max_len bounds win_len (None: its maximum, one host round
+        trip).  -> (records int32[n, 8], heads int32[n, 4], ops int32[n, pitch]) CUDA tensors: the records are the scans',
+        head = (path_len, read_first, adapter_first, opens), ops holds two bits per step in TRACEBACK order (the words'
+        bits are the library's uint32; decode_paths turns them into forward strings).  Asynchronous; call sync()."""
+        import torch
+        assert arena.is_cuda and win_off.is_cuda and win_len.is_cuda and adapter_idx.is_cuda
+        assert arena.dtype == torch.uint8 and win_off.dtype == torch.int64 and win_len.dtype == torch.int32 and adapter_idx.dtype == torch.int32
+        assert win_off.is_contiguous() and win_len.is_contiguous() and adapter_idx.is_contiguous()
+        n = int(win_off.shape[0])
+        assert int(win_len.shape[0]) == n and int(adapter_idx.shape[0]) == n
+        if max_len is None:
+            max_len = int(win_len.max().item()) if n else 0
+        max_len = int(max_len)
+        pitch = max(1, (max_len + self.longest_adapter() + 15) // 16)
+        dev = arena.device
+        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=dev)
+        heads = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        ops = torch.zeros((n, pitch), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.pc_align_paths(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), adapter_idx.data_ptr(), n,
+                                      max_len, records.data_ptr(), heads.data_ptr(), ops.data_ptr(), pitch, ctypes.c_void_p(s)),
+              "pc_align_paths")
+        return records, heads, ops
+
+    def align_pairs_paths(self, pairs):
+        """pairs: iterable of (read_str, adapter_index) -> (records int32[n, 8], heads int32[n, 4], forward op strings):
+        the host-side convenience beside align_pairs."""
+        import torch
+        offs, lens, idx, chunks, pos = [], [], [], [], 0
+        for rd, ai in pairs:
+            b = rd if isinstance(rd, bytes) else rd.encode()
+            if not 0 <= int(ai) < len(self.adapters):
+                raise ValueError("adapter index %r outside the table of %d" % (ai, len(self.adapters)))
+            offs.append(pos)
+            lens.append(len(b))
+            idx.append(int(ai))
+            chunks.append(b)
+            pos += len(b)
+        dev = torch.device("cuda")
+        arena = torch.from_numpy(np.frombuffer(b"".join(chunks) + b"N", dtype=np.uint8).copy()).to(dev)
+        recs, heads, ops = self.align_paths(arena, torch.tensor(offs, dtype=torch.int64, device=dev),
+                                            torch.tensor(lens, dtype=torch.int32, device=dev),
+                                            torch.tensor(idx, dtype=torch.int32, device=dev), max_len=max(lens or [0]))
+        self.sync()
+        heads = heads.cpu().numpy()
+        return recs.cpu().numpy(), heads, decode_paths(heads, ops.cpu().numpy())
 
     def floor_skipped(self, stream=None):
         """-> (pairs the last floored scan left untraced, those of all floored scans of this context) (pc_floor_skipped;

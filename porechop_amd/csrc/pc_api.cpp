@@ -23,6 +23,7 @@
 #include "../../include/porechop_amd.h"
 #include "pc_bounds.h"
 #include "pc_slow.h"
+#include "pc_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
 #include "pc_prefilter_plan.h"
@@ -164,6 +165,7 @@ struct pc_ctx {
     std::vector<char> ad_slow;               // per adapter: takes the plain-int32 kernel
     std::vector<int64_t> slow_ad_off;        // offsets of the adapters' Dna5 codes in d_slow_ad
     DevBuf d_slow_ad, d_slow_state, d_slow_trace;
+    DevBuf d_paths_trace;                    // pc_align_paths: the packed trace of one launch (pc_paths.hip)
     std::vector<int32_t> last_job_adapter, last_job_adapter_b;
     std::vector<int64_t> last_job_start;
     int last_max_len = -1, last_mode = -1;
@@ -799,7 +801,7 @@ void pc_destroy(pc_ctx *c)
                       &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
                       &c->d_sd_entries, &c->d_sd_meta, &c->d_sd_eq, &c->d_sd_cand, &c->d_sd_count, &c->d_slow_ad, &c->d_slow_state,
-                      &c->d_slow_trace};
+                      &c->d_slow_trace, &c->d_paths_trace};
     if (c->h_sd_count) (void)hipHostFree(c->h_sd_count);
     c->h_table_slot[0].release(); c->h_table_slot[1].release();
     for (DevBuf *b : bufs) b->release();
@@ -1287,6 +1289,61 @@ int pc_debug_value_range(pc_ctx *c, int32_t *lo, int32_t *hi)
     HIP_TRY(hipMemset((char *)c->d_err.p + 16, 0, 8));
     *hi = v[0]; *lo = -v[1];
     return PC_OK;
+}
+
+// trace scratch one launch of the path kernel may take, unless PC_PATHS_SCRATCH_MB says otherwise
+constexpr size_t kPathsScratchMB = 256;
+
+int pc_align_paths(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                   const int32_t *d_adapter_idx, int64_t n, int max_len, int32_t *d_records, int32_t *d_heads,
+                   uint32_t *d_ops, int64_t ops_pitch_words, void *stream_v)
+{
+    if (!c || n < 0 || max_len < 0 || ops_pitch_words < 0) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = upload_panel(c);
+    if (rc) return rc;
+    int rows = 1;
+    for (int len : c->ad_len) {
+        if (len > pcb::MAX_ADAPTER) return PC_ERR_BAD_ARG;          // the code table holds 128 bases per adapter
+        rows = std::max(rows, len);
+    }
+    if (ops_pitch_words < pcpath::ops_words(max_len, c->adapters.empty() ? 0 : rows)) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !d_adapter_idx || !d_records || !d_heads || !d_ops) return PC_ERR_BAD_ARG;
+    if (!pcs::fits(max_len, rows, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
+        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
+                c->match, c->mismatch, c->gap_open, c->gap_extend, max_len, rows);
+        return PC_ERR_UNSUPPORTED_SCORES;
+    }
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    // the budget is read per call (tests force several slices with a few hundred pairs)
+    size_t budget = kPathsScratchMB << 20;
+    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
+    const int groups = pcpath::row_groups(rows);
+    const size_t per_pair = (size_t)std::max(1, max_len) * (size_t)groups * 4;
+    int64_t P = (int64_t)(budget / per_pair) / 64 * 64;
+    if (P < 64) P = 64;                                             // never fewer than a wave, whatever that makes the scratch
+    P = std::min<int64_t>(P, (n + 63) / 64 * 64);
+    if ((rc = c->d_paths_trace.ensure((size_t)P * per_pair + 256))) return rc;
+    pck::PathArgs a;
+    memset(&a, 0, sizeof a);
+    a.arena = (const uint8_t *)d_arena; a.win_off = d_win_off; a.win_len = d_win_len; a.adapter_idx = d_adapter_idx;
+    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
+    a.rows = rows; a.groups = groups; a.max_len = max_len;
+    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
+    a.records = d_records; a.heads = d_heads; a.ops = d_ops; a.ops_pitch = ops_pitch_words;
+    a.trace = c->d_paths_trace.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
+    for (int64_t first = 0; first < n; first += P) {
+        a.first = first; a.count = std::min<int64_t>(P, n - first);
+        if (pck::launch_paths(a, stream)) return PC_ERR_NO_DEVICE;
+    }
+    return PC_OK;
+}
+
+int pc_path_cigar(const uint32_t *ops, int path_len, char *buf, size_t buflen)
+{
+    if (path_len < 0 || (path_len > 0 && !ops)) return 0;
+    return pcpath::path_cigar(ops, path_len, buf, buflen);
 }
 
 int pc_trace_ops_x100(pc_ctx *c)

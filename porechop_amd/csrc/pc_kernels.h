@@ -351,4 +351,28 @@ struct SlowArgs {
 };
 int launch_slow(const SlowArgs &a, void *stream);
 
+// the path kernel of pc_paths.hip: pairs first .. first + count of the caller's arrays, each lane its own adapter of the
+// context's code table; records / heads / ops are indexed by the pair of the CALL, the trace scratch by the pair of the launch
+struct PathArgs {
+    const uint8_t *arena;
+    const int64_t *win_off;
+    const int32_t *win_len;
+    const int32_t *adapter_idx;
+    int64_t first, count;
+    const uint32_t *ad_codes;    // [nadapters][kMaxRows] Dna5 codes
+    const int32_t *ad_len;       // [nadapters]
+    int32_t nadapters;
+    int32_t rows, groups;        // longest adapter of the table (LDS rows) and its row groups of eight (scratch)
+    int32_t max_len;
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t *records;            // [n][8]
+    int32_t *heads;              // [n][4]
+    uint32_t *ops;               // [n][ops_pitch]
+    int64_t ops_pitch;
+    uint32_t *trace;             // [max_len][groups][P] dwords
+    int64_t P;                   // pairs of a launch (stride of the scratch)
+    uint32_t *err;
+};
+int launch_paths(const PathArgs &a, void *stream);
+
 }  // namespace pck

@@ -35,6 +35,7 @@ class Found:
     nearest: Optional[str] = None      # annotation (discover): name of the nearest panel sequence,
     identity: float = 0.0              # its full identity in percent,
     known: bool = False                # and whether that reaches adapter_threshold
+    alignment: Optional[str] = None    # discover(alignments=True): render_alignment of the sequence (as the read) against it
 
 
 def min_count(n_windows, min_fraction=0.05):
@@ -215,10 +216,12 @@ def _blocks(input_path):
 
 
 def discover(input_path, k=12, end_size=150, max_reads=None, device=None, aligner=None, adapter_threshold=90.0,
-             **assemble_options) -> Discovery:
+             alignments=False, **assemble_options) -> Discovery:
     """Census, assembly and annotation of one input (file or Albacore directory) -> Discovery.
     max_reads: count only the first so many reads.  aligner: an Aligner of `device` to use (its adapter table is replaced by
-    the panel's sequences); default: one of its own.  assemble_options: min_fraction, extend_ratio, min_len."""
+    the panel's sequences); default: one of its own.  alignments: every found sequence also gets the alignment against its
+    nearest known adapter, drawn (Found.alignment; Aligner.align_pairs_paths).  assemble_options: min_fraction, extend_ratio,
+    min_len."""
     import torch
     from . import runner
     from .batch import Aligner, records_to_fields
@@ -267,10 +270,19 @@ def discover(input_path, k=12, end_size=150, max_reads=None, device=None, aligne
         if every:
             rec = aligner.align_pairs([(f.sequence, a) for f in every for a in range(len(seqs))])
             full = records_to_fields(rec)[0].reshape(len(every), len(seqs))
+            bests = []
             for f, row in zip(every, full):
                 best = int(np.argmax(row))                         # (the first of equals: panel order)
                 f.nearest, f.identity = names[best], float(row[best])
                 f.known = f.identity >= adapter_threshold
+                bests.append(best)
+            if alignments:
+                from .batch import render_alignment
+                if not getattr(aligner, "paths", False):
+                    raise RuntimeError("this aligner returns no alignment paths (Aligner.align_pairs_paths)")
+                _, heads, strings = aligner.align_pairs_paths(list(zip([f.sequence for f in every], bests)))
+                for f, best, head, text in zip(every, bests, heads, strings):
+                    f.alignment = render_alignment(f.sequence, seqs[best], head, text)
         return Discovery(found[0], found[1], reads=n, windows=2 * n, k=k)
     finally:
         if own:
@@ -278,14 +290,17 @@ def discover(input_path, k=12, end_size=150, max_reads=None, device=None, aligne
 
 
 # ---- command line --------------------------------------------------------------------------------------------------------
-def report_lines(d: Discovery):
+def report_lines(d: Discovery, alignments=False):
     """One line per found sequence: side, sequence, peak, support, share of the side's windows, nearest known adapter, its
-    identity, known / new."""
+    identity, known / new.  alignments: under each line the three lines of its alignment against that adapter (the found
+    sequence above, the adapter below, '|' between equal bases, '-' for gaps), indented by two blanks."""
     lines = []
     for side, found in (("start", d.start), ("end", d.end)):
         for f in found:
             lines.append("%s\t%s\t%d\t%d\t%.4f\t%s\t%.1f\t%s" % (side, f.sequence, f.peak, f.support, f.peak / max(1, d.reads),
                                                                f.nearest, f.identity, "known" if f.known else "new"))
+            if alignments and f.alignment is not None:
+                lines += ["  " + row for row in f.alignment.split("\n")]
     return lines
 
 
@@ -299,16 +314,18 @@ def main(argv=None):
     p.add_argument("--max_reads", type=int, default=None, help="count only the first so many reads (default: all)")
     p.add_argument("--adapters_out", help="write the new sequences as a FASTA of adapter sets")
     p.add_argument("--extra_adapters", help="FASTA of adapter sets (as --adapters_out writes it) to add to the panel of the run")
+    p.add_argument("--alignments", action="store_true",
+                   help="under every found sequence, draw its alignment against the nearest known adapter")
     a = p.parse_args(argv)
     try:
         extra = read_adapters(a.extra_adapters) if a.extra_adapters else []
         d = discover(a.input, k=a.k, end_size=a.end_size, max_reads=a.max_reads, adapter_threshold=a.adapter_threshold,
-                     min_fraction=a.min_fraction, extend_ratio=a.extend_ratio, min_len=a.min_len)
+                     min_fraction=a.min_fraction, extend_ratio=a.extend_ratio, min_len=a.min_len, alignments=a.alignments)
     except ValueError as e:
         sys.exit(str(e))
     except RuntimeError as e:
         sys.exit("Error: " + str(e))
-    print("\n".join(["side\tsequence\tpeak\tsupport\tshare\tnearest\tidentity\tstatus"] + report_lines(d)))
+    print("\n".join(["side\tsequence\tpeak\tsupport\tshare\tnearest\tidentity\tstatus"] + report_lines(d, a.alignments)))
     new = d.adapter_sets()
     if a.adapters_out:
         write_adapters(a.adapters_out, new)

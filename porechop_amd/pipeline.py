@@ -134,6 +134,9 @@ class EndExplain:
     hits: torch.Tensor        # int32 [H, 6]    job, read_start, read_end (exclusive), matches, aligned_len, full_len
     jobs: List[Tuple[int, int]] = field(default_factory=list)     # job -> (side: 0 start / 1 end, index into Pipeline.sets)
     bins: Optional[list] = None                                   # the bins the call was made over, or None
+    # phase_b_explain(paths=True): the path of every hit, row for row with `hits` (Aligner.align_paths' heads and operations)
+    path_heads: Optional[torch.Tensor] = None                     # int32 [H, 4]  path_len, read_first, adapter_first, opens
+    path_ops: Optional[torch.Tensor] = None                       # int32 [H, pitch]
 
 
 def _round6(x):
@@ -786,10 +789,35 @@ class Pipeline:
         self.stats["pairs_end"] += sum(int(j[1].shape[0]) for j in jobs)
         return (start_trim, end_trim, fulls) if full_for else (start_trim, end_trim)
 
+    def _hit_paths(self, reads, jobs, sides, hit_first, hits):
+        """The paths of the qualifying alignments (Aligner.align_paths, one call): the pair list is built on the device -- a
+        hit's read from hit_first, its window and adapter from its job -- and the returned records must carry the hit's
+        read_start, read_end, matches, aligned_len and full_len.  -> (heads int32 [H, 4], ops int32 [H, pitch])."""
+        if not getattr(self.aligner, "paths", False):
+            raise RuntimeError("this aligner returns no alignment paths (Aligner.align_paths)")
+        dev = self.device
+        H = int(hits.shape[0])
+        so, sl = self._end_windows(reads, None, "start")
+        eo, el = self._end_windows(reads, None, "end")
+        hj = hits[:, 0].to(torch.int64)
+        hr = torch.searchsorted(hit_first[1:].contiguous(), torch.arange(H, dtype=torch.int64, device=dev), right=True)
+        is_end = torch.tensor([bool(s_) for s_ in sides], dtype=torch.bool, device=dev)[hj]
+        off = torch.where(is_end, eo[hr], so[hr]).contiguous()
+        length = torch.where(is_end, el[hr], sl[hr]).to(torch.int32).contiguous()
+        adapter = torch.tensor([j[0] for j in jobs], dtype=torch.int32, device=dev)[hj].contiguous()
+        recs, heads, ops = self.aligner.align_paths(self._ends_arena(reads), off, length, adapter, max_len=self.p.end_size)
+        same = (recs[:, 0] == hits[:, 1]) & (recs[:, 1] + 1 == hits[:, 2]) & (recs[:, 5:8] == hits[:, 3:6]).all(dim=1)
+        if H and not bool(same.all()):
+            k = int(torch.nonzero(~same)[0])
+            raise RuntimeError("alignment path of hit %d (read %d, job %d) does not carry the hit's record: %r against %r"
+                               % (k, int(hr[k]), int(hj[k]), recs[k].tolist(), hits[k].tolist()))
+        return heads, ops
+
     def phase_b_explain(self, reads: DeviceReads, matching: List[int], bins=None, barcode_threshold: float = 75.0,
-                        barcode_diff: float = 5.0, require_two: bool = False):
+                        barcode_diff: float = 5.0, require_two: bool = False, paths: bool = False):
         """Phase B with its reasons kept: -> (start_trim, end_trim int32[R], call -- numpy int64[R] as phase_b_demux gives it,
         or None without bins --, EndExplain).  The trims and the call are the ones phase_b / phase_b_demux return.
+        paths=True: the EndExplain also carries the path of every qualifying alignment (_hit_paths; middle hits have none).
 
         This route runs phase B with EVERY pair traced (prune=False).  Under the exact pruning only the alignments that can
         decide a trim or a call are traced -- the non-deciding alignments and the second-best barcode are deliberately left
@@ -813,6 +841,9 @@ class Pipeline:
             ex = EndExplain(summary, torch.zeros((R, 4), dtype=torch.float64, device=dev),
                             torch.zeros(R + 1, dtype=torch.int64, device=dev), torch.zeros((0, 6), dtype=torch.int32, device=dev),
                             list(where), bins)
+            if paths:
+                ex.path_heads = torch.zeros((0, 4), dtype=torch.int32, device=dev)
+                ex.path_ops = torch.zeros((0, 1), dtype=torch.int32, device=dev)
             return summary[:, 0].contiguous(), summary[:, 1].contiguous(), call, ex
         sides = [w[0] for w in where]
         outs, out, rec_off = self._scan_jobs(self._ends_arena(reads), jobs, MODE_TRACE, p.end_size, with_layout=True)
@@ -833,6 +864,8 @@ class Pipeline:
             if bins:
                 call = call_barcodes(len(bins), S, E, barcode_threshold, barcode_diff, require_two)
         ex = EndExplain(summary, bscore, hit_first, hits, list(where), bins)
+        if paths:
+            ex.path_heads, ex.path_ops = self._hit_paths(reads, jobs, sides, hit_first, hits)
         return summary[:, 0].contiguous(), summary[:, 1].contiguous(), call, ex
 
     def _explain_torch(self, rec, sides, jb):

@@ -94,6 +94,7 @@ class RunExplain:
     middle_names: List[str]
     albacore: Optional[List[Optional[str]]] = None
     calls: Optional[List[str]] = None        # the final call, after the Albacore rule
+    hit_cigars: Optional[List[str]] = None   # run(..., report_paths=True): per row of `hits`, "read_first|adapter_first|CIGAR"
 
     @staticmethod
     def identity(matches, length):
@@ -106,6 +107,15 @@ class RunExplain:
         out = ([], [])
         for j, rs, re, m, al, fl in self.hits[int(self.hit_first[r]):int(self.hit_first[r + 1])].tolist():
             out[self.job_side[j]].append((self.job_set[j], self.identity(m, fl), self.identity(m, al), rs, re))
+        return out
+
+    def end_cigars(self, r):
+        """-> (start list, end list) of "read_first|adapter_first|CIGAR", entry for entry with end_alignments(r): the path of
+        each alignment in the window coordinates its read_start / read_end use."""
+        out = ([], [])
+        a, b = int(self.hit_first[r]), int(self.hit_first[r + 1])
+        for (j, *_), text in zip(self.hits[a:b].tolist(), self.hit_cigars[a:b]):
+            out[self.job_side[j]].append(text)
         return out
 
     def barcodes(self, r):
@@ -124,12 +134,16 @@ REPORT_COLUMNS = ["name", "length", "start_trim", "end_trim", "start_alignments"
                   "best_end_barcode", "best_end_identity", "second_end_barcode", "second_end_identity", "albacore_call", "barcode_call"]
 
 
-def report_header():
-    return "#" + "\t".join(REPORT_COLUMNS) + "\n"
+REPORT_PATH_COLUMNS = ["start_cigars", "end_cigars"]              # appended by run(..., report_paths=True)
+
+
+def report_header(paths=False):
+    return "#" + "\t".join(REPORT_COLUMNS + (REPORT_PATH_COLUMNS if paths else [])) + "\n"
 
 
 def report_rows(ex: RunExplain, names, lengths):
-    """The report's rows for the reads of `ex` (TSV; list columns ';'-joined, '.' when empty or not applicable)."""
+    """The report's rows for the reads of `ex` (TSV; list columns ';'-joined, '.' when empty or not applicable).  With the
+    per-hit paths (ex.hit_cigars) two columns follow: start_cigars / end_cigars, entry for entry with the alignment columns."""
     rows = []
     for r in range(ex.summary.shape[0]):
         starts, ends = ex.end_alignments(r)
@@ -144,6 +158,8 @@ def report_rows(ex: RunExplain, names, lengths):
                 cols += [name, "%.6f" % v]
             alb = ex.albacore[r] if ex.albacore is not None else None
             cols += [alb if alb is not None else ".", ex.calls[r]]
+        if ex.hit_cigars is not None:
+            cols += [";".join(xs) or "." for xs in ex.end_cigars(r)]
         rows.append("\t".join(cols) + "\n")
     return "".join(rows)
 
@@ -158,7 +174,7 @@ def _chain(firsts, tables):
     return np.concatenate(out), np.concatenate(tables)
 
 
-def _host_explain(parts, R, pl, match_idx, sc, albacore):
+def _host_explain(parts, R, pl, match_idx, sc, albacore, paths=False):
     """RunExplain of R reads from the EndExplain of every block (in order) and the host results of their scan (sc: _Scan, with
     the middle hits' identities)."""
     hits_h, hits_id = sc.hits, sc.identity
@@ -172,12 +188,21 @@ def _host_explain(parts, R, pl, match_idx, sc, albacore):
         summary[:, 4:10] = -1
         bscore = np.zeros((R, 4), dtype=np.float64)
         hits, hit_first, jobs = np.zeros((0, 6), dtype=np.int32), np.zeros(R + 1, dtype=np.int64), []
+    cigars = None
+    if parts and all(e.path_heads is not None for e in parts):
+        from .batch import cigar, decode_paths
+        cigars = []
+        for e in parts:                                               # chained like `hits`
+            heads = e.path_heads.cpu().numpy()
+            cigars += ["%d|%d|%s" % (int(h[1]), int(h[2]), cigar(t)) for h, t in zip(heads, decode_paths(heads, e.path_ops.cpu().numpy()))]
+    elif not parts and paths:
+        cigars = []
     order = np.argsort(hits_h[:, 0], kind="stable")                  # per read, in discovery order
     middle_first = np.zeros(R + 1, dtype=np.int64)
     np.cumsum(np.bincount(hits_h[:, 0], minlength=R), out=middle_first[1:])
     return RunExplain(summary, bscore, hit_first, hits, [side for side, _ in jobs], [pl.sets[si].name for _, si in jobs], sc.bin_names,
                       middle_first, hits_h[order][:, 1:4], hits_id[order],
-                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, sc.calls)
+                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, sc.calls, cigars)
 
 
 # (read, adapter) pairs one block of phases B / C may hold at a time: 8 ints each, a few copies -> a few GB of HBM
@@ -420,11 +445,11 @@ def _find_sets(pl, panel, reads, check_idx, opts, barcode_dir, sharded=False):
     return matching, [index_of[id(s)] for s in matching], orientation
 
 
-def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None):
+def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, explain_paths=False):
     """Phases B (+ barcode calls) and C for R resident reads -> (start_trim, end_trim [device int32], bin index per
     read [numpy int64, -1 = none], MiddleHits or None).
     explain: a list that receives the EndExplain of every block; phase B then runs with every pair traced
-    (Pipeline.phase_b_explain) -- the same trims and calls."""
+    (Pipeline.phase_b_explain) -- the same trims and calls; explain_paths: with the path of every qualifying alignment."""
     dev = pl.device
     start_trim = torch.zeros(R, dtype=torch.int32, device=dev)
     end_trim = torch.zeros(R, dtype=torch.int32, device=dev)
@@ -449,7 +474,8 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
             sub = reads if (b0 == 0 and b1 == R) else DeviceReads(reads.arena, reads.off[b0:b1], reads.length[b0:b1])
             if explain is not None:
                 st_b, et_b, ci_b, ex_b = pl.phase_b_explain(sub, match_idx, bins if check_barcodes else None, opts.barcode_threshold,
-                                                            opts.barcode_diff, opts.require_two_barcodes)
+                                                            opts.barcode_diff, opts.require_two_barcodes,
+                                                            **({"paths": True} if explain_paths else {}))
                 explain.append(ex_b)
                 if check_barcodes:
                     ci_parts.append(ci_b)
@@ -495,12 +521,12 @@ class _Scan:
 
 
 def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, read_base=0,
-                  gather=None):
+                  gather=None, explain_paths=False):
     """_scan_reads for R resident reads, then everything a run needs of it on the host -> _Scan.  The hits' reads are numbered
     from read_base.  gather: called with the device tensors (start_trim, end_trim, bin index, hits [H, 4]) before they leave the
     device -> the same four for the reads the _Scan is to cover (run() gathers every rank's there)."""
     dev = pl.device
-    start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain)
+    start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain, explain_paths)
     if hasattr(pl.aligner, "sync"):
         pl.aligner.sync()
     if hits is not None and hits.read.numel():
@@ -533,7 +559,8 @@ def _concat_explain(blocks):
     return RunExplain(cat("summary"), cat("bscore"), hit_first, hits, b0.job_side, b0.job_set, b0.bin_names,
                       middle_first, middle, cat("middle_identity"), b0.middle_names,
                       None if b0.albacore is None else [a for b in blocks for a in b.albacore],
-                      None if b0.calls is None else [c for b in blocks for c in b.calls])
+                      None if b0.calls is None else [c for b in blocks for c in b.calls],
+                      None if b0.hit_cigars is None else [c for b in blocks for c in b.hit_cigars])
 
 
 def _plan_pieces(opts, barcode_dir, lengths, sc, matching, pl, match_idx):
@@ -595,14 +622,15 @@ def _stream_block_bytes():
 
 
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
-                 adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None) -> Optional[RunResult]:
+                 adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
+                 report_paths: bool = False) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
     Phase A and the set-level rules run once, on the first block, which must hold the check reads.  Everything after
     that is per read in Porechop (phases B and C, barcode calls, splitting, naming), so the output files are the ones
     run() writes.  Plain FASTA files (cut where a line begins with '>') and the gzip forms of both stream the same way.
-    report: the per-read report of run(), appended block after block (the same bytes as a whole run's).
+    report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths as in run().
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
@@ -731,7 +759,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     try:
         if report is not None:
             report_fh = open(report, "w")
-            report_fh.write(report_header())
+            report_fh.write(report_header(report_paths))
         rs = first
         while rs is not None:
             if failure:
@@ -745,11 +773,11 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 res.matching_sets = [s.name for s in matching]
                 res.barcode_orientation = orientation
             ex_parts = [] if report is not None else None
-            sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts)
+            sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts, explain_paths=report_paths)
             if barcode_dir is not None:
                 calls_all.extend(sc.calls)
             if report is not None:
-                ex = _host_explain(ex_parts, R, pl, match_idx, sc, None)
+                ex = _host_explain(ex_parts, R, pl, match_idx, sc, None, report_paths)
                 report_fh.write(report_rows(ex, [rs.name(i) for i in range(R)], rs.lengths))
                 ex_blocks.append(ex)
             pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
@@ -972,7 +1000,7 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
-        adapter_panel: List[AdapterSet] = None, report: str = None) -> RunResult:
+        adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -980,6 +1008,10 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     the middle hits behind every trim and call, one TSV row per read in input order) and fills RunResult.explain.  Phase B
     then runs with every pair traced (Pipeline.phase_b_explain); trims, calls and output files are the same bytes as
     without it.  Not available in a sharded run.
+    report_paths=True appends two columns, start_cigars and end_cigars: per entry of start_alignments / end_alignments its
+    path as read_first|adapter_first|CIGAR (= X I D run lengths; the adapter plays SAM's reference), in the window
+    coordinates of the entry's read_start / read_end (Pipeline.phase_b_explain(paths=True), Aligner.align_paths).  Without
+    it the report is byte for byte the one above.  Middle hits get no paths.
 
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
@@ -999,13 +1031,15 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
 
     import torch.distributed as dist
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1     # one process per GPU
+    if report_paths and report is None:
+        raise UsageError("Error: --report_paths needs --report")
     if report is not None and sharded:
         raise UsageError("Error: the per-read report is not available in a sharded run (one process per GPU): run it in a single process")
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
-                                report=report)
+                                report=report, report_paths=report_paths)
         if streamed is not None:
             return streamed
 
@@ -1052,7 +1086,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
 
         ex_parts = [] if report is not None else None
         sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, ex_parts, read_base=lo_r,
-                           gather=gather if sharded else None)
+                           gather=gather if sharded else None, explain_paths=report_paths)
         if rank != 0:
             res.start_trim, res.end_trim = sc.st, sc.et
             return res                                           # rank 0 writes
@@ -1061,9 +1095,9 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
             sc.calls = [c if (a is None or a == c) else "none" for c, a in zip(sc.calls, albacore)]
         res.start_trim, res.end_trim, res.barcode_calls = sc.st, sc.et, sc.calls
         if report is not None:
-            res.explain = _host_explain(ex_parts, R, pl, match_idx, sc, albacore)
+            res.explain = _host_explain(ex_parts, R, pl, match_idx, sc, albacore, report_paths)
             with open(report, "w") as fh:
-                fh.write(report_header())
+                fh.write(report_header(report_paths))
                 fh.write(report_rows(res.explain, [rs.name(i) for i in range(R)], rs.lengths))
             lap("report")
 
