@@ -27,6 +27,7 @@
 #include "pc_jit.h"
 #include "pc_kernels.h"
 #include "pc_prefilter_plan.h"
+#include "pc_scan_plan.h"
 
 #define PC_VERSION "porechop_amd 0.1 (gfx950)"
 
@@ -65,42 +66,6 @@ struct PinBuf {            // page-locked host staging: an async upload from it 
     }
     void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
-
-struct Group {            // tiles that run in one launch
-    int rows;             // 0: generic kernel
-    int gen_max_rows;     // generic: largest adapter in the group
-    bool pad;
-    bool two_pass;
-    size_t tile_begin, tile_count;
-    int max_window;       // for two-pass groups: slab columns needed by the traced window
-    std::vector<pck::TileRun> runs;   // the group's tiles, run by run (tile0 relative to tile_begin)
-    // single-pass groups (end windows): the segments -- runs of output slots with one adapter -- and their pieces, for the
-    // two-pass end scan's ordering by end column (pck::launch_bucket_pairs); offsets into the slot's bucket table
-    size_t seg_begin = 0, nseg = 0, blk_begin = 0, nblk = 0;
-    // two-pass groups of a PC_MODE_TWO_PASS call have them too: the second pass of a floored call puts the pairs below their
-    // job's score floor behind the others of their segment.  seg_job[s] = 2 * job + (0: its first adapter, 1: its second)
-    std::vector<int32_t> seg_job;
-};
-
-inline int64_t run_tiles(const pck::TileRun &r) { return r.dual ? (r.n + 63) / 64 : (r.n + 127) / 128; }
-// pairs in tiles [b, e) of a run
-inline int64_t run_pairs(const pck::TileRun &r, int64_t b, int64_t e)
-{
-    const int64_t w = r.dual ? 64 : 128;
-    const int64_t windows = std::min<int64_t>(r.n, w * e) - w * b;
-    return windows <= 0 ? 0 : (r.dual ? 2 * windows : windows);
-}
-// pairs in tiles [b, e) of a group
-inline int64_t group_pairs(const Group &g, size_t b, size_t e)
-{
-    int64_t np = 0;
-    for (const pck::TileRun &r : g.runs) {
-        const int64_t t0 = r.tile0, t1 = r.tile0 + run_tiles(r);
-        const int64_t lo = std::max<int64_t>(t0, (int64_t)b), hi = std::min<int64_t>(t1, (int64_t)e);
-        if (lo < hi) np += run_pairs(r, lo - t0, hi - t0);
-    }
-    return np;
-}
 
 }  // namespace
 
@@ -156,11 +121,7 @@ struct pc_ctx {
     int64_t pf_deferred_cap = 0;                // > 0: the last prefilter call left its count check to pc_prefilter_overflowed
     // cached job table (bench loops repeat the same one: skip the re-upload).  The tile table itself only
     // exists on the device: it is expanded there from the groups' runs (one per job and shape).
-    std::vector<Group> groups;
-    // jobs the packed 16-bit kernels cannot take (scheme outside pcb::scores_supported, adapter above pcb::MAX_ADAPTER):
-    // they run the plain-int32 kernel of pc_slow.hip after the tiles, each with its place in the output kept
-    struct SlowJob { int64_t win_start, n, out_base; int adapter; };
-    std::vector<SlowJob> slow_jobs;
+    pcn::Table table;                        // the plan of the last job list (pc_scan_plan.h): groups, plain-int32 jobs, total
     bool slow_scheme = false;                // the scoring scheme itself is outside the packed kernels' exact range
     std::vector<char> ad_slow;               // per adapter: takes the plain-int32 kernel
     std::vector<int64_t> slow_ad_off;        // offsets of the adapters' Dna5 codes in d_slow_ad
@@ -179,8 +140,6 @@ struct pc_ctx {
 };
 
 namespace {
-
-int drift_period(const pc_ctx *c);
 
 using pcp::dna5;
 
@@ -273,18 +232,43 @@ int upload_panel(pc_ctx *c)
     return PC_OK;
 }
 
-// Build (or reuse) the tile table for a job list.  Job k scans windows [job_start[k], job_start[k+1])
-// against adapter job_adapter[k] and, when job_adapter_b[k] >= 0, ALSO against that second adapter in
-// the same pass (both halves of a lane then read the same window: one read stream instead of two).
-// Outputs: out_start(k) = sum over k' < k of n_k' * (1 or 2); adapter A's records first, then B's.
-int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapter_b, const int64_t *job_start,
-                int njobs, int max_len, int mode, int64_t *total_out)
+// The scan's environment switches, all read here, once per process -- except PC_FORCE_CHUNKS and PC_NO_SCORE_FORK, which
+// are read for every call (tests change them between calls).
+pcn::Options scan_options()
+{
+    static const pcn::Options once = [] {
+        auto on = [](const char *name) { const char *e = getenv(name); return e && *e && *e != '0'; };
+        pcn::Options o;
+        o.no_split_dual = on("PC_NO_SPLIT_DUAL");
+        o.no_merge_small = on("PC_NO_MERGE_SMALL");
+        o.f16_disabled = on("PC_DISABLE_F16");
+        o.no_trace_fork = on("PC_NO_TRACE_FORK");     // (a profile whose per-kernel durations add up to the step)
+        o.no_end_order = on("PC_NO_END_ORDER");
+        o.no_pair_trace_bound = on("PC_NO_PAIR_TRACE_BOUND");
+        return o;
+    }();
+    pcn::Options o = once;
+    if (const char *f = getenv("PC_FORCE_CHUNKS")) o.force_chunks = atoi(f);
+    o.no_score_fork = getenv("PC_NO_SCORE_FORK") != nullptr;
+    return o;
+}
+
+pcn::Params plan_params(const pc_ctx *c)
+{
+    pcn::Params p;
+    p.ncu = c->ncu; p.len_hint = c->len_hint; p.int16_only = c->int16_only;
+    p.match = c->match; p.mismatch = c->mismatch; p.gap_open = c->gap_open; p.gap_extend = c->gap_extend;
+    p.opt = scan_options();
+    return p;
+}
+
+// Build (or reuse) the tile table for a job list: the plan is pcn::build_table's (the jobs' contract is stated there), the
+// tile table itself is expanded from the plan's runs on the device.
+int build_tiles(pc_ctx *c, const pcn::Params &p, const int32_t *job_adapter, const int32_t *job_adapter_b, const int64_t *job_start,
+                int njobs, int max_len, int mode)
 {
     std::vector<int32_t> jb(njobs, -1);
     if (job_adapter_b) jb.assign(job_adapter_b, job_adapter_b + njobs);
-    int64_t tot = 0;
-    for (int k = 0; k < njobs; ++k) tot += (job_start[k + 1] - job_start[k]) * (jb[k] >= 0 ? 2 : 1);
-    if (total_out) *total_out = tot;
     const bool same = c->tiles_uploaded && c->last_max_len == max_len && c->last_mode == mode &&
                       (int)c->last_job_adapter.size() == njobs &&
                       std::equal(job_adapter, job_adapter + njobs, c->last_job_adapter.begin()) &&
@@ -292,175 +276,16 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
                       std::equal(job_start, job_start + njobs + 1, c->last_job_start.begin());
     if (same) return PC_OK;
 
-    std::map<std::pair<int, int>, std::vector<pck::TileRun>> by_group;   // (rows*2+pad, two_pass) -> runs
-    std::map<std::pair<int, int>, int> group_window;
-    std::vector<pc_ctx::SlowJob> slow;
-    std::map<int64_t, int32_t> job_of_first;
-    int64_t out_pos = 0;
-    for (int k = 0; k < njobs; ++k) {
-        const int ad = job_adapter[k], adb = jb[k];
-        const int nad = (int)c->adapters.size();
-        if (ad < 0 || ad >= nad || adb >= nad) return PC_ERR_BAD_ARG;
-        const int m = c->ad_len[ad], mb = adb >= 0 ? c->ad_len[adb] : m;
-        if (m <= 0 || mb <= 0) return PC_ERR_BAD_ARG;
-        const int64_t ws = job_start[k], n = job_start[k + 1] - job_start[k];
-        if (n < 0) return PC_ERR_BAD_ARG;
-        if (c->ad_slow[ad] || (adb >= 0 && c->ad_slow[adb])) {
-            // no tiles: the plain-int32 kernel runs this job after them (adapter A's records first, then B's)
-            if (n > 0) slow.push_back({ws, n, out_pos, ad});
-            out_pos += n;
-            if (adb >= 0) { if (n > 0) slow.push_back({ws, n, out_pos, adb}); out_pos += n; }
-            continue;
-        }
-        // the register variants run in drifting coordinates: linear-gap schemes (extension made
-        // impossible, pc_bounds.h) and schemes whose gap extension is too large to drift in int16 take
-        // the generic kernel
-        const bool no_drift = drift_period(c) < 64;
-        auto group_of = [&](int ma, int mbb, int window, int *rows_out) -> std::vector<pck::TileRun> & {
-            bool pad = false;
-            int rows = pck::pick_rows(ma, mbb, &pad);         // 0 => generic LDS-state kernel
-            if (no_drift) { rows = 0; pad = true; }
-            const bool two = (mode == PC_MODE_TWO_PASS) || (mode == PC_MODE_SCORE) || (mode == PC_MODE_TRACE_AT) ||
-                             (mode == PC_MODE_AUTO && max_len > 2 * window + 64);
-            // PC_MODE_TRACE_AT over short windows: a traced window never needs to be longer than the windows themselves
-            // (one that holds its read's column 0 starts from the true column 0: no warm-up before it)
-            if (mode == PC_MODE_TRACE_AT) window = std::min(window, std::max(1, max_len));
-            auto key = std::make_pair(rows * 2 + (pad ? 1 : 0), two ? 1 : 0);
-            group_window[key] = std::max(group_window[key], window);
-            *rows_out = rows;
-            return by_group[key];
-        };
-        // one adapter, two windows per lane (the halves read different streams): tiles of 128 windows
-        auto emit_single = [&](int a1, int64_t out_base) {
-            const int m1 = c->ad_len[a1];
-            int rows;
-            auto &v = group_of(m1, m1, c->ad_window[a1], &rows);
-            if (n > 0) v.push_back(pck::TileRun{ws, out_base, n, 0, a1, a1, rows ? rows : m1, 0});
-        };
-        const int window = std::max(c->ad_window[ad], adb >= 0 ? c->ad_window[adb] : 0);
-        const bool two_pass_job = (mode == PC_MODE_TWO_PASS) || (mode == PC_MODE_SCORE) || (mode == PC_MODE_TRACE_AT) ||
-                                  (mode == PC_MODE_AUTO && max_len > 2 * window + 64);
-        // A dual tile runs both halves with the longer adapter's rows and saves the second read stream and
-        // the second byte -> row lookup per column.  For whole reads that is worth more than the padding
-        // rows -- measured on the headline's four middle adapters, 1 M x 8 kb reads: (33 | 30) + (28 | 22)
-        // dual 74.6 ms of pc_spec_score per step, the four adapters alone with two streams per lane 81.3 ms,
-        // where dropping the 9 padded rows of 122 could have saved 5.5 ms (profiles/score_layout_ab.txt) --
-        // so two-pass jobs stay dual.  For 150-byte end windows two adapters of different row classes cost
-        // fewer rows as two single-adapter jobs (same tile count, same output layout).
-        bool pa_ = false, pb_ = false;
-        static const bool no_split = [] { const char *e = getenv("PC_NO_SPLIT_DUAL"); return e && *e && *e != '0'; }();
-        const bool split_dual = adb >= 0 && !two_pass_job && !no_drift && !no_split &&
-                                pck::pick_rows(m, m, &pa_) != pck::pick_rows(mb, mb, &pb_);
-        job_of_first[out_pos] = 2 * k;                         // (first record of a segment -> whose it is)
-        if (adb >= 0) job_of_first[out_pos + n] = 2 * k + 1;
-        if (adb >= 0 && !split_dual) {
-            // both halves of a lane scan the same 64 windows: adapter A's records first, then B's
-            int rows;
-            auto &v = group_of(m, mb, window, &rows);
-            if (n > 0) v.push_back(pck::TileRun{ws, out_pos, n, 0, ad, adb, rows ? rows : std::max(m, mb), 1});
-            out_pos += 2 * n;
-        } else if (adb >= 0) {
-            emit_single(ad, out_pos);
-            emit_single(adb, out_pos + n);
-            out_pos += 2 * n;
-        } else {
-            emit_single(ad, out_pos);
-            out_pos += n;
-        }
-    }
-    // Small single-pass groups run together.  A group is one launch; a handful of jobs of a rare adapter length (phase A:
-    // 217 of the panel's sequences are 24-mers, the other 19 fall into nine row classes of 80-470 tiles each) ends in a
-    // launch that fills a tenth of the chip for the duration of a whole tile, and ten of those in a row cost more than the
-    // 24-mers' launch.  Ascending by rows, groups below kSmallTiles are merged into the next larger small group (its rows,
-    // padded variant: a shorter adapter sits bottom-aligned under padding rows, as in any tile of two different adapters)
-    // until the merged group is large enough; the extra rows are cheap next to an idle chip.  Results do not depend on the
-    // row class a pair runs in (tests/test_gpu_parity.py: ragged / padded classes).
-    {
-        static const bool no_merge = [] { const char *e = getenv("PC_NO_MERGE_SMALL"); return e && *e && *e != '0'; }();
-        const int64_t kSmallTiles = 2048;
-        std::vector<std::pair<int, int>> keys;
-        for (auto &kv : by_group) if (kv.first.second == 0 && kv.first.first / 2 > 0) keys.push_back(kv.first);
-        std::sort(keys.begin(), keys.end(), [](const std::pair<int, int> &x, const std::pair<int, int> &y) {
-            return x.first / 2 != y.first / 2 ? x.first / 2 < y.first / 2 : x.first < y.first; });
-        auto tiles_of = [&](const std::pair<int, int> &k) { int64_t t = 0; for (auto &r : by_group[k]) t += run_tiles(r); return t; };
-        auto padded_class = [](int rows) { for (int r : pck::kPaddedRows) if (r == rows) return true; return false; };
-        bool have_open = false;
-        std::pair<int, int> open;
-        int64_t open_tiles = 0;
-        int open_min_rows = 0;                                         // (never more than twice the rows a pair needs)
-        for (const auto &key : keys) {
-            if (no_merge) break;
-            const int64_t t = tiles_of(key);
-            if (t >= kSmallTiles) continue;                            // large groups stay as they are
-            const int rows_t = key.first / 2;
-            if (have_open && key == open) continue;                    // (already the group the smaller classes were merged into)
-            if (!have_open || rows_t > 2 * open_min_rows) { have_open = true; open = key; open_tiles = t; open_min_rows = rows_t; continue; }
-            if (!padded_class(rows_t) || rows_t < open.first / 2) continue;   // no padded variant of this class: it stays alone
-            const std::pair<int, int> target(rows_t * 2 + 1, 0);
-            std::vector<pck::TileRun> moved;
-            int window = 0;
-            const std::pair<int, int> olds[2] = {open, key};
-            for (const auto &old : olds) {
-                auto it = by_group.find(old);
-                if (it == by_group.end()) continue;
-                for (auto &r : it->second) { r.rows = rows_t; moved.push_back(r); }
-                window = std::max(window, group_window[old]);
-                by_group.erase(it);
-                group_window.erase(old);
-            }
-            // (the padded group of this class may exist already -- e.g. 27-mers beside exact 28-mers: joined, not replaced)
-            auto &dst = by_group[target];
-            for (auto &r : dst) r.rows = rows_t;
-            dst.insert(dst.end(), moved.begin(), moved.end());
-            group_window[target] = std::max(group_window[target], window);
-            open = target; open_tiles += t;
-            if (open_tiles >= kSmallTiles) have_open = false;
-        }
-    }
+    pcn::Table plan;
+    const pcn::Panel panel{(int)c->adapters.size(), c->ad_len.data(), c->ad_window.data(), c->ad_slow.data()};
+    int rc = pcn::build_table(panel, p, job_adapter, jb.data(), job_start, njobs, max_len, mode, plan);
+    if (rc) return rc;
     // from here on the cached table is being replaced: an error below must not leave the "same job list" fast
     // path pointing at half-built groups or an unbuilt slot
     c->tiles_uploaded = false;
     c->last_max_len = -1;
-    c->groups.clear();
-    c->slow_jobs.swap(slow);
-    std::vector<pck::TileRun> all_runs;
-    std::vector<int64_t> seg_first;
-    std::vector<pck::BucketBlock> bblocks;
-    size_t ntiles = 0;
-    for (auto &kv : by_group) {
-        Group g;
-        g.rows = kv.first.first / 2; g.pad = (kv.first.first & 1) != 0; g.two_pass = kv.first.second != 0;
-        g.tile_begin = ntiles;
-        g.max_window = group_window[kv.first];
-        g.gen_max_rows = 1;
-        int64_t t = 0;
-        for (pck::TileRun &r : kv.second) {
-            g.gen_max_rows = std::max(g.gen_max_rows, (int)r.rows);
-            r.tile0 = t;
-            t += run_tiles(r);
-            all_runs.push_back(r);
-            all_runs.back().tile0 += (int64_t)g.tile_begin;     // the device table is indexed over all groups
-        }
-        g.tile_count = (size_t)t;
-        g.runs.swap(kv.second);
-        ntiles += g.tile_count;
-        if (((!g.two_pass || mode == PC_MODE_TRACE_AT) && g.rows > 0) || (g.two_pass && mode == PC_MODE_TWO_PASS)) {
-            g.seg_begin = seg_first.size(); g.blk_begin = bblocks.size();
-            for (const pck::TileRun &r : g.runs) {
-                for (int half = 0; half < (r.dual ? 2 : 1); ++half) {
-                    const int64_t first = r.out0 + (half ? r.n : 0);
-                    const int32_t sgm = (int32_t)(seg_first.size() - g.seg_begin);
-                    seg_first.push_back(first);
-                    g.seg_job.push_back(job_of_first.at(first));
-                    for (int64_t at = 0; at < r.n; at += pck::kBucketBlock)
-                        bblocks.push_back(pck::BucketBlock{first + at, (int32_t)std::min<int64_t>(pck::kBucketBlock, r.n - at), sgm});
-                }
-            }
-            g.nseg = seg_first.size() - g.seg_begin; g.nblk = bblocks.size() - g.blk_begin;
-        }
-        if (g.tile_count) c->groups.push_back(std::move(g));
-    }
-    if (ntiles > (size_t)INT32_MAX) return PC_ERR_BAD_ARG;
+    c->table = std::move(plan);
+    const pcn::Table &t = c->table;
     // Build in the other slot: the scans that read it were enqueued two tables ago (their end is marked by
     // slot_free); the scans in flight on the current slot are not waited for.  No device-wide synchronisation:
     // a caller's upload of the next batch on another stream keeps running.
@@ -468,31 +293,31 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
     const int sl = c->slot;
     HIP_TRY(hipEventSynchronize(c->slot_free[sl]));
     HIP_TRY(hipEventSynchronize(c->table_up[sl]));   // (two tables ago: long past)
-    int rc = c->d_tiles_slot[sl].ensure(std::max<size_t>(1, ntiles) * sizeof(pck::Tile));
+    rc = c->d_tiles_slot[sl].ensure(std::max<size_t>(1, t.ntiles) * sizeof(pck::Tile));
     if (rc) return rc;
-    if ((rc = c->d_runs_slot[sl].ensure(std::max<size_t>(1, all_runs.size()) * sizeof(pck::TileRun)))) return rc;
-    c->bucket_blocks_at = (seg_first.size() * 8 + 15) & ~(size_t)15;
-    if ((rc = c->d_bucket_slot[sl].ensure(c->bucket_blocks_at + std::max<size_t>(1, bblocks.size()) * sizeof(pck::BucketBlock)))) return rc;
-    if (ntiles) {
+    if ((rc = c->d_runs_slot[sl].ensure(std::max<size_t>(1, t.runs.size()) * sizeof(pck::TileRun)))) return rc;
+    c->bucket_blocks_at = (t.seg_first.size() * 8 + 15) & ~(size_t)15;
+    if ((rc = c->d_bucket_slot[sl].ensure(c->bucket_blocks_at + std::max<size_t>(1, t.blocks.size()) * sizeof(pck::BucketBlock)))) return rc;
+    if (t.ntiles) {
         // The tables go up from page-locked memory of the slot (reusable once table_up[sl] has passed, above): the call does not
         // wait for its own upload -- with the tables in locals it had to, and that wait was for EVERYTHING on the context's
         // stream, the previous call's forked launches among them.
-        const size_t seg_bytes = seg_first.size() * 8, blk_bytes = bblocks.size() * sizeof(pck::BucketBlock), run_bytes = all_runs.size() * sizeof(pck::TileRun);
+        const size_t seg_bytes = t.seg_first.size() * 8, blk_bytes = t.blocks.size() * sizeof(pck::BucketBlock), run_bytes = t.runs.size() * sizeof(pck::TileRun);
         const size_t blk_at = (seg_bytes + 15) & ~(size_t)15, run_at = (blk_at + blk_bytes + 15) & ~(size_t)15;
         if ((rc = c->h_table_slot[sl].ensure(run_at + run_bytes))) return rc;
         char *hp = (char *)c->h_table_slot[sl].p;
-        if (!seg_first.empty()) {
-            memcpy(hp, seg_first.data(), seg_bytes);
-            memcpy(hp + blk_at, bblocks.data(), blk_bytes);
+        if (!t.seg_first.empty()) {
+            memcpy(hp, t.seg_first.data(), seg_bytes);
+            memcpy(hp + blk_at, t.blocks.data(), blk_bytes);
             HIP_TRY(hipMemcpyAsync(c->d_bucket_slot[sl].p, hp, seg_bytes, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(hipMemcpyAsync((char *)c->d_bucket_slot[sl].p + c->bucket_blocks_at, hp + blk_at, blk_bytes, hipMemcpyHostToDevice, c->stream));
         }
         // a few hundred bytes per job cross PCIe; the tiles (56 B per 64..128 windows) are written by the GPU
-        memcpy(hp + run_at, all_runs.data(), run_bytes);
+        memcpy(hp + run_at, t.runs.data(), run_bytes);
         HIP_TRY(hipMemcpyAsync(c->d_runs_slot[sl].p, hp + run_at, run_bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipEventRecord(c->table_up[sl], c->stream));
-        if (pck::launch_expand_tiles(c->d_runs_slot[sl].as<pck::TileRun>(), (int)all_runs.size(), c->d_tiles_slot[sl].as<pck::Tile>(),
-                                     (int64_t)ntiles, c->stream))
+        if (pck::launch_expand_tiles(c->d_runs_slot[sl].as<pck::TileRun>(), (int)t.runs.size(), c->d_tiles_slot[sl].as<pck::Tile>(),
+                                     (int64_t)t.ntiles, c->stream))
             return PC_ERR_NO_DEVICE;
         HIP_TRY(hipEventRecord(c->table_ready, c->stream));
     }
@@ -504,139 +329,33 @@ int build_tiles(pc_ctx *c, const int32_t *job_adapter, const int32_t *job_adapte
     return PC_OK;
 }
 
-constexpr int kMaxChunks = 64, kMaxChunksLong = 2048;
 // pairs below their score floor, as two 64-bit counters behind the error words of d_err (bytes 0..23): those of the last floored
 // call, and all since the context was made (pc_floor_skipped)
 constexpr size_t kFloorCounterAt = 32;
 
-// Columns the register variants' drifting coordinates (pc_kernels.hip, column_step) can run before
-// int16 needs a renormalisation: values drift up by eps = -gap_extend per column on top of a true
-// range of at most +-8000 (pcb::scores_supported) and (rows + 2) * eps of row offsets.  0 = the
-// scheme cannot drift (linear-gap mode replaces gap_extend by a huge value).
-int drift_period(const pc_ctx *c)
-{
-    if (pcb::is_linear(c->gap_open, c->gap_extend)) return 0;
-    const long eps = -(long)c->gap_extend;
-    const long k = (24000 - (long)(pcb::MAX_ADAPTER + 2) * eps) / eps;
-    return (int)std::max<long>(0, std::min<long>(k, 1 << 20));
-}
-
-// Column chunks of the score pass.  With enough tiles to fill the chip: 1 (no warm-up overhead).
-// Under-filled (small batches, mask-and-realign rounds): the launch's duration is the serial column
-// loop of one wave, so cut the windows into as many chunks as there are idle wave slots, down to
-// chunks about as long as their SPAN warm-up (exact, see pc_bounds.h).
-int chunks_for(int64_t tile_count, int capacity, int max_len, int max_window)
-{
-    if (tile_count <= 0 || tile_count * 2 > capacity) return 1;
-    int chunks = (int)std::min<int64_t>(kMaxChunks, capacity / tile_count);
-    const int min_len = std::max(128, max_window / 2);
-    return std::max(1, std::min(chunks, max_len / min_len));
-}
-
-struct ScopedTimer {
-    pc_ctx *c; hipStream_t s; bool on; pc_ctx::Timed t;
-    ScopedTimer(pc_ctx *c_, hipStream_t s_, int kind, int64_t pairs) : c(c_), s(s_), on(c_ && c_->timing)     // c_ == null: untimed
+// HIP-event timing of a region of launches (pc_set_timing / pc_get_timing): begin() records on the stream where the region
+// starts, end() where it ends, and files the pair under its kind.  c_ == null: untimed.
+struct TimedRegion {
+    pc_ctx *c = nullptr; hipStream_t s = nullptr; bool on = false; pc_ctx::Timed t;
+    void begin(pc_ctx *c_, hipStream_t s_, int kind, int64_t pairs)
     {
+        c = c_; s = s_; on = c_ && c_->timing;
         if (!on) return;
         t.kind = kind; t.pairs = pairs;
         if (hipEventCreate(&t.e0) != hipSuccess || hipEventCreate(&t.e1) != hipSuccess) { on = false; return; }
         (void)hipEventRecord(t.e0, s);
     }
-    ~ScopedTimer() { if (on) { (void)hipEventRecord(t.e1, s); c->timed.push_back(t); } }
+    void end() { if (on) { (void)hipEventRecord(t.e1, s); c->timed.push_back(t); on = false; } }
+};
+struct ScopedTimer : TimedRegion {
+    ScopedTimer(pc_ctx *c_, hipStream_t s_, int kind, int64_t pairs) { begin(c_, s_, kind, pairs); }
+    ~ScopedTimer() { end(); }
 };
 
-// Resident waves the chip holds for this group's kernels: by register footprint (2 packed VGPRs per
-// row + ~48) for the register variants, by LDS (8 B per row per lane) for the generic one.
-int resident_waves(const pc_ctx *c, const Group &g)
-{
-    const int rows = g.rows ? g.rows : g.gen_max_rows;
-    int per_simd = g.rows ? 512 / (2 * rows + 48) : (int)((160 * 1024) / ((size_t)rows * 520 + 1024)) / 4;
-    per_simd = std::max(1, std::min(8, per_simd));
-    return c->ncu * 4 * per_simd;
-}
-
-// Column chunks of a two-pass group's score pass: the under-filled rule above, or -- reads of very
-// different lengths (the caller's typical length is far below the longest, pc_set_length_hint) -- chunks
-// about as long as a typical read, so that no unit of work is much longer than the others: a launch
-// otherwise lasts as long as its longest read (measured on log-normal lengths, mean 8 kb, longest
-// 113 kb: 3.4 times the balanced duration).  The windows come longest first, units are drawn in
-// that order (work_counter), and chunks beyond a window's end cost a few microseconds.
-bool ragged_lengths(const pc_ctx *c, int max_len) { return c->len_hint > 0 && (int64_t)max_len * 2 > (int64_t)c->len_hint * 3; }
-
-int group_chunks_for(const pc_ctx *c, const Group &g, int max_len)
-{
-    // PC_FORCE_CHUNKS=n (tests): that many column chunks whatever the fill -- 1 runs a whole window in one unit, which a
-    // launch otherwise only does when thousands of tiles fill the chip (tests/test_gpu_ultralong.py: columns beyond 65 535
-    // through the un-chunked branch of the specialised score kernel without a 20 GB batch)
-    if (const char *f = getenv("PC_FORCE_CHUNKS")) {
-        const int n = atoi(f);
-        if (n >= 1) return std::min(n, std::min(kMaxChunks, std::max(1, max_len / std::max(128, g.max_window / 2))));
-    }
-    int chunks = chunks_for((int64_t)g.tile_count, resident_waves(c, g), max_len, g.max_window);
-    if (ragged_lengths(c, max_len)) {
-        const int unit = std::max(c->len_hint, std::max(512, 4 * g.max_window));
-        // (a batch whose longest read is a hundred times the typical one -- a 4 Mb read among 20 kb reads -- needs more than
-        // kMaxChunks units of typical length: up to kMaxChunksLong, as far as the [pair][chunk] pass-1 buffer stays below 4 GiB)
-        const int64_t pairs = std::max<int64_t>(1, group_pairs(g, 0, g.tile_count));
-        const int by_memory = (int)std::max<int64_t>(kMaxChunks, std::min<int64_t>(kMaxChunksLong, ((int64_t)4 << 30) / (pairs * 16)));
-        // ... and few windows (a batch of 40 000 long reads is 625 tiles: units of typical length would be a fifth of the wave slots,
-        // and the launch would last as long as ONE such unit, 5 ms at 20 kb): then the units are made short enough that there are
-        // about three per slot -- the windows' columns, estimated as tiles x typical length, over 3 x the resident waves -- but
-        // not shorter than a few warm-up spans
-        int unit_len = unit;
-        const int64_t slots = resident_waves(c, g);
-        const int64_t est_units = (int64_t)g.tile_count * std::max(1, c->len_hint / std::max(1, unit)) ;
-        if (est_units < 3 * slots) {
-            const int64_t cols = (int64_t)g.tile_count * c->len_hint;
-            unit_len = (int)std::max<int64_t>(std::max(512, 4 * g.max_window), std::min<int64_t>(unit, cols / (3 * slots)));
-        }
-        chunks = std::max(chunks, std::min(by_memory, (max_len + unit_len - 1) / unit_len));
-    }
-    return chunks;
-}
-
-// Workgroups to launch for `ntiles` tiles.  Measured on MI355X (tools/time_score.py, time_trace.py):
-// handing the hardware dispatcher one tile per workgroup beats a persistent grid of exactly the
-// resident waves striding over the tiles -- 4-5 % on the uniform whole-read score pass, 13 % on the
-// traced end windows, whose tiles differ in cost (window lengths, traceback lengths).  The grid is
-// therefore the tile count, bounded only by the per-workgroup scratch (trace slab, last-column
-// save); above the bound the kernels stride.
-constexpr int64_t kMaxGrid = 32768;
-int grid_for(const pc_ctx *c, const Group &g, size_t ntiles, int slab_cols, size_t *slab_stride_dwords)
-{
-    const int rows = g.rows ? g.rows : g.gen_max_rows;
-    int64_t grid = std::max<int64_t>(kMaxGrid, resident_waves(c, g));
-    const size_t stride = (size_t)std::max(1, slab_cols) * pck::trace_words_per_col(rows) * 64;
-    const size_t budget = (size_t)8 << 30;    // keep the trace scratch under 8 GiB
-    while (grid > 1 && (size_t)grid * stride * 4 > budget) grid = grid * 3 / 4;
-    grid = std::min<int64_t>(grid, (int64_t)ntiles);
-    if (slab_stride_dwords) *slab_stride_dwords = stride;
-    return (int)std::max<int64_t>(1, grid);
-}
-
-// The traced scan runs in packed fp16 (pc_kernels.hip trace16_kernel, 13.25 instead of 21 packed ops per
-// two cells) whenever the scheme's values stay exact there for the columns of this launch
-// (pc_bounds.h f16_plan); otherwise -- linear-gap schemes, very large scores, adapters above 72 rows,
-// the LDS-state generic kernel -- in packed int16.  PC_DISABLE_F16=1 forces the int16 kernels.
-bool f16_disabled()
-{
-    static const bool off = [] { const char *e = getenv("PC_DISABLE_F16"); return e && *e && *e != '0'; }();
-    return off;
-}
-
-bool trace16_plan(const pc_ctx *c, int rows, int cols, pcb::F16Plan *out)
-{
-    if (f16_disabled() || c->int16_only || rows <= 0 || !pck::trace16_has(rows)) return false;
-    const pcb::F16Plan p = pcb::f16_plan(c->match, c->mismatch, c->gap_open, c->gap_extend, rows);
-    if (!p.ok || cols > p.max_cols) return false;
-    *out = p;
-    return true;
-}
-
-int launch_traced(const pc_ctx *c, pck::ScanArgs &a, const Group &g, int grid, hipStream_t stream)
+int launch_traced(const pcn::Params &p, pck::ScanArgs &a, const pcn::Group &g, int grid, hipStream_t stream)
 {
     pcb::F16Plan fp;
-    if (trace16_plan(c, g.rows, a.slab_cols, &fp)) {
+    if (pcn::trace16_plan(p, g.rows, a.slab_cols, &fp)) {
         a.f16_cen = fp.cen; a.f16_max_cols = fp.max_cols;
         static const int dbg = [] {
             const char *e = getenv("PC_DEBUG_TRACE"), *r = getenv("PC_CHECK_RANGE");
@@ -648,82 +367,391 @@ int launch_traced(const pc_ctx *c, pck::ScanArgs &a, const Group &g, int grid, h
     return pck::launch_trace(a, g.rows, g.pad, grid, stream);
 }
 
-// One launch of the score pass: a run of tiles, each cut into `chunks` column chunks, writing its
-// [pair][chunk] maxima at k1_ints of the pass-1 buffer; spec = the run-time specialised kernel of
-// the run's adapter pair, or null for the generic kernel (which takes the adapter from each tile).
-// k1_ints may be "virtual": the kernels index a launch's region by GLOBAL pair index, a chunked tail's region only
-// holds its own job's pairs, so its base is moved back by the job's first pair (never dereferenced below the region).
-struct ScoreLaunch { size_t begin, count; int chunks; int64_t k1_ints; pcj::Spec *spec; int adapter_lo, adapter_hi; };
+// ---- one scan call: what its steps share ---------------------------------------------------------------------------
+struct ScanCall {
+    const void *arena; const int64_t *win_off; const int32_t *win_len;      // the caller's reads and windows (device)
+    int max_len, mode;
+    int32_t *out;
+    hipStream_t stream;
+    pcn::Floors floors;
+    int64_t npairs;
+    bool linear;
+    // the plan (plan_scan)
+    pcn::Params p;
+    pcn::Scratch scratch;
+    std::vector<std::vector<pcn::ScoreLaunch>> score_plan;       // per group: the launches of its score pass
+    size_t k1_ints = 0, n_score_launches = 0;
+    size_t unit_ints = 0;                // (real, prefix) tables of the launches cut into very many chunks
+    size_t ordered_segments = 0;         // > 0: some group's second pass is ordered or floored (pcn::ordered_segments)
+    bool any_floored = false;
+    bool fork = false;                   // the single-pass groups alternate between the caller's stream and the context's
+    // where the launches are
+    size_t unit_at = 0, score_launch_no = 0;
+    bool ctx_stream_used = false;
+    TimedRegion fork_region;
+};
 
-// Launch plan of a two-pass group.  Tiles of one job (= one adapter pair) are contiguous.  A job
-// with a specialised kernel and more tiles than resident waves is launched as a balanced head (a
-// multiple of the resident waves, whole windows) plus a tail whose tiles are cut into column
-// chunks: the last, partly filled round of whole tiles would idle part of the chip for a whole tile
-// (measured 5 % at 7.6 tiles per wave, 11 % at 4.05), the chunked tail fills it.  Each chunked tail
-// gets its own region of the pass-1 buffer (its [pair][chunk] indexing differs from the head's).
-std::vector<ScoreLaunch> plan_score_launches(pc_ctx *c, const Group &g, int max_len, int64_t npairs, bool linear,
-                                             int group_chunks, size_t *k1_ints_needed)
+// Everything decided before anything is enqueued: the scratch layout, and the launch plans of the score pass of every two-pass
+// group -- they decide how large the pass-1 buffer must be, and growing it later would pull it from under kernels
+// already in flight.
+void plan_scan(pc_ctx *c, ScanCall &s)
 {
-    std::vector<ScoreLaunch> out;
-    size_t k1 = (size_t)npairs * 4 * (size_t)group_chunks;
-    size_t ri = 0;
-    while (ri < g.runs.size()) {
-        // consecutive runs of one adapter pair share their launches
-        const pck::TileRun &r0 = g.runs[ri];
-        size_t re = ri + 1;
-        while (re < g.runs.size() && g.runs[re].adapter_lo == r0.adapter_lo && g.runs[re].adapter_hi == r0.adapter_hi) ++re;
-        const size_t i = (size_t)r0.tile0;
-        const size_t e = (size_t)(g.runs[re - 1].tile0 + run_tiles(g.runs[re - 1]));
-        // the specialised kernel for this pair, once the work seen for the pair has paid for its
-        // compile (pc_jit.cpp); until then the generic one
-        // (windows of very different lengths: their typical length, not the longest, is what the launch costs)
-        const double est_len = ragged_lengths(c, max_len) ? (double)c->len_hint : (double)max_len;
-        const double est_cells = (double)group_pairs(g, i, e) * est_len * (double)(g.rows ? g.rows : g.gen_max_rows);
-        pcj::Spec *sp = !linear ? pcj::get(c->device, c->adapters[r0.adapter_lo], c->adapters[r0.adapter_hi], c->match,
-                                           c->mismatch, c->gap_open, c->gap_extend, est_cells, c->int16_only)
-                                : nullptr;
-        const size_t n = e - i;
-        if (!sp) {
-            if (!out.empty() && !out.back().spec && out.back().begin + out.back().count == i && out.back().chunks == group_chunks)
-                out.back().count += n;                       // runs of pairs without a kernel share a launch
-            else
-                out.push_back({i, n, group_chunks, 0, nullptr, r0.adapter_lo, r0.adapter_hi});
-        } else {
-            size_t head = n;
-            int tail_chunks = 1;
-            const size_t slots = (size_t)c->ncu * (size_t)sp->blocks_per_cu;
-            // the job's records are [out0, out0 + pairs): its chunked tail gets a region of that many [pair][chunk]
-            // entries (not one sized for the whole call: 98 barcode jobs x 245 M pairs would be terabytes), and only
-            // while the tails of the call stay within kTailBudget -- later jobs then run whole tiles to the end
-            int64_t job_out0 = r0.out0, job_pairs = 0;
-            for (size_t q = ri; q < re; ++q) {
-                job_out0 = std::min<int64_t>(job_out0, g.runs[q].out0);
-                job_pairs = std::max<int64_t>(job_pairs, g.runs[q].out0 + (g.runs[q].dual ? 2 : 1) * g.runs[q].n);
-            }
-            job_pairs -= job_out0;
-            constexpr size_t kTailBudget = (size_t)6 << 30;
-            if (group_chunks == 1 && n > slots && n % slots && (k1 + (size_t)job_pairs * 4 * 8) * 4 <= kTailBudget + (size_t)npairs * 16) {
-                const size_t tail = n % slots;
-                double best = 1.0;                           // in tile-times: one more round of whole tiles
-                const double span = 0.5 * g.max_window;
-                for (int cc = 2; cc <= 8; ++cc) {
-                    if (max_len / cc < std::max(128, g.max_window / 2)) break;
-                    const double rounds = (double)((tail * (size_t)cc + slots - 1) / slots);
-                    const double cost = rounds / cc * (1.0 + cc * span / std::max(1, max_len));
-                    if (cost < best - 0.05) { best = cost; tail_chunks = cc; }
-                }
-                if (tail_chunks > 1) head = n - tail;
-            }
-            out.push_back({i, head, group_chunks, 0, sp, r0.adapter_lo, r0.adapter_hi});
-            if (head < n) {
-                out.push_back({i + head, n - head, tail_chunks, (int64_t)k1 - job_out0 * 4 * tail_chunks, sp, r0.adapter_lo, r0.adapter_hi});
-                k1 += (size_t)job_pairs * 4 * (size_t)tail_chunks;
-            }
-        }
-        ri = re;
+    const std::vector<pcn::Group> &groups = c->table.groups;
+    s.scratch = pcn::scratch_layout(s.p, groups, s.max_len, s.mode);
+    s.fork = s.scratch.n_single >= 2 && s.stream != c->stream && !s.p.opt.no_trace_fork;
+    auto lookup = [&](int lo, int hi, double cells) {
+        pcj::Spec *sp = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only);
+        return pcn::SpecKernel{sp, sp ? sp->blocks_per_cu : 0};
+    };
+    s.score_plan.assign(groups.size(), {});
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const pcn::Group &g = groups[gi];
+        if (!g.two_pass || s.mode == PC_MODE_TRACE_AT) continue;           // (TRACE_AT: the end cells are the caller's)
+        size_t need = 0;
+        s.score_plan[gi] = pcn::plan_score_launches(s.p, g, s.max_len, s.npairs, pcn::group_chunks_for(s.p, g, s.max_len), lookup, &need);
+        s.k1_ints = std::max(s.k1_ints, need);
+        s.n_score_launches += s.score_plan[gi].size();
+        for (const pcn::ScoreLaunch &L : s.score_plan[gi]) if (L.chunks > pcn::kMaxChunks) s.unit_ints += 2 * (L.count + 1);
     }
-    if (k1_ints_needed) *k1_ints_needed = k1;
-    return out;
+    s.ordered_segments = pcn::ordered_segments(s.p, groups, s.mode, s.floors, &s.any_floored);
+}
+
+int grow_buffers(pc_ctx *c, const ScanCall &s)
+{
+    int rc;
+    if ((rc = c->d_slab.ensure(s.scratch.slab_bytes + 256)) || (rc = c->d_fin.ensure(s.scratch.fin_bytes + 256))) return rc;
+    if (s.n_score_launches) {
+        if ((rc = c->d_work.ensure(s.n_score_launches * 4 + 256))) return rc;
+        if (s.unit_ints && (rc = c->d_units.ensure(s.unit_ints * 4 + 256))) return rc;
+    }
+    if (s.ordered_segments &&
+        ((rc = c->d_perm.ensure((size_t)s.npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * s.ordered_segments * pck::kBucketSlots * 4 + 256))))
+        return rc;
+    if (s.scratch.any_two) {                       // (an ordered group is a two-pass group)
+        const size_t n = (size_t)s.npairs;
+        if ((rc = c->d_k1.ensure(s.k1_ints * 4 + 256)) || (rc = c->d_woff2.ensure(n * 8)) || (rc = c->d_wlen2.ensure(n * 4)) ||
+            (rc = c->d_col0.ensure(n * 4)) || (rc = c->d_ntot.ensure(n * 4)) || (rc = c->d_frow.ensure(n * 4)) ||
+            (rc = c->d_fscore.ensure(n * 4)) || (rc = c->d_tcols.ensure(n * 4)))
+            return rc;
+    }
+    return PC_OK;
+}
+
+// Single-pass traced groups of one call run two at a time (see pc_ctx): the fork opens before anything of the call is
+// enqueued and closes behind its last launch; the concurrent launches are timed as ONE region.
+int open_trace_fork(pc_ctx *c, ScanCall &s)
+{
+    if (!s.fork) return PC_OK;
+    int64_t np_all = 0;
+    for (const pcn::Group &g : c->table.groups) if (!g.two_pass) np_all += pcn::group_pairs(g);
+    s.fork_region.begin(c, s.stream, 2, np_all);
+    HIP_TRY(hipEventRecord(c->ev_fork, s.stream));
+    return PC_OK;
+}
+
+int close_trace_fork(pc_ctx *c, ScanCall &s)
+{
+    if (s.ctx_stream_used) {
+        HIP_TRY(hipEventRecord(c->ev_join, c->stream));
+        HIP_TRY(hipStreamWaitEvent(s.stream, c->ev_join, 0));
+    }
+    s.fork_region.end();
+    return PC_OK;
+}
+
+// the work counters of the score launches, the bucket counts and cursors of every ordered group (each group has its own
+// rows: one fill) and this call's counter of pairs below their floor
+int zero_counters(pc_ctx *c, const ScanCall &s)
+{
+    if (s.n_score_launches) HIP_TRY(hipMemsetAsync(c->d_work.p, 0, s.n_score_launches * 4, s.stream));
+    if (s.ordered_segments) HIP_TRY(hipMemsetAsync(c->d_bucket_cnt.p, 0, 2 * s.ordered_segments * pck::kBucketSlots * 4, s.stream));
+    if (s.any_floored) HIP_TRY(hipMemsetAsync((char *)c->d_err.p + kFloorCounterAt, 0, 8, s.stream));
+    return PC_OK;
+}
+
+// what every launch over group gi is told: the caller's windows, the group's tiles and its scratch regions
+pck::ScanArgs group_args(const pc_ctx *c, const ScanCall &s, size_t gi)
+{
+    const pcn::Group &g = c->table.groups[gi];
+    pck::ScanArgs a;
+    memset(&a, 0, sizeof(a));
+    a.arena = (const uint8_t *)s.arena;
+    a.win_off = s.win_off; a.win_len = s.win_len;
+    a.ad_codes = c->d_ad_codes.as<uint32_t>();
+    a.ad_len = c->d_ad_len.as<int32_t>();
+    a.tiles = c->d_tiles_slot[c->slot].as<pck::Tile>() + g.tile_begin;
+    a.ntiles = (int32_t)g.tile_count;
+    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open;
+    a.gap_extend = s.linear ? pcb::kLinearExtend : c->gap_extend;
+    a.init_extend = c->gap_extend; a.linear = s.linear ? 1 : 0;
+    a.kren = std::max(1, pcn::drift_period(c->gap_open, c->gap_extend));
+    a.err = c->d_err.as<uint32_t>();
+    a.slab = (uint32_t *)((char *)c->d_slab.p + s.scratch.slab_off[gi]);
+    a.gen_max_rows = g.gen_max_rows;
+    a.fin_scratch = (uint32_t *)((char *)c->d_fin.p + s.scratch.fin_off[gi]);
+    a.ad_span = c->d_ad_span.as<int32_t>();
+    a.ad_window = c->d_ad_window.as<int32_t>();
+    return a;
+}
+
+// the traced launch of group gi over `slab_cols` columns a window
+int run_traced(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, int slab_cols, pc_ctx *timed, hipStream_t stream)
+{
+    const pcn::Group &g = c->table.groups[gi];
+    size_t stride;
+    const int grid = pcn::grid_for(s.p, g, g.tile_count, slab_cols, &stride);
+    a.out = s.out;
+    a.slab_cols = slab_cols; a.slab_stride = (int64_t)stride;
+    ScopedTimer tm(timed, stream, 2, pcn::group_pairs(g));
+    return launch_traced(s.p, a, g, grid, stream) ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
+// The single-pass groups in table order; under the fork every other one on the context's own stream.
+int run_single_pass_groups(pc_ctx *c, ScanCall &s)
+{
+    int n_forked = 0;
+    for (size_t gi = 0; gi < c->table.groups.size(); ++gi) {
+        if (c->table.groups[gi].two_pass) continue;
+        pck::ScanArgs a = group_args(c, s, gi);
+        hipStream_t ps = (s.fork && (n_forked++ & 1)) ? c->stream : s.stream;
+        if (s.fork && ps == c->stream && !s.ctx_stream_used) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0)); s.ctx_stream_used = true; }
+        const int rc = run_traced(c, s, gi, a, s.max_len, s.fork ? nullptr : c, ps);
+        if (rc) return rc;
+    }
+    return PC_OK;
+}
+
+// A two-pass group's first pass, score only over the whole windows: the launches of its plan, each writing its
+// [pair][chunk] maxima into its region of the pass-1 buffer.
+int score_pass(pc_ctx *c, ScanCall &s, size_t gi, const pck::ScanArgs &a, bool records)
+{
+    const pcn::Group &g = c->table.groups[gi];
+    const std::vector<pcn::ScoreLaunch> &plan = s.score_plan[gi];
+    hipStream_t stream = s.stream;
+    // A score-only call over short windows (phase B's pruning pass: ~100 launches of 150-column windows, one per
+    // adapter pair) cannot cut its tails into column chunks, and every launch would end with a round of tiles that
+    // fills a fraction of the chip (15 625 tiles on 3072 resident waves: 15 % of the launch).  Its launches
+    // alternate between the caller's stream and the context's: the next kernel's first tiles fill the CUs the
+    // previous one's last round leaves idle.  Timed as ONE region.
+    const bool ragged = pcn::ragged_lengths(s.p, s.max_len);
+    const bool sfork = s.mode == PC_MODE_SCORE && !s.fork && stream != c->stream && plan.size() >= 2 && !ragged &&
+                       s.max_len / 2 < std::max(128, g.max_window / 2) && !s.p.opt.no_score_fork;
+    bool any_spec = false;
+    for (const pcn::ScoreLaunch &L : plan) any_spec |= L.spec != nullptr;
+    ScopedTimer region(sfork ? c : nullptr, stream, any_spec ? 3 : 0, pcn::group_pairs(g));
+    if (sfork) {
+        HIP_TRY(hipEventRecord(c->ev_fork, stream));
+        HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0));
+    }
+    size_t launch_in_group = 0;
+    for (const pcn::ScoreLaunch &L : plan) {
+        const int chunk_len = (s.max_len + L.chunks - 1) / L.chunks;
+        int grid = pcn::grid_for(s.p, g, L.count * (size_t)L.chunks, 1, nullptr);
+        const bool alt = sfork && (launch_in_group++ & 1);
+        hipStream_t stream_k = alt ? c->stream : stream;
+        uint32_t *fin_k = (uint32_t *)((char *)a.fin_scratch + (alt ? s.scratch.fin_region[gi] : 0));
+        // windows of very different lengths: exactly the resident workgroups, every further unit drawn from
+        // the counter in launch order -- longest first.  (With a larger grid the first workgroups would stay
+        // resident drawing the short units while the long ones waited for a slot until the very end.)
+        if (ragged)
+            grid = (int)std::min<size_t>((size_t)grid, L.spec ? (size_t)c->ncu * (size_t)L.blocks_per_cu : (size_t)pcn::resident_waves(s.p, g));
+        ScopedTimer tm(sfork ? nullptr : c, stream, L.spec ? 3 : 0, pcn::group_pairs(g, L.begin, L.begin + L.count));   // one timed region per kernel launch
+        // windows cut into very many chunks (a batch with an ultra-long tail): only the chunks that hold columns are units
+        const int32_t *unit_prefix = nullptr;
+        if (L.chunks > pcn::kMaxChunks) {
+            int32_t *real = c->d_units.as<int32_t>() + s.unit_at, *prefix = real + (L.count + 1);
+            s.unit_at += 2 * (L.count + 1);
+            if (pck::launch_unit_prefix(a.tiles + L.begin, (int)L.count, a.win_len, chunk_len, real, prefix, stream_k)) return PC_ERR_NO_DEVICE;
+            unit_prefix = prefix;
+        }
+        if (L.spec) {
+            pcj::SpecArgs sa;
+            memset(&sa, 0, sizeof(sa));
+            sa.arena = a.arena; sa.win_off = a.win_off; sa.win_len = a.win_len;
+            sa.tiles = a.tiles + L.begin; sa.ntiles = (int32_t)L.count;
+            sa.out = c->d_k1.as<int32_t>() + L.k1_ints; sa.fin_scratch = fin_k;
+            sa.gap_open = c->gap_open; sa.gap_extend = c->gap_extend;
+            sa.chunks = L.chunks; sa.chunk_len = chunk_len;
+            sa.span = std::max(c->ad_span[L.adapter_lo], c->ad_span[L.adapter_hi]);
+            sa.err = a.err;
+            sa.work_counter = c->d_work.as<uint32_t>() + s.score_launch_no++;
+            // a score-only request over whole windows: the kernel writes the records itself (no planner launch)
+            sa.rec_out = (records && L.chunks == 1) ? s.out : nullptr;
+            sa.unit_prefix = unit_prefix;
+            if (pcj::launch((const pcj::Spec *)L.spec, sa, grid, stream_k)) return PC_ERR_NO_DEVICE;
+        } else {
+            pck::ScanArgs b = a;
+            b.slab = nullptr;
+            b.tiles = a.tiles + L.begin; b.ntiles = (int32_t)L.count;
+            b.out = c->d_k1.as<int32_t>() + L.k1_ints;
+            b.chunks = L.chunks; b.chunk_len = chunk_len;
+            b.fin_scratch = fin_k;
+            b.work_counter = c->d_work.as<uint32_t>() + s.score_launch_no++;
+            b.unit_prefix = unit_prefix;
+            if (pck::launch_score(b, g.rows, g.pad, grid, stream_k)) return PC_ERR_NO_DEVICE;
+        }
+    }
+    if (sfork) {
+        HIP_TRY(hipEventRecord(c->ev_join, c->stream));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
+    }
+    return PC_OK;
+}
+
+// Between the passes: the planner turns every pair's best cell into its bounded window (per score launch: the [pair][chunk]
+// layout is the launch's); where the end cells are records in the output -- PC_MODE_TRACE_AT, a floored group -- the bucket
+// pass orders the pairs first.  Leaves in `a` what pass 2 reads.
+int plan_windows(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, bool fl)
+{
+    const pcn::Group &g = c->table.groups[gi];
+    const bool records = s.mode == PC_MODE_SCORE || fl;
+    pck::PlanArgs pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.win_off = s.win_off; pl.win_len = s.win_len;
+    pl.win_off2 = c->d_woff2.as<int64_t>(); pl.win_len2 = c->d_wlen2.as<int32_t>();
+    pl.col02 = c->d_col0.as<int32_t>(); pl.ntot2 = c->d_ntot.as<int32_t>();
+    pl.force_row2 = c->d_frow.as<int32_t>(); pl.force_score2 = c->d_fscore.as<int32_t>();
+    // the pair's own bound on the traced columns (schemes of the packed kernels: match > 0, both gap scores < 0)
+    pl.match = c->match; pl.gap_unit = std::min(-c->gap_open, -(s.linear ? c->gap_open : c->gap_extend));
+    pl.trace_cols2 = (!s.p.opt.no_pair_trace_bound && pl.match > 0 && pl.gap_unit > 0) ? c->d_tcols.as<int32_t>() : nullptr;
+    pl.ad_window = c->d_ad_window.as<int32_t>();
+    pl.score_out = records ? s.out : nullptr;
+    // end-aligned windows only for the packed-fp16 traced kernel (it is the one that knows lead-ins)
+    pl.end_align = pcn::trace16_plan(s.p, g.rows, g.max_window + 1) ? 1 : 0;
+    pl.err = a.err;
+    ScopedTimer tm(c, s.stream, 1, pcn::group_pairs(g));
+    for (const pcn::ScoreLaunch &L : s.score_plan[gi]) {
+        if (records && L.chunks == 1 && L.spec) continue;      // records written by the kernel itself
+        pl.k1 = c->d_k1.as<int32_t>() + L.k1_ints;
+        pl.tiles = a.tiles + L.begin; pl.ntiles = (int32_t)L.count; pl.chunks = L.chunks;
+        pl.chunk_len = (s.max_len + L.chunks - 1) / L.chunks;
+        if (pck::launch_plan(pl, s.stream)) return PC_ERR_NO_DEVICE;
+    }
+    if (s.mode == PC_MODE_TRACE_AT || fl) {   // the score records (the caller's / pass 1's), read before pass 2 overwrites them
+        pl.k1 = nullptr; pl.end_records = s.out; pl.score_out = nullptr;
+        if (s.mode == PC_MODE_TRACE_AT) pl.window_cap = std::max(1, s.max_len);
+        pl.tiles = a.tiles; pl.ntiles = (int32_t)g.tile_count; pl.chunks = 1;
+        if (fl || pcn::ordered_trace_at(s.p, g, s.mode)) {
+            pck::BucketArgs b;
+            memset(&b, 0, sizeof b);
+            b.records = s.out;
+            if (fl) {
+                b.mark = s.out;
+                for (size_t sg = 0; sg < g.nseg; ++sg) b.seg_floor[sg] = pcn::seg_floor_of(g, sg, s.floors);
+                b.skipped = (unsigned long long *)((char *)c->d_err.p + kFloorCounterAt);
+                pl.floor_out = s.out;
+                a.skip_marked = 1;
+            }
+            b.seg_first = (const int64_t *)c->d_bucket_slot[c->slot].p + g.seg_begin; b.nsegments = (int32_t)g.nseg;
+            b.blocks = (const pck::BucketBlock *)((const char *)c->d_bucket_slot[c->slot].p + c->bucket_blocks_at) + g.blk_begin;
+            b.nblocks = (int32_t)g.nblk;
+            b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBucketSlots;
+            b.cursors = c->d_bucket_cnt.as<uint32_t>() + (s.ordered_segments + g.seg_begin) * pck::kBucketSlots;
+            b.perm = c->d_perm.as<int64_t>();
+            if (pck::launch_bucket_pairs(b, s.stream)) return PC_ERR_NO_DEVICE;
+            pl.perm = b.perm; a.perm = b.perm;
+        }
+        if (pck::launch_plan(pl, s.stream)) return PC_ERR_NO_DEVICE;
+    }
+    // pass 2: traced window ending at the max cell
+    a.win_off = pl.win_off2; a.win_len = pl.win_len2; a.col0 = pl.col02; a.n_total = pl.ntot2;
+    a.win_by_out = 1;
+    a.force_row = pl.force_row2; a.force_score = pl.force_score2; a.trace_cols = pl.trace_cols2;
+    a.chunks = 1;
+    return PC_OK;
+}
+
+int run_two_pass_group(pc_ctx *c, ScanCall &s, size_t gi)
+{
+    const pcn::Group &g = c->table.groups[gi];
+    const bool fl = pcn::floored(g, s.mode, s.floors);
+    pck::ScanArgs a = group_args(c, s, gi);
+    int rc;
+    if ((rc = score_pass(c, s, gi, a, s.mode == PC_MODE_SCORE || fl))) return rc;
+    if ((rc = plan_windows(c, s, gi, a, fl))) return rc;
+    if (s.mode == PC_MODE_SCORE) return PC_OK;      // no traceback asked for
+    return run_traced(c, s, gi, a, g.max_window + 1, c, s.stream);
+}
+
+// jobs outside the packed kernels' range: plain int32, one lane per pair (pc_slow.hip)
+int run_slow_jobs(pc_ctx *c, const ScanCall &s)
+{
+    for (const pcn::SlowJob &J : c->table.slow_jobs) {
+        const int m = c->ad_len[J.adapter];
+        if (!pcs::fits(s.max_len, m, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
+            fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
+                    c->match, c->mismatch, c->gap_open, c->gap_extend, s.max_len, m);
+            return PC_ERR_UNSUPPORTED_SCORES;
+        }
+        static const size_t budget = [] { const char *e = getenv("PC_SLOW_SCRATCH_MB"); return (size_t)(e && atol(e) > 0 ? atol(e) : 2048) << 20; }();
+        const bool lds = m <= 128;
+        const size_t per_pair = (size_t)std::max(1, s.max_len) * (size_t)m + (lds ? 0 : (size_t)m * 8);
+        if ((size_t)pcn::budget_pairs(budget, per_pair) * per_pair > ((size_t)16 << 30)) {
+            fprintf(stderr, "porechop_amd: a window of %d bases against an adapter of %d needs %zu bytes of trace per pair: too large for the plain-int32 path\n",
+                    s.max_len, m, per_pair);
+            return PC_ERR_ADAPTER_TOO_LONG;
+        }
+        const int64_t P = pcn::slice_pairs(budget, per_pair, J.n);
+        int rc;
+        if ((rc = c->d_slow_trace.ensure((size_t)P * (size_t)std::max(1, s.max_len) * (size_t)m + 256))) return rc;
+        if (!lds && (rc = c->d_slow_state.ensure((size_t)P * (size_t)m * 8 + 256))) return rc;
+        pck::SlowArgs sa;
+        memset(&sa, 0, sizeof sa);
+        sa.arena = (const uint8_t *)s.arena; sa.win_off = s.win_off; sa.win_len = s.win_len;
+        sa.adapter = c->d_slow_ad.as<uint8_t>() + c->slow_ad_off[J.adapter];
+        sa.m = m; sa.max_len = s.max_len;
+        sa.match = c->match; sa.mismatch = c->mismatch; sa.gap_open = c->gap_open; sa.gap_extend = c->gap_extend;
+        sa.out = s.out; sa.state = lds ? nullptr : c->d_slow_state.as<int32_t>(); sa.trace = c->d_slow_trace.as<uint8_t>();
+        sa.P = P; sa.err = c->d_err.as<uint32_t>();
+        ScopedTimer tm(c, s.stream, 2, J.n);
+        for (int64_t first = 0; first < J.n; first += P) {
+            sa.first_window = J.win_start + first; sa.count = std::min<int64_t>(P, J.n - first); sa.out_base = J.out_base + first;
+            if (pck::launch_slow(sa, s.stream)) return PC_ERR_NO_DEVICE;
+        }
+    }
+    return PC_OK;
+}
+
+int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                const int32_t *job_floor, const int32_t *job_floor_b)
+{
+    // 1: the arguments, the panel, the table of the job list
+    if (!c || nwindows < 0 || njobs < 0 || max_len < 0) return PC_ERR_BAD_ARG;
+    if (nwindows == 0 || njobs == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !job_adapter || !job_start || !d_out) return PC_ERR_BAD_ARG;
+    if (job_start[0] < 0 || job_start[njobs] > nwindows) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = upload_panel(c);
+    if (rc) return rc;
+    ScanCall s;
+    s.arena = d_arena; s.win_off = d_win_off; s.win_len = d_win_len; s.max_len = max_len; s.mode = mode; s.out = d_out;
+    s.stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    s.floors.a = job_floor; s.floors.b = job_floor_b;
+    s.linear = pcb::is_linear(c->gap_open, c->gap_extend);
+    s.p = plan_params(c);
+    if ((rc = build_tiles(c, s.p, job_adapter, job_adapter_b, job_start, njobs, max_len, mode))) return rc;
+    s.npairs = c->table.total;
+    if (mode == PC_MODE_SCORE && !c->table.slow_jobs.empty()) {
+        // score-only records (the end cell) feed bounds that are derived for the packed kernels' schemes (pc_select.hip)
+        fprintf(stderr, "porechop_amd: PC_MODE_SCORE is not available for scoring schemes / adapters that take the plain-int32 kernel\n");
+        return PC_ERR_UNSUPPORTED_SCORES;
+    }
+    if (s.stream != c->stream) HIP_TRY(hipStreamWaitEvent(s.stream, c->table_ready, 0));   // the table is built on the context's stream
+    // 2, 3: the plan of the call, and room for it
+    plan_scan(c, s);
+    if ((rc = grow_buffers(c, s))) return rc;
+    // 4: the single-pass groups, side by side on two streams
+    if ((rc = open_trace_fork(c, s)) || (rc = zero_counters(c, s)) || (rc = run_single_pass_groups(c, s))) return rc;
+    // 5: the two-pass groups, one after the other
+    for (size_t gi = 0; gi < c->table.groups.size(); ++gi)
+        if (c->table.groups[gi].two_pass && (rc = run_two_pass_group(c, s, gi))) return rc;
+    if ((rc = close_trace_fork(c, s))) return rc;
+    // 6, 7: the plain-int32 jobs; the last launch that reads this table slot
+    if ((rc = run_slow_jobs(c, s))) return rc;
+    HIP_TRY(hipEventRecord(c->slot_free[c->slot], s.stream));
+    return PC_OK;
 }
 
 }  // namespace
@@ -851,11 +879,6 @@ int pc_set_adapters(pc_ctx *c, const char *const *seqs, int n)
     return upload_panel(c);
 }
 
-static int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                       int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
-                       const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
-                       const int32_t *job_floor, const int32_t *job_floor_b);
-
 int pc_scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                    int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
                    const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v)
@@ -888,396 +911,6 @@ int pc_floor_skipped(pc_ctx *c, void *stream_v, int64_t *last_call, int64_t *tot
     return PC_OK;
 }
 
-static int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                       int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
-                       const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
-                       const int32_t *job_floor, const int32_t *job_floor_b)
-{
-    if (!c || nwindows < 0 || njobs < 0 || max_len < 0) return PC_ERR_BAD_ARG;
-    if (nwindows == 0 || njobs == 0) return PC_OK;
-    if (!d_arena || !d_win_off || !d_win_len || !job_adapter || !job_start || !d_out) return PC_ERR_BAD_ARG;
-    if (job_start[0] < 0 || job_start[njobs] > nwindows) return PC_ERR_BAD_ARG;
-    (void)hipSetDevice(c->device);
-    int rc = upload_panel(c);
-    if (rc) return rc;
-    int64_t npairs = 0;
-    if ((rc = build_tiles(c, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, &npairs))) return rc;
-    if (mode == PC_MODE_SCORE && !c->slow_jobs.empty()) {
-        // score-only records (the end cell) feed bounds that are derived for the packed kernels' schemes (pc_select.hip)
-        fprintf(stderr, "porechop_amd: PC_MODE_SCORE is not available for scoring schemes / adapters that take the plain-int32 kernel\n");
-        return PC_ERR_UNSUPPORTED_SCORES;
-    }
-    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
-    if (stream != c->stream) HIP_TRY(hipStreamWaitEvent(stream, c->table_ready, 0));   // the table is built on the context's stream
-
-    // scratch sizing over all groups
-    // single-pass groups get slab / last-column regions of their own (they run concurrently); two-pass groups
-    // run one after the other and share the region behind them
-    size_t slab_bytes = 0, fin_bytes = 0, slab_single = 0, fin_single = 0;
-    std::vector<size_t> slab_off(c->groups.size(), 0), fin_off(c->groups.size(), 0), fin_region(c->groups.size(), 0);
-    bool any_two = false;
-    int n_single = 0;
-    for (const Group &g : c->groups) {
-        size_t stride;
-        const int cols = g.two_pass ? g.max_window + 1 : max_len;
-        const int grid = grid_for(c, g, g.tile_count, cols, &stride);
-        if (!g.two_pass) {
-            const size_t gi = (size_t)(&g - &c->groups[0]);
-            slab_off[gi] = slab_single; fin_off[gi] = fin_single;
-            slab_single += ((size_t)grid * stride * 4 + 255) & ~(size_t)255;
-            fin_single += ((size_t)grid * (size_t)std::max(1, g.rows ? g.rows : g.gen_max_rows) * 64 * 8 + 255) & ~(size_t)255;
-            ++n_single;
-            continue;
-        }
-        slab_bytes = std::max(slab_bytes, (size_t)grid * stride * 4);
-        const int chunks = g.two_pass ? group_chunks_for(c, g, max_len) : 1;
-        // score pass: chunked launches, and the chunked tails of big jobs (at most 8 chunks x resident waves)
-        const int grid1 = grid_for(c, g, std::max<size_t>(g.tile_count * (size_t)chunks, (size_t)c->ncu * 64), 1, nullptr);
-        // (x2: the specialised score kernel parks the two halves of a lane separately)
-        // (x2 again for a score-only call: its launches alternate between two streams, each with a region of its own)
-        fin_region[(size_t)(&g - &c->groups[0])] = (size_t)std::max(grid, grid1) * (size_t)std::max(1, g.rows ? g.rows : g.gen_max_rows) * 64 * 8 * 2;
-        fin_bytes = std::max(fin_bytes, fin_region[(size_t)(&g - &c->groups[0])] * (mode == PC_MODE_SCORE ? 2 : 1));
-        any_two |= g.two_pass;
-    }
-    for (size_t gi = 0; gi < c->groups.size(); ++gi)
-        if (c->groups[gi].two_pass) { slab_off[gi] = slab_single; fin_off[gi] = fin_single; }
-    slab_bytes += slab_single; fin_bytes += fin_single;
-    if ((rc = c->d_slab.ensure(slab_bytes + 256)) || (rc = c->d_fin.ensure(fin_bytes + 256))) return rc;
-    // (PC_NO_TRACE_FORK=1 keeps them on one stream: a profile whose per-kernel durations add up to the step)
-    static const bool no_trace_fork = [] { const char *e = getenv("PC_NO_TRACE_FORK"); return e && *e && *e != '0'; }();
-    const bool fork = n_single >= 2 && stream != c->stream && !no_trace_fork;
-    pc_ctx::Timed fork_timer;
-    bool fork_timed = false;
-    if (fork) {
-        int64_t np_all = 0;
-        for (const Group &g : c->groups) if (!g.two_pass) np_all += group_pairs(g, 0, g.tile_count);
-        if (c->timing && hipEventCreate(&fork_timer.e0) == hipSuccess && hipEventCreate(&fork_timer.e1) == hipSuccess) {
-            fork_timer.kind = 2; fork_timer.pairs = np_all; fork_timed = true;
-            (void)hipEventRecord(fork_timer.e0, stream);            // the concurrent launches are timed as ONE region
-        }
-        HIP_TRY(hipEventRecord(c->ev_fork, stream));
-    }
-    // launch plans of the score pass of every two-pass group, made BEFORE anything is enqueued: they
-    // decide how large the pass-1 buffer must be, and growing it later would pull it from under
-    // kernels already in flight
-    std::vector<std::vector<ScoreLaunch>> score_plan(c->groups.size());
-    std::vector<int> group_chunks(c->groups.size(), 1);
-    size_t k1_ints = 0, n_score_launches = 0;
-    {
-        const bool lin = pcb::is_linear(c->gap_open, c->gap_extend);
-        for (size_t gi = 0; gi < c->groups.size(); ++gi) {
-            const Group &g = c->groups[gi];
-            if (!g.two_pass || mode == PC_MODE_TRACE_AT) continue;           // (TRACE_AT: the end cells are the caller's)
-            group_chunks[gi] = group_chunks_for(c, g, max_len);
-            size_t need = 0;
-            score_plan[gi] = plan_score_launches(c, g, max_len, npairs, lin, group_chunks[gi], &need);
-            k1_ints = std::max(k1_ints, need);
-            n_score_launches += score_plan[gi].size();
-        }
-    }
-    size_t unit_ints = 0;                   // (real, prefix) tables of the launches cut into very many chunks
-    for (size_t gi = 0; gi < c->groups.size(); ++gi)
-        for (const ScoreLaunch &L : score_plan[gi]) if (L.chunks > kMaxChunks) unit_ints += 2 * (L.count + 1);
-    if (n_score_launches) {
-        if ((rc = c->d_work.ensure(n_score_launches * 4 + 256))) return rc;
-        HIP_TRY(hipMemsetAsync(c->d_work.p, 0, n_score_launches * 4, stream));
-        if (unit_ints && (rc = c->d_units.ensure(unit_ints * 4 + 256))) return rc;
-    }
-    size_t unit_at = 0;
-    size_t score_launch_no = 0;
-    // PC_MODE_TRACE_AT (the traced minority of a pruned phase B), where the end cells are the caller's: the pairs of each
-    // segment are taken by end column (coarsely), so that a tile is as long as its latest end cell needs, and every pair traces
-    // only the columns its path can occupy (plan_kernel).  PC_NO_END_ORDER=1: the pairs as handed over.  (The same scheme over
-    // PC_MODE_TRACE end windows, behind a score-only pass of the traced kernel, did not pay: profiles/r06_two_pass_ends.txt.)
-    static const bool no_end_order = [] { const char *e = getenv("PC_NO_END_ORDER"); return e && *e && *e != '0'; }();
-    auto ordered_trace_at = [&](const Group &g) -> bool {
-        pcb::F16Plan fp;
-        return !no_end_order && mode == PC_MODE_TRACE_AT && g.two_pass && g.rows > 0 && g.nseg > 0 && trace16_plan(c, g.rows, g.max_window + 1, &fp);
-    };
-    // A floored PC_MODE_TWO_PASS call (pc_scan_device_floored): between the passes the pairs whose best score is below their job's
-    // floor are answered by the planner ("no alignment") and put behind the others of their segment, by the same bucket pass, so
-    // that pass 2 costs what the remaining pairs cost: its tiles hold them densely and the tiles behind them end at once.  The
-    // first pass then leaves score records in d_out -- the specialised kernel writes them itself where a window is one unit --
-    // which is where the bucket pass and the planner read the end cells, as in PC_MODE_TRACE_AT.  A group none of whose jobs
-    // has a floor (INT32_MIN) runs exactly as in an unfloored call.
-    auto seg_floor_of = [&](const Group &g, size_t s) -> int32_t {
-        const int32_t sj = g.seg_job[s];
-        const int32_t *f = (sj & 1) ? job_floor_b : job_floor;
-        return f ? f[sj >> 1] : INT32_MIN;
-    };
-    auto floored = [&](const Group &g) -> bool {
-        if (!(job_floor || job_floor_b) || mode != PC_MODE_TWO_PASS || !g.two_pass || g.nseg == 0 || g.nseg > (size_t)pck::kFloorSegments ||
-            g.seg_job.size() != g.nseg)
-            return false;
-        for (size_t s = 0; s < g.nseg; ++s) if (seg_floor_of(g, s) != INT32_MIN) return true;
-        return false;
-    };
-    bool any_ordered = false, any_floored = false;
-    size_t ordered_segments = 0;         // segments up to the last one of an ordered group: the stride of the bucket counters
-    for (const Group &g : c->groups) {
-        const bool fl = floored(g);
-        any_floored |= fl;
-        if (fl || ordered_trace_at(g)) { any_ordered = true; ordered_segments = std::max(ordered_segments, g.seg_begin + g.nseg); }
-    }
-    if (any_ordered) {
-        if ((rc = c->d_perm.ensure((size_t)npairs * 8)) || (rc = c->d_bucket_cnt.ensure(2 * ordered_segments * pck::kBucketSlots * 4 + 256))) return rc;
-        // (the counts and cursors of every ordered group of the call, zeroed by one fill: each group has its own rows)
-        HIP_TRY(hipMemsetAsync(c->d_bucket_cnt.p, 0, 2 * ordered_segments * pck::kBucketSlots * 4, stream));
-    }
-    if (any_floored) HIP_TRY(hipMemsetAsync((char *)c->d_err.p + kFloorCounterAt, 0, 8, stream));    // this call's counter
-    if (any_two) {                       // (an ordered group is a two-pass group)
-        const size_t n = (size_t)npairs;
-        if ((rc = c->d_k1.ensure(k1_ints * 4 + 256)) || (rc = c->d_woff2.ensure(n * 8)) || (rc = c->d_wlen2.ensure(n * 4)) ||
-            (rc = c->d_col0.ensure(n * 4)) || (rc = c->d_ntot.ensure(n * 4)) || (rc = c->d_frow.ensure(n * 4)) ||
-            (rc = c->d_fscore.ensure(n * 4)) || (rc = c->d_tcols.ensure(n * 4)))
-            return rc;
-    }
-
-    // Launch order: the single-pass groups in table order (side by side on two streams, see pc_ctx), then the two-pass groups
-    std::vector<size_t> order;
-    for (size_t gi = 0; gi < c->groups.size(); ++gi) if (!c->groups[gi].two_pass) order.push_back(gi);
-    for (size_t gi = 0; gi < c->groups.size(); ++gi) if (c->groups[gi].two_pass) order.push_back(gi);
-    bool ctx_stream_used = false;
-    int n_forked = 0;
-    for (const size_t gi_ : order) {
-        const Group &g = c->groups[gi_];
-        pck::ScanArgs a;
-        memset(&a, 0, sizeof(a));
-        a.arena = (const uint8_t *)d_arena;
-        a.ad_codes = c->d_ad_codes.as<uint32_t>();
-        a.ad_len = c->d_ad_len.as<int32_t>();
-        a.tiles = c->d_tiles_slot[c->slot].as<pck::Tile>() + g.tile_begin;
-        a.ntiles = (int32_t)g.tile_count;
-        const bool linear = pcb::is_linear(c->gap_open, c->gap_extend);
-        a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open;
-        a.gap_extend = linear ? pcb::kLinearExtend : c->gap_extend;
-        a.init_extend = c->gap_extend; a.linear = linear ? 1 : 0;
-        a.kren = std::max(1, drift_period(c));
-        a.err = c->d_err.as<uint32_t>();
-        const size_t gidx = (size_t)(&g - &c->groups[0]);
-        a.slab = (uint32_t *)((char *)c->d_slab.p + slab_off[gidx]);
-        a.gen_max_rows = g.gen_max_rows;
-        a.fin_scratch = (uint32_t *)((char *)c->d_fin.p + fin_off[gidx]);
-        a.ad_span = c->d_ad_span.as<int32_t>();
-        a.ad_window = c->d_ad_window.as<int32_t>();
-        a.win_by_out = 0;
-        size_t stride;
-        if (!g.two_pass) {
-            a.win_off = d_win_off; a.win_len = d_win_len;
-            a.out = d_out;
-            a.slab_cols = max_len;
-            const int grid = grid_for(c, g, g.tile_count, max_len, &stride);
-            a.slab_stride = (int64_t)stride;
-            const int64_t np = group_pairs(g, 0, g.tile_count);
-            if (fork) {
-                // every other group on the context's own stream
-                hipStream_t ps = (n_forked++ & 1) ? c->stream : stream;
-                if (ps == c->stream && !ctx_stream_used) { HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0)); ctx_stream_used = true; }
-                if ((rc = launch_traced(c, a, g, grid, ps))) return PC_ERR_NO_DEVICE;
-            } else {
-                ScopedTimer tm(c, stream, 2, np);
-                if ((rc = launch_traced(c, a, g, grid, stream))) return PC_ERR_NO_DEVICE;
-            }
-        } else {
-            const int64_t np = group_pairs(g, 0, g.tile_count);
-            // pass 1: score only, whole window
-            a.win_off = d_win_off; a.win_len = d_win_len;
-            a.out = c->d_k1.as<int32_t>();
-            a.slab = nullptr; a.slab_cols = 0; a.slab_stride = 0;
-            a.ad_span = c->d_ad_span.as<int32_t>();
-            const size_t gi = (size_t)(&g - &c->groups[0]);
-            const bool fl = floored(g);
-            // A score-only call over short windows (phase B's pruning pass: ~100 launches of 150-column windows, one per
-            // adapter pair) cannot cut its tails into column chunks, and every launch would end with a round of tiles that
-            // fills a fraction of the chip (15 625 tiles on 3072 resident waves: 15 % of the launch).  Its launches
-            // alternate between the caller's stream and the context's: the next kernel's first tiles fill the CUs the
-            // previous one's last round leaves idle.  Timed as ONE region.
-            const bool sfork = mode == PC_MODE_SCORE && !fork && stream != c->stream && score_plan[gi].size() >= 2 &&
-                               !ragged_lengths(c, max_len) && max_len / 2 < std::max(128, g.max_window / 2) && !getenv("PC_NO_SCORE_FORK");
-            const size_t fin_alt = fin_region[gi];
-            pc_ctx::Timed region;
-            bool region_timed = false;
-            size_t launch_in_group = 0;
-            if (sfork) {
-                bool any_spec = false;
-                for (const ScoreLaunch &L : score_plan[gi]) any_spec |= L.spec != nullptr;
-                if (c->timing && hipEventCreate(&region.e0) == hipSuccess && hipEventCreate(&region.e1) == hipSuccess) {
-                    region.kind = any_spec ? 3 : 0; region.pairs = np; region_timed = true;
-                    (void)hipEventRecord(region.e0, stream);
-                }
-                HIP_TRY(hipEventRecord(c->ev_fork, stream));
-                HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_fork, 0));
-            }
-            for (const ScoreLaunch &L : score_plan[gi]) {
-                const int chunk_len = (max_len + L.chunks - 1) / L.chunks;
-                int grid = grid_for(c, g, L.count * (size_t)L.chunks, 1, nullptr);
-                const bool alt = sfork && (launch_in_group++ & 1);
-                hipStream_t stream_k = alt ? c->stream : stream;
-                uint32_t *fin_k = (uint32_t *)((char *)a.fin_scratch + (alt ? fin_alt : 0));
-                // windows of very different lengths: exactly the resident workgroups, every further unit drawn from
-                // the counter in launch order -- longest first.  (With a larger grid the first workgroups would stay
-                // resident drawing the short units while the long ones waited for a slot until the very end.)
-                if (ragged_lengths(c, max_len))
-                    grid = (int)std::min<size_t>((size_t)grid, L.spec ? (size_t)c->ncu * (size_t)L.spec->blocks_per_cu
-                                                                      : (size_t)resident_waves(c, g));
-                const int64_t sub_pairs = group_pairs(g, L.begin, L.begin + L.count);
-                ScopedTimer tm(sfork ? nullptr : c, stream, L.spec ? 3 : 0, sub_pairs);       // one timed region per kernel launch
-                // windows cut into very many chunks (a batch with an ultra-long tail): only the chunks that hold columns are units
-                const int32_t *unit_prefix = nullptr;
-                if (L.chunks > kMaxChunks) {
-                    int32_t *real = c->d_units.as<int32_t>() + unit_at, *prefix = real + (L.count + 1);
-                    unit_at += 2 * (L.count + 1);
-                    if (pck::launch_unit_prefix(a.tiles + L.begin, (int)L.count, a.win_len, chunk_len, real, prefix, stream_k)) return PC_ERR_NO_DEVICE;
-                    unit_prefix = prefix;
-                }
-                if (L.spec) {
-                    pcj::SpecArgs sa;
-                    memset(&sa, 0, sizeof(sa));
-                    sa.arena = a.arena; sa.win_off = a.win_off; sa.win_len = a.win_len;
-                    sa.tiles = a.tiles + L.begin; sa.ntiles = (int32_t)L.count;
-                    sa.out = c->d_k1.as<int32_t>() + L.k1_ints; sa.fin_scratch = fin_k;
-                    sa.gap_open = c->gap_open; sa.gap_extend = c->gap_extend;
-                    sa.chunks = L.chunks; sa.chunk_len = chunk_len;
-                    sa.span = std::max(c->ad_span[L.adapter_lo], c->ad_span[L.adapter_hi]);
-                    sa.err = a.err;
-                    sa.work_counter = c->d_work.as<uint32_t>() + score_launch_no++;
-                    // a score-only request over whole windows: the kernel writes the records itself (no planner launch)
-                    sa.rec_out = ((mode == PC_MODE_SCORE || fl) && L.chunks == 1) ? d_out : nullptr;
-                    sa.unit_prefix = unit_prefix;
-                    if (pcj::launch(L.spec, sa, grid, stream_k)) return PC_ERR_NO_DEVICE;
-                } else {
-                    pck::ScanArgs b = a;
-                    b.tiles = a.tiles + L.begin; b.ntiles = (int32_t)L.count;
-                    b.out = c->d_k1.as<int32_t>() + L.k1_ints;
-                    b.chunks = L.chunks; b.chunk_len = chunk_len;
-                    b.fin_scratch = fin_k;
-                    b.work_counter = c->d_work.as<uint32_t>() + score_launch_no++;
-                    b.unit_prefix = unit_prefix;
-                    if ((rc = pck::launch_score(b, g.rows, g.pad, grid, stream_k))) return PC_ERR_NO_DEVICE;
-                }
-            }
-            if (sfork) {
-                HIP_TRY(hipEventRecord(c->ev_join, c->stream));
-                HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
-                if (region_timed) { (void)hipEventRecord(region.e1, stream); c->timed.push_back(region); }
-            }
-            // plan the bounded windows, per launch (the [pair][chunk] layout is the launch's)
-            pck::PlanArgs pl;
-            memset(&pl, 0, sizeof(pl));
-            pl.win_off = d_win_off; pl.win_len = d_win_len;
-            pl.win_off2 = c->d_woff2.as<int64_t>(); pl.win_len2 = c->d_wlen2.as<int32_t>();
-            pl.col02 = c->d_col0.as<int32_t>(); pl.ntot2 = c->d_ntot.as<int32_t>();
-            pl.force_row2 = c->d_frow.as<int32_t>(); pl.force_score2 = c->d_fscore.as<int32_t>();
-            {   // the pair's own bound on the traced columns (schemes of the packed kernels: match > 0, both gap scores < 0)
-                static const bool off = [] { const char *e = getenv("PC_NO_PAIR_TRACE_BOUND"); return e && *e && *e != '0'; }();
-                pl.match = c->match; pl.gap_unit = std::min(-c->gap_open, -(linear ? c->gap_open : c->gap_extend));
-                pl.trace_cols2 = (!off && pl.match > 0 && pl.gap_unit > 0) ? c->d_tcols.as<int32_t>() : nullptr;
-            }
-            a.chunks = 1;
-            pl.ad_window = c->d_ad_window.as<int32_t>();
-            pl.score_out = (mode == PC_MODE_SCORE || fl) ? d_out : nullptr;
-            {   // end-aligned windows only for the packed-fp16 traced kernel (it is the one that knows lead-ins)
-                pcb::F16Plan fp_;
-                pl.end_align = trace16_plan(c, g.rows, g.max_window + 1, &fp_) ? 1 : 0;
-            }
-            pl.err = a.err;
-            {
-                ScopedTimer tm(c, stream, 1, np);
-                for (const ScoreLaunch &L : score_plan[gi]) {
-                    if ((mode == PC_MODE_SCORE || fl) && L.chunks == 1 && L.spec) continue;      // records written by the kernel itself
-                    pl.k1 = c->d_k1.as<int32_t>() + L.k1_ints;
-                    pl.tiles = a.tiles + L.begin; pl.ntiles = (int32_t)L.count; pl.chunks = L.chunks;
-                    pl.chunk_len = (max_len + L.chunks - 1) / L.chunks;
-                    if ((rc = pck::launch_plan(pl, stream))) return PC_ERR_NO_DEVICE;
-                }
-                if (mode == PC_MODE_TRACE_AT || fl) {   // the score records (the caller's / pass 1's), read before pass 2 overwrites them
-                    pl.k1 = nullptr; pl.end_records = d_out; pl.score_out = nullptr;
-                    if (mode == PC_MODE_TRACE_AT) pl.window_cap = std::max(1, max_len);
-                    pl.tiles = a.tiles; pl.ntiles = (int32_t)g.tile_count; pl.chunks = 1;
-                    if (fl || ordered_trace_at(g)) {
-                        pck::BucketArgs b;
-                        memset(&b, 0, sizeof b);
-                        b.records = d_out;
-                        if (fl) {
-                            b.mark = d_out;
-                            for (size_t s = 0; s < g.nseg; ++s) b.seg_floor[s] = seg_floor_of(g, s);
-                            b.skipped = (unsigned long long *)((char *)c->d_err.p + kFloorCounterAt);
-                            pl.floor_out = d_out;
-                            a.skip_marked = 1;
-                        }
-                        b.seg_first = (const int64_t *)c->d_bucket_slot[c->slot].p + g.seg_begin; b.nsegments = (int32_t)g.nseg;
-                        b.blocks = (const pck::BucketBlock *)((const char *)c->d_bucket_slot[c->slot].p + c->bucket_blocks_at) + g.blk_begin;
-                        b.nblocks = (int32_t)g.nblk;
-                        b.counts = c->d_bucket_cnt.as<uint32_t>() + g.seg_begin * pck::kBucketSlots;
-                        b.cursors = c->d_bucket_cnt.as<uint32_t>() + (ordered_segments + g.seg_begin) * pck::kBucketSlots;
-                        b.perm = c->d_perm.as<int64_t>();
-                        if (pck::launch_bucket_pairs(b, stream)) return PC_ERR_NO_DEVICE;
-                        pl.perm = b.perm; a.perm = b.perm;
-                    }
-                    if ((rc = pck::launch_plan(pl, stream))) return PC_ERR_NO_DEVICE;
-                }
-            }
-            if (mode == PC_MODE_SCORE) continue;      // no traceback asked for
-            // pass 2: traced window ending at the max cell
-            a.win_off = pl.win_off2; a.win_len = pl.win_len2; a.col0 = pl.col02; a.n_total = pl.ntot2;
-            a.win_by_out = 1;
-            a.force_row = pl.force_row2; a.force_score = pl.force_score2; a.trace_cols = pl.trace_cols2;
-            a.out = d_out;
-            a.slab = (uint32_t *)((char *)c->d_slab.p + slab_off[gidx]);
-            a.slab_cols = g.max_window + 1;
-            const int grid = grid_for(c, g, g.tile_count, a.slab_cols, &stride);
-            a.slab_stride = (int64_t)stride;
-            {
-                ScopedTimer tm(c, stream, 2, np);
-                if ((rc = launch_traced(c, a, g, grid, stream))) return PC_ERR_NO_DEVICE;
-            }
-        }
-    }
-    if (fork) {
-        if (ctx_stream_used) {
-            HIP_TRY(hipEventRecord(c->ev_join, c->stream));
-            HIP_TRY(hipStreamWaitEvent(stream, c->ev_join, 0));
-        }
-        if (fork_timed) { (void)hipEventRecord(fork_timer.e1, stream); c->timed.push_back(fork_timer); }
-    }
-    // ---- jobs outside the packed kernels' range: plain int32, one lane per pair (pc_slow.hip) -----------------------
-    for (const pc_ctx::SlowJob &J : c->slow_jobs) {
-        const int m = c->ad_len[J.adapter];
-        if (!pcs::fits(max_len, m, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
-            fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
-                    c->match, c->mismatch, c->gap_open, c->gap_extend, max_len, m);
-            return PC_ERR_UNSUPPORTED_SCORES;
-        }
-        static const size_t budget = [] { const char *e = getenv("PC_SLOW_SCRATCH_MB"); return (size_t)(e && atol(e) > 0 ? atol(e) : 2048) << 20; }();
-        const bool lds = m <= 128;
-        const size_t per_pair = (size_t)std::max(1, max_len) * (size_t)m + (lds ? 0 : (size_t)m * 8);
-        int64_t P = (int64_t)(budget / per_pair) / 64 * 64;
-        if (P < 64) P = 64;
-        if ((size_t)P * per_pair > ((size_t)16 << 30)) {
-            fprintf(stderr, "porechop_amd: a window of %d bases against an adapter of %d needs %zu bytes of trace per pair: too large for the plain-int32 path\n",
-                    max_len, m, per_pair);
-            return PC_ERR_ADAPTER_TOO_LONG;
-        }
-        P = std::min<int64_t>(P, (J.n + 63) / 64 * 64);
-        if ((rc = c->d_slow_trace.ensure((size_t)P * (size_t)std::max(1, max_len) * (size_t)m + 256))) return rc;
-        if (!lds && (rc = c->d_slow_state.ensure((size_t)P * (size_t)m * 8 + 256))) return rc;
-        pck::SlowArgs sa;
-        memset(&sa, 0, sizeof sa);
-        sa.arena = (const uint8_t *)d_arena; sa.win_off = d_win_off; sa.win_len = d_win_len;
-        sa.adapter = c->d_slow_ad.as<uint8_t>() + c->slow_ad_off[J.adapter];
-        sa.m = m; sa.max_len = max_len;
-        sa.match = c->match; sa.mismatch = c->mismatch; sa.gap_open = c->gap_open; sa.gap_extend = c->gap_extend;
-        sa.out = d_out; sa.state = lds ? nullptr : c->d_slow_state.as<int32_t>(); sa.trace = c->d_slow_trace.as<uint8_t>();
-        sa.P = P; sa.err = c->d_err.as<uint32_t>();
-        ScopedTimer tm(c, stream, 2, J.n);
-        for (int64_t first = 0; first < J.n; first += P) {
-            sa.first_window = J.win_start + first; sa.count = std::min<int64_t>(P, J.n - first); sa.out_base = J.out_base + first;
-            if (pck::launch_slow(sa, stream)) return PC_ERR_NO_DEVICE;
-        }
-    }
-    HIP_TRY(hipEventRecord(c->slot_free[c->slot], stream));      // the last launch that reads this table slot
-    return PC_OK;
-}
 
 int pc_debug_value_range(pc_ctx *c, int32_t *lo, int32_t *hi)
 {
@@ -1321,9 +954,7 @@ int pc_align_paths(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
     const int groups = pcpath::row_groups(rows);
     const size_t per_pair = (size_t)std::max(1, max_len) * (size_t)groups * 4;
-    int64_t P = (int64_t)(budget / per_pair) / 64 * 64;
-    if (P < 64) P = 64;                                             // never fewer than a wave, whatever that makes the scratch
-    P = std::min<int64_t>(P, (n + 63) / 64 * 64);
+    const int64_t P = pcn::slice_pairs(budget, per_pair, n);
     if ((rc = c->d_paths_trace.ensure((size_t)P * per_pair + 256))) return rc;
     pck::PathArgs a;
     memset(&a, 0, sizeof a);
@@ -1349,9 +980,8 @@ int pc_path_cigar(const uint32_t *ops, int path_len, char *buf, size_t buflen)
 int pc_trace_ops_x100(pc_ctx *c)
 {
     if (!c) return 2100;
-    pcb::F16Plan fp;
     // the end-window shape: the ligation adapters' row class, 150 columns
-    return trace16_plan(c, 28, 150, &fp) ? 1325 : 2100;
+    return pcn::trace16_plan(plan_params(c), 28, 150) ? 1325 : 2100;
 }
 
 int pc_phase_b_reduce(pc_ctx *c, const int32_t *d_records, int64_t n, int njobs, const int64_t *job_record_offset,

@@ -30,6 +30,32 @@ struct TileRun {
 };
 int launch_expand_tiles(const TileRun *d_runs, int nruns, Tile *d_tiles, int64_t ntiles, void *stream);
 
+#if defined(__HIPCC__)
+#define PCK_HD __host__ __device__
+#else
+#define PCK_HD
+#endif
+// tile k of a run: what expand_tiles_kernel writes, and what the host's tests expand plans with
+PCK_HD inline Tile expand_tile(const TileRun &r, int64_t k)
+{
+    Tile o;
+    if (r.dual) {
+        const int64_t s = 64 * k;
+        o.win_lo = r.win0 + s; o.win_hi = r.win0 + s;
+        o.out_lo = r.out0 + s; o.out_hi = r.out0 + r.n + s;
+        const int64_t c = r.n - s < 64 ? r.n - s : 64;
+        o.count_lo = o.count_hi = (int32_t)(c > 0 ? c : 0);
+    } else {
+        const int64_t s = 128 * k;
+        o.win_lo = r.win0 + s; o.win_hi = r.win0 + s + 64;
+        o.out_lo = r.out0 + s; o.out_hi = r.out0 + s + 64;
+        const int64_t cl = r.n - s < 64 ? r.n - s : 64, ch = r.n - s - 64 < 64 ? r.n - s - 64 : 64;
+        o.count_lo = (int32_t)(cl > 0 ? cl : 0); o.count_hi = (int32_t)(ch > 0 ? ch : 0);
+    }
+    o.adapter_lo = r.adapter_lo; o.adapter_hi = r.adapter_hi; o.rows = r.rows; o.pad_ = 0;
+    return o;
+}
+
 struct ScanArgs {
     const uint8_t *arena;        // read bytes, 1 B/base, as delivered by the caller
     const int64_t *win_off;      // [nwindows] byte offset of the window's first column
@@ -281,11 +307,16 @@ inline int pick_rows(int m_lo, int m_hi, bool *pad)
     *pad = true;
     return 0;
 }
+inline bool trace16_has(int rows)
+{
+    for (int r : kTrace16Rows) if (r == rows) return true;
+    return false;
+}
+inline int trace_words_per_col(int rows) { return (rows + 3) / 4; }   // NW: dwords of trace per column and lane
 
 // launchers (pc_kernels.hip); stream is a hipStream_t passed as void*
 int launch_trace(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
 int launch_score(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
-bool trace16_has(int rows);
 int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream);   // packed-fp16 traced scan (needs a.f16_*)
 
 // The pairs of every segment (a run of output slots that share one adapter) in the order of their end columns, coarsely:
@@ -322,7 +353,6 @@ int launch_group_survivors(const int32_t *mask, int64_t n, int words, const int3
 int launch_round_consume(const double *full_all, const int32_t *rec_all, const int64_t *cur, const int64_t *act, int64_t nact, int A, int64_t Dn,
                          double threshold, uint8_t *anyh, int32_t *a_hit, int64_t *cnt, int64_t *stats, void *stream);
 int launch_plan(const PlanArgs &a, void *stream);
-int trace_words_per_col(int rows);   // NW
 
 // the k-mer census of adapter discovery (pc_discover.hip): counts[code] += 1 for every k-mer of every window that holds
 // bases only (4 <= k <= 13, checked by the caller); the qualifying entries of such a table as a capped list

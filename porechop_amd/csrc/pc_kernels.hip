@@ -1300,8 +1300,6 @@ int launch_unit_prefix(const Tile *tiles, int ntiles, const int32_t *win_len, in
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int trace_words_per_col(int rows) { return (rows + 3) / 4; }
-
 template <bool TRACE>
 static int launch_scan(const ScanArgs &a0, int rows, bool pad, int grid, void *stream)
 {
@@ -1336,12 +1334,6 @@ static int launch_scan(const ScanArgs &a0, int rows, bool pad, int grid, void *s
 }
 
 int launch_trace(const ScanArgs &a, int rows, bool pad, int grid, void *stream) { return launch_scan<true>(a, rows, pad, grid, stream); }
-
-bool trace16_has(int rows)
-{
-    for (int r : kTrace16Rows) if (r == rows) return true;
-    return false;
-}
 
 int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream)
 {

@@ -117,23 +117,7 @@ __global__ __launch_bounds__(256) void expand_tiles_kernel(const TileRun *runs, 
         if (runs[mid].tile0 <= t) lo = mid; else hi = mid - 1;
     }
     const TileRun r = runs[lo];
-    const int64_t k = t - r.tile0;
-    Tile o;
-    if (r.dual) {
-        const int64_t s = 64 * k;
-        o.win_lo = r.win0 + s; o.win_hi = r.win0 + s;
-        o.out_lo = r.out0 + s; o.out_hi = r.out0 + r.n + s;
-        const int64_t c = r.n - s < 64 ? r.n - s : 64;
-        o.count_lo = o.count_hi = (int32_t)(c > 0 ? c : 0);
-    } else {
-        const int64_t s = 128 * k;
-        o.win_lo = r.win0 + s; o.win_hi = r.win0 + s + 64;
-        o.out_lo = r.out0 + s; o.out_hi = r.out0 + s + 64;
-        const int64_t cl = r.n - s < 64 ? r.n - s : 64, ch = r.n - s - 64 < 64 ? r.n - s - 64 : 64;
-        o.count_lo = (int32_t)(cl > 0 ? cl : 0); o.count_hi = (int32_t)(ch > 0 ? ch : 0);
-    }
-    o.adapter_lo = r.adapter_lo; o.adapter_hi = r.adapter_hi; o.rows = r.rows; o.pad_ = 0;
-    tiles[t] = o;
+    tiles[t] = expand_tile(r, t - r.tile0);
 }
 
 int launch_expand_tiles(const TileRun *d_runs, int nruns, Tile *d_tiles, int64_t ntiles, void *stream)
