@@ -149,7 +149,29 @@ int pc_scan_device_floored(pc_ctx *ctx, const void *d_arena, const int64_t *d_wi
                            int mode, int32_t *d_out, void *stream, const int32_t *job_floor,
                            const int32_t *job_floor_b);
 
-/* Pairs pc_scan_device_floored left untraced: in the last floored call of this context, and in all of them.  Waits for `stream`.  Either pointer may be NULL. */
+/* pc_scan_device over END WINDOWS with the trimming rule of their caller: phase B keeps, per read and side, the largest trim
+ * among the alignments that qualify (identity above end_threshold, not flush with the window's inner edge, at least
+ * min_trim_size columns), so a pair that cannot qualify need not be traced.  job_side (host, njobs entries) says what a
+ * job's windows are: 0 = start windows (seq[:end_size]), 1 = end windows (seq[-end_size:]), negative = the rule does not
+ * apply to the job.  The library scans every window score-only first (this call, and only this call, takes windows shorter
+ * than 2 * window + 64 columns in two passes under PC_MODE_AUTO; PC_MODE_TWO_PASS is accepted too, any other mode is
+ * PC_ERR_BAD_ARG), decides between the passes from each pair's score record and window length (csrc/pc_end_rule.h: one
+ * round, nothing about other pairs' trims or barcode calls), answers the pairs that cannot trim with the "no alignment"
+ * record (field 0 = -1, the others 0) and traces the rest as PC_MODE_TRACE_AT does, taken by end column.  Every traced pair
+ * gets exactly the record pc_scan_device writes.  No host round trip.  rule == NULL and job_side == NULL is pc_scan_device
+ * itself; PC_NO_END_FLOOR=1 in the environment makes every call so.  The rule is ignored -- every pair traced -- for jobs
+ * on the plain-int32 kernel and for a launch group of more than 16 (job, adapter) segments. */
+typedef struct pc_end_rule {
+    int32_t end_size, min_trim_size, extra_end_trim;
+    double end_threshold;                /* percent, as --end_threshold */
+} pc_end_rule;
+int pc_scan_device_end_rule(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off,
+                            const int32_t *d_win_len, int64_t nwindows, const int32_t *job_adapter,
+                            const int32_t *job_adapter_b, const int64_t *job_start, int njobs, int max_len,
+                            int mode, int32_t *d_out, void *stream, const pc_end_rule *rule,
+                            const int32_t *job_side);
+
+/* Pairs pc_scan_device_floored or pc_scan_device_end_rule left untraced: in the last such call of this context, and in all of them.  Waits for `stream`.  Either pointer may be NULL. */
 int pc_floor_skipped(pc_ctx *ctx, void *stream, int64_t *last_call, int64_t *total);
 
 /* Alignment PATHS: pair p aligns window [d_win_off[p], + d_win_len[p]) of the arena with adapter d_adapter_idx[p] of the

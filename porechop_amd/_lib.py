@@ -24,13 +24,19 @@ EXPORTS = [
     "pc_gzstream_open", "pc_gzstream_next", "pc_gzstream_close", "pc_gz_member_start", "pc_gzstream_open_range", "pc_prefilter_packed", "pc_prefilter_packed_any", "pc_unpack_windows", "pc_prefilter_defer_count", "pc_prefilter_overflowed", "pc_trim_windows", "pc_middle_hits", "pc_group_survivors", "pc_round_consume",
     "pc_gz_sized_size", "pc_gz_sized_find_record", "pc_readset_load_gz_range",
     "pc_kmer_count", "pc_kmer_select",
-    "pc_scan_device_floored", "pc_floor_skipped",
+    "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule",
     "pc_align_paths", "pc_path_cigar",
 ]
 
 
 class LibraryMissing(RuntimeError):
     pass
+
+
+class EndRule(ctypes.Structure):
+    """pc_end_rule: what phase B asks of an end-window alignment before it trims (pc_scan_device_end_rule)."""
+    _fields_ = [("end_size", ctypes.c_int32), ("min_trim_size", ctypes.c_int32), ("extra_end_trim", ctypes.c_int32),
+                ("end_threshold", ctypes.c_double)]
 
 
 _lib = None
@@ -79,6 +85,8 @@ def load_library():
     L.pc_scan_device.restype = c_int
     L.pc_scan_device_floored.argtypes = L.pc_scan_device.argtypes + [c_vp, c_vp]
     L.pc_scan_device_floored.restype = c_int
+    L.pc_scan_device_end_rule.argtypes = L.pc_scan_device.argtypes + [ctypes.POINTER(EndRule), c_vp]
+    L.pc_scan_device_end_rule.restype = c_int
     L.pc_floor_skipped.argtypes = [c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     L.pc_floor_skipped.restype = c_int
     L.pc_align_paths.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp]

@@ -137,6 +137,7 @@ class Aligner:
     score_end_cell = True      # MODE_SCORE records carry the reference's end cell (row, column) besides the score
     reduce_takes_mask = True   # phase_b_reduce(traced_mask=...): pairs whose bit is clear are skipped without a load
     trace_at = True            # MODE_TRACE_AT: the traced record of a pair whose MODE_SCORE record (its end cell) is known
+    end_rule = True            # scan_device(end_rule=..., job_side=...): end windows traced only where phase B's rule can trim
     paths = True               # align_paths / align_pairs_paths: records with the alignment's path (pc_align_paths)
 
     def __init__(self, adapters, scores=DEFAULT_SCORES, device=-1):
@@ -194,13 +195,16 @@ class Aligner:
 
     # ---- device buffers (torch tensors on the GPU) --------------------------------------
     def scan_device(self, arena, win_off, win_len, job_adapter, job_start, max_len, out,
-                    mode=MODE_AUTO, stream=None, job_adapter_b=None, floors=None, floors_b=None):
+                    mode=MODE_AUTO, stream=None, job_adapter_b=None, floors=None, floors_b=None, end_rule=None, job_side=None):
         """arena uint8[*], win_off int64[n], win_len int32[n]: CUDA(HIP) tensors describing n windows.
         job_adapter int32[k], job_start int64[k+1] (window ranges), optional job_adapter_b int32[k]
         (-1 = none): host numpy.  out int32[total,8] with total = sum n_k * (1 or 2), job order,
         adapter A's records before adapter B's.  Asynchronous; call sync().
         floors / floors_b int32[k] (MODE_TWO_PASS only; NO_FLOOR = none): a pair whose best score is below its job's floor is
-        not traced and gets the record (-1, 0, ..., 0) (pc_scan_device_floored); every other record is unchanged."""
+        not traced and gets the record (-1, 0, ..., 0) (pc_scan_device_floored); every other record is unchanged.
+        end_rule = (end_size, min_trim_size, extra_end_trim, end_threshold) with job_side int32[k] (0 = start windows, 1 = end
+        windows; MODE_AUTO or MODE_TWO_PASS): a pair that cannot trim its read by phase B's rule is not traced and gets that
+        same record (pc_scan_device_end_rule); every other record is unchanged."""
         import torch
         assert arena.is_cuda and win_off.is_cuda and win_len.is_cuda and out.is_cuda
         assert win_off.dtype == torch.int64 and win_len.dtype == torch.int32 and out.dtype == torch.int32
@@ -211,6 +215,19 @@ class Aligner:
             jb = np.ascontiguousarray(job_adapter_b, dtype=np.int32)
         n = win_off.shape[0]
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if end_rule is not None:
+            assert floors is None and floors_b is None and job_side is not None
+            from ._lib import EndRule
+            rule = EndRule(int(end_rule[0]), int(end_rule[1]), int(end_rule[2]), float(end_rule[3]))
+            side = np.ascontiguousarray(job_side, dtype=np.int32)
+            assert side.shape[0] == len(job_adapter)
+            check(self.lib.pc_scan_device_end_rule(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
+                                                   job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None,
+                                                   job_start.ctypes.data, len(job_adapter),
+                                                   int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s),
+                                                   ctypes.byref(rule), side.ctypes.data),
+                  "pc_scan_device_end_rule")
+            return
         if floors is not None or floors_b is not None:
             fa = np.ascontiguousarray(floors if floors is not None else np.full(len(job_adapter), NO_FLOOR), dtype=np.int32)
             fb = None if jb is None else np.ascontiguousarray(floors_b if floors_b is not None else np.full(len(job_adapter), NO_FLOOR),

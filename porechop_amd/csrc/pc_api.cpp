@@ -130,6 +130,7 @@ struct pc_ctx {
     std::vector<int32_t> last_job_adapter, last_job_adapter_b;
     std::vector<int64_t> last_job_start;
     int last_max_len = -1, last_mode = -1;
+    bool last_end_rule = false;
     bool tiles_uploaded = false;
     std::mutex mu;
     // optional per-launch HIP-event timing (pc_set_timing / pc_get_timing)
@@ -232,8 +233,8 @@ int upload_panel(pc_ctx *c)
     return PC_OK;
 }
 
-// The scan's environment switches, all read here, once per process -- except PC_FORCE_CHUNKS and PC_NO_SCORE_FORK, which
-// are read for every call (tests change them between calls).
+// The scan's environment switches, all read here, once per process -- except PC_FORCE_CHUNKS, PC_NO_SCORE_FORK and
+// PC_NO_END_FLOOR, which are read for every call (tests change them between calls).
 pcn::Options scan_options()
 {
     static const pcn::Options once = [] {
@@ -250,6 +251,7 @@ pcn::Options scan_options()
     pcn::Options o = once;
     if (const char *f = getenv("PC_FORCE_CHUNKS")) o.force_chunks = atoi(f);
     o.no_score_fork = getenv("PC_NO_SCORE_FORK") != nullptr;
+    if (const char *e = getenv("PC_NO_END_FLOOR")) o.no_end_floor = *e && *e != '0';
     return o;
 }
 
@@ -269,7 +271,7 @@ int build_tiles(pc_ctx *c, const pcn::Params &p, const int32_t *job_adapter, con
 {
     std::vector<int32_t> jb(njobs, -1);
     if (job_adapter_b) jb.assign(job_adapter_b, job_adapter_b + njobs);
-    const bool same = c->tiles_uploaded && c->last_max_len == max_len && c->last_mode == mode &&
+    const bool same = c->tiles_uploaded && c->last_max_len == max_len && c->last_mode == mode && c->last_end_rule == p.end_rule &&
                       (int)c->last_job_adapter.size() == njobs &&
                       std::equal(job_adapter, job_adapter + njobs, c->last_job_adapter.begin()) &&
                       jb == c->last_job_adapter_b &&
@@ -324,7 +326,7 @@ int build_tiles(pc_ctx *c, const pcn::Params &p, const int32_t *job_adapter, con
     c->last_job_adapter.assign(job_adapter, job_adapter + njobs);
     c->last_job_adapter_b = jb;
     c->last_job_start.assign(job_start, job_start + njobs + 1);
-    c->last_max_len = max_len; c->last_mode = mode;
+    c->last_max_len = max_len; c->last_mode = mode; c->last_end_rule = p.end_rule;
     c->tiles_uploaded = true;
     return PC_OK;
 }
@@ -374,6 +376,7 @@ struct ScanCall {
     int32_t *out;
     hipStream_t stream;
     pcn::Floors floors;
+    pcr::EndRule rule;                   // of a call with an end rule (floors.rule_side says for which jobs)
     int64_t npairs;
     bool linear;
     // the plan (plan_scan)
@@ -465,7 +468,7 @@ int zero_counters(pc_ctx *c, const ScanCall &s)
 {
     if (s.n_score_launches) HIP_TRY(hipMemsetAsync(c->d_work.p, 0, s.n_score_launches * 4, s.stream));
     if (s.ordered_segments) HIP_TRY(hipMemsetAsync(c->d_bucket_cnt.p, 0, 2 * s.ordered_segments * pck::kBucketSlots * 4, s.stream));
-    if (s.any_floored) HIP_TRY(hipMemsetAsync((char *)c->d_err.p + kFloorCounterAt, 0, 8, s.stream));
+    if (s.any_floored || s.p.end_rule) HIP_TRY(hipMemsetAsync((char *)c->d_err.p + kFloorCounterAt, 0, 8, s.stream));
     return PC_OK;
 }
 
@@ -619,6 +622,9 @@ int plan_windows(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, bool
     // end-aligned windows only for the packed-fp16 traced kernel (it is the one that knows lead-ins)
     pl.end_align = pcn::trace16_plan(s.p, g.rows, g.max_window + 1) ? 1 : 0;
     pl.err = a.err;
+    // (PC_MODE_TRACE_AT, a call with an end rule: no traced window longer than the windows themselves -- the table's max_window is capped alike)
+    if (s.mode == PC_MODE_TRACE_AT || s.p.end_rule) pl.window_cap = std::max(1, s.max_len);
+    const bool rl = fl && pcn::ruled(s.p, g, s.mode, s.floors);
     ScopedTimer tm(c, s.stream, 1, pcn::group_pairs(g));
     for (const pcn::ScoreLaunch &L : s.score_plan[gi]) {
         if (records && L.chunks == 1 && L.spec) continue;      // records written by the kernel itself
@@ -629,7 +635,6 @@ int plan_windows(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, bool
     }
     if (s.mode == PC_MODE_TRACE_AT || fl) {   // the score records (the caller's / pass 1's), read before pass 2 overwrites them
         pl.k1 = nullptr; pl.end_records = s.out; pl.score_out = nullptr;
-        if (s.mode == PC_MODE_TRACE_AT) pl.window_cap = std::max(1, s.max_len);
         pl.tiles = a.tiles; pl.ntiles = (int32_t)g.tile_count; pl.chunks = 1;
         if (fl || pcn::ordered_trace_at(s.p, g, s.mode)) {
             pck::BucketArgs b;
@@ -637,7 +642,12 @@ int plan_windows(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, bool
             b.records = s.out;
             if (fl) {
                 b.mark = s.out;
-                for (size_t sg = 0; sg < g.nseg; ++sg) b.seg_floor[sg] = pcn::seg_floor_of(g, sg, s.floors);
+                for (size_t sg = 0; sg < g.nseg; ++sg) b.seg_floor[sg] = rl ? INT32_MIN : pcn::seg_floor_of(g, sg, s.floors);
+                if (rl) {
+                    b.rule_win_len = s.win_len; b.rule = s.rule;
+                    for (size_t sg = 0; sg < g.nseg; ++sg)
+                        b.seg_rule[sg] = pck::SegRule{g.seg_win[sg], pcn::seg_side_of(g, sg, s.floors), c->ad_len[g.seg_adapter[sg]]};
+                }
                 b.skipped = (unsigned long long *)((char *)c->d_err.p + kFloorCounterAt);
                 pl.floor_out = s.out;
                 a.skip_marked = 1;
@@ -664,7 +674,7 @@ int plan_windows(pc_ctx *c, const ScanCall &s, size_t gi, pck::ScanArgs &a, bool
 int run_two_pass_group(pc_ctx *c, ScanCall &s, size_t gi)
 {
     const pcn::Group &g = c->table.groups[gi];
-    const bool fl = pcn::floored(g, s.mode, s.floors);
+    const bool fl = pcn::floored(g, s.mode, s.floors) || pcn::ruled(s.p, g, s.mode, s.floors);
     pck::ScanArgs a = group_args(c, s, gi);
     int rc;
     if ((rc = score_pass(c, s, gi, a, s.mode == PC_MODE_SCORE || fl))) return rc;
@@ -715,7 +725,7 @@ int run_slow_jobs(pc_ctx *c, const ScanCall &s)
 int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                 int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
                 const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
-                const int32_t *job_floor, const int32_t *job_floor_b)
+                const int32_t *job_floor, const int32_t *job_floor_b, const pc_end_rule *rule = nullptr, const int32_t *job_side = nullptr)
 {
     // 1: the arguments, the panel, the table of the job list
     if (!c || nwindows < 0 || njobs < 0 || max_len < 0) return PC_ERR_BAD_ARG;
@@ -731,6 +741,12 @@ int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const 
     s.floors.a = job_floor; s.floors.b = job_floor_b;
     s.linear = pcb::is_linear(c->gap_open, c->gap_extend);
     s.p = plan_params(c);
+    if (rule && job_side && !s.p.opt.no_end_floor) {
+        s.p.end_rule = true;
+        s.floors.rule_side = job_side;
+        s.rule = pcr::make_end_rule(c->match, c->mismatch, c->gap_open, c->gap_extend, rule->end_size, rule->min_trim_size,
+                                    rule->extra_end_trim, rule->end_threshold);
+    }
     if ((rc = build_tiles(c, s.p, job_adapter, job_adapter_b, job_start, njobs, max_len, mode))) return rc;
     s.npairs = c->table.total;
     if (mode == PC_MODE_SCORE && !c->table.slow_jobs.empty()) {
@@ -896,6 +912,18 @@ int pc_scan_device_floored(pc_ctx *c, const void *d_arena, const int64_t *d_win_
     if (job_floor_b && !job_adapter_b) return PC_ERR_BAD_ARG;
     return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
                        stream_v, job_floor, job_floor_b);
+}
+
+int pc_scan_device_end_rule(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                            int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                            const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                            const pc_end_rule *rule, const int32_t *job_side)
+{
+    if ((rule || job_side) && mode != PC_MODE_AUTO && mode != PC_MODE_TWO_PASS) return PC_ERR_BAD_ARG;   // the rule sits between two passes
+    if ((rule != nullptr) != (job_side != nullptr)) return PC_ERR_BAD_ARG;
+    if (rule && (rule->end_size < 0 || !(rule->end_threshold == rule->end_threshold))) return PC_ERR_BAD_ARG;
+    return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
+                       stream_v, nullptr, nullptr, rule, job_side);
 }
 
 int pc_floor_skipped(pc_ctx *c, void *stream_v, int64_t *last_call, int64_t *total)

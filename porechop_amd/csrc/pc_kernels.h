@@ -2,6 +2,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "pc_end_rule.h"
+
 namespace pck {
 
 // One tile = one wavefront's worth of work: up to 128 (window, adapter) pairs.  Lanes 0..63
@@ -332,6 +334,11 @@ constexpr int kBucketSlots = kBuckets + 1;             // + the bucket of the pa
 constexpr int kFloorSegments = 256;                    // segments a floored group may have (more: the group is traced in full)
 constexpr int kBelowFloor = -3;                        // field 0 of a score record whose pair is below its floor
 constexpr int kSkipRow = -2;                           // force_row of such a pair in pass 2: not there for the traced kernels
+// An end rule in place of the floors (pc_scan_device_end_rule): a pair of an end-window segment goes into that last bucket when
+// pcr::can_trim says that it cannot trim its read.  The test needs the pair's window length: a segment's pairs and windows run
+// in step, so pair p of segment s scans window seg_rule[s].win_first + (p - seg_first[s]).
+constexpr int kRuleSegments = 16;                      // segments a ruled group may have (more: the group is traced in full)
+struct SegRule { int64_t win_first; int32_t side, adapter_len; };   // side 0: start windows, 1: end windows, < 0: no rule
 struct BucketBlock { int64_t first; int32_t count, segment; };
 struct BucketArgs {
     const int32_t *records;
@@ -342,6 +349,9 @@ struct BucketArgs {
     int32_t *mark;                                     // null, or the records again: pairs below seg_floor are marked there
     unsigned long long *skipped;                       // with mark: [2] += the pairs marked (this call's counter, the running one)
     int32_t seg_floor[kFloorSegments];                 // read only when mark is set
+    const int32_t *rule_win_len;                       // with mark: null (the floors decide), or the call's window lengths -- then
+    pcr::EndRule rule;                                 // the end rule decides, segment by segment (nsegments <= kRuleSegments)
+    SegRule seg_rule[kRuleSegments];
 };
 int launch_bucket_pairs(const BucketArgs &a, void *stream);
 

@@ -1366,7 +1366,15 @@ __device__ __forceinline__ int bucket_of(const BucketArgs &a, int64_t pair, int 
 {
     const int2 v = *(const int2 *)(a.records + pair * TRACE_OUT_INTS);      // (flag, J)
     if (v.x != -2 || v.y < 0) return kBuckets - 1;                          // not a score record: among the longest
-    if (a.mark && a.records[pair * TRACE_OUT_INTS + 4] < a.seg_floor[segment]) return kBuckets;   // below its floor: behind all others
+    if (a.mark && a.rule_win_len) {
+        // an end rule: a pair that cannot trim its read goes behind all others (what is not a plain score record never does)
+        const SegRule sr = a.seg_rule[segment];
+        if (sr.side >= 0) {
+            const int2 u = *(const int2 *)(a.records + pair * TRACE_OUT_INTS + 2);   // (I, 0)
+            const int n = a.rule_win_len[sr.win_first + (pair - a.seg_first[segment])];
+            if (!pcr::can_trim(a.rule, sr.side, v.x, a.records[pair * TRACE_OUT_INTS + 4], u.x, v.y, n, sr.adapter_len)) return kBuckets;
+        }
+    } else if (a.mark && a.records[pair * TRACE_OUT_INTS + 4] < a.seg_floor[segment]) return kBuckets;   // below its floor: behind all others
     const int b = v.y / kBucketWidth;
     return b < kBuckets ? b : kBuckets - 1;
 }
@@ -1433,7 +1441,7 @@ __global__ __launch_bounds__(256) void bucket_scatter_kernel(BucketArgs a)
 int launch_bucket_pairs(const BucketArgs &a, void *stream)
 {
     if (a.nblocks <= 0 || a.nsegments <= 0) return 0;
-    if (a.mark && a.nsegments > kFloorSegments) return -1;
+    if (a.mark && a.nsegments > (a.rule_win_len ? kRuleSegments : kFloorSegments)) return -1;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(bucket_count_kernel, dim3((unsigned)a.nblocks), dim3(256), 0, s, a);
     hipLaunchKernelGGL(bucket_prefix_kernel, dim3((unsigned)((a.nsegments + 255) / 256)), dim3(256), 0, s, a);

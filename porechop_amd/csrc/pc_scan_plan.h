@@ -31,6 +31,7 @@ struct Options {
     bool no_pair_trace_bound = false;   // PC_NO_PAIR_TRACE_BOUND: pass 2 traces the adapter-wide W + 2 columns
     bool no_score_fork = false;         // PC_NO_SCORE_FORK (per call): a score-only call's launches on one stream
     int force_chunks = 0;               // PC_FORCE_CHUNKS (per call); < 1: by the fill
+    bool no_end_floor = false;          // PC_NO_END_FLOOR (per call): an end rule handed to the scan is ignored
 };
 
 // What the rules below need to know of the context.
@@ -39,6 +40,7 @@ struct Params {
     int len_hint = 0;                   // pc_set_length_hint
     bool int16_only = false;            // pc_set_int16_only
     int match = 3, mismatch = -6, gap_open = -5, gap_extend = -2;
+    bool end_rule = false;              // the call carries an end rule (pc_scan_device_end_rule, and the switch above is off)
     Options opt;
 };
 
@@ -59,6 +61,10 @@ struct Group {            // tiles that run in one launch
     // two-pass groups of a PC_MODE_TWO_PASS call have them too: the second pass of a floored call puts the pairs below their
     // job's score floor behind the others of their segment.  seg_job[s] = 2 * job + (0: its first adapter, 1: its second)
     std::vector<int32_t> seg_job;
+    // ... and so have the two-pass groups of a call with an end rule, which also asks for every segment's first window and
+    // adapter (the rule looks at the window's length and names the adapter's)
+    std::vector<int64_t> seg_win;
+    std::vector<int32_t> seg_adapter;
 };
 
 inline int group_rows(const Group &g) { return g.rows ? g.rows : g.gen_max_rows; }
@@ -112,10 +118,12 @@ struct Table {
 };
 
 // A pair whose windows of up to max_len columns are scanned score-only first and traced over `window` columns around the best cell
-inline bool two_pass_rule(int mode, int max_len, int window)
+// (end_rule: the call carries an end rule -- then, and only then, PC_MODE_AUTO takes short windows in two passes as well: what
+// the first pass costs is won back by the pairs the rule keeps out of the second)
+inline bool two_pass_rule(int mode, int max_len, int window, bool end_rule = false)
 {
     return mode == PC_MODE_TWO_PASS || mode == PC_MODE_SCORE || mode == PC_MODE_TRACE_AT ||
-           (mode == PC_MODE_AUTO && max_len > 2 * window + 64);
+           (mode == PC_MODE_AUTO && (end_rule || max_len > 2 * window + 64));
 }
 
 // The table of a job list.  Job k scans windows [job_start[k], job_start[k+1]) against adapter job_adapter[k] and, when
@@ -153,10 +161,11 @@ inline int build_table(const Panel &ad, const Params &p, const int32_t *job_adap
             bool pad = false;
             int rows = pck::pick_rows(ma, mbb, &pad);         // 0 => generic LDS-state kernel
             if (no_drift) { rows = 0; pad = true; }
-            const bool two = two_pass_rule(mode, max_len, window);
+            const bool two = two_pass_rule(mode, max_len, window, p.end_rule);
             // PC_MODE_TRACE_AT over short windows: a traced window never needs to be longer than the windows themselves
-            // (one that holds its read's column 0 starts from the true column 0: no warm-up before it)
-            if (mode == PC_MODE_TRACE_AT) window = std::min(window, std::max(1, max_len));
+            // (one that holds its read's column 0 starts from the true column 0: no warm-up before it); a call with an end
+            // rule caps its traced windows in the same way (plan_kernel: window_cap)
+            if (mode == PC_MODE_TRACE_AT || p.end_rule) window = std::min(window, std::max(1, max_len));
             auto key = std::make_pair(rows * 2 + (pad ? 1 : 0), two ? 1 : 0);
             group_window[key] = std::max(group_window[key], window);
             *rows_out = rows;
@@ -178,7 +187,7 @@ inline int build_table(const Panel &ad, const Params &p, const int32_t *job_adap
         // so two-pass jobs stay dual.  For 150-byte end windows two adapters of different row classes cost
         // fewer rows as two single-adapter jobs (same tile count, same output layout).
         bool pa_ = false, pb_ = false;
-        const bool split_dual = adb >= 0 && !two_pass_rule(mode, max_len, window) && !no_drift && !p.opt.no_split_dual &&
+        const bool split_dual = adb >= 0 && !two_pass_rule(mode, max_len, window, p.end_rule) && !no_drift && !p.opt.no_split_dual &&
                                 pck::pick_rows(m, m, &pa_) != pck::pick_rows(mb, mb, &pb_);
         job_of_first[out_pos] = 2 * k;                         // (first record of a segment -> whose it is)
         if (adb >= 0) job_of_first[out_pos + n] = 2 * k + 1;
@@ -262,7 +271,7 @@ inline int build_table(const Panel &ad, const Params &p, const int32_t *job_adap
         g.tile_count = (size_t)t;
         g.runs.swap(kv.second);
         out.ntiles += g.tile_count;
-        if (((!g.two_pass || mode == PC_MODE_TRACE_AT) && g.rows > 0) || (g.two_pass && mode == PC_MODE_TWO_PASS)) {
+        if (((!g.two_pass || mode == PC_MODE_TRACE_AT) && g.rows > 0) || (g.two_pass && (mode == PC_MODE_TWO_PASS || p.end_rule))) {
             g.seg_begin = out.seg_first.size(); g.blk_begin = out.blocks.size();
             for (const pck::TileRun &r : g.runs) {
                 for (int half = 0; half < (r.dual ? 2 : 1); ++half) {
@@ -270,6 +279,8 @@ inline int build_table(const Panel &ad, const Params &p, const int32_t *job_adap
                     const int32_t sgm = (int32_t)(out.seg_first.size() - g.seg_begin);
                     out.seg_first.push_back(first);
                     g.seg_job.push_back(job_of_first.at(first));
+                    g.seg_win.push_back(r.win0);
+                    g.seg_adapter.push_back(half ? r.adapter_hi : r.adapter_lo);
                     for (int64_t at = 0; at < r.n; at += pck::kBucketBlock)
                         out.blocks.push_back(pck::BucketBlock{first + at, (int32_t)std::min<int64_t>(pck::kBucketBlock, r.n - at), sgm});
                 }
@@ -517,8 +528,10 @@ inline std::vector<ScoreLaunch> plan_score_launches(const Params &p, const Group
 
 // ---- ordered and floored second passes -----------------------------------------------------------------------------
 
-// The score floors of a pc_scan_device_floored call: per job, for its first and its second adapter; null: none
-struct Floors { const int32_t *a = nullptr, *b = nullptr; };
+// The score floors of a pc_scan_device_floored call: per job, for its first and its second adapter; null: none.
+// rule_side: the sides of a pc_scan_device_end_rule call instead, per job (0: start windows, 1: end windows, < 0: the rule
+// does not apply to this job); null: no rule.  A call has floors or a rule, never both.
+struct Floors { const int32_t *a = nullptr, *b = nullptr, *rule_side = nullptr; };
 
 // PC_MODE_TRACE_AT (the traced minority of a pruned phase B), where the end cells are the caller's: the pairs of each
 // segment are taken by end column (coarsely), so that a tile is as long as its latest end cell needs, and every pair traces
@@ -549,13 +562,27 @@ inline bool floored(const Group &g, int mode, const Floors &f)
     for (size_t s = 0; s < g.nseg; ++s) if (seg_floor_of(g, s, f) != INT32_MIN) return true;
     return false;
 }
-// segments up to the last one of an ordered (or floored) group: the stride of the bucket counters; 0: no such group
+// A call with an end rule (pc_scan_device_end_rule) takes the same route with another test: between the passes the pairs of
+// which pc_end_rule.h proves, from their score records and window lengths, that they cannot trim their read are answered by
+// the planner and put behind the others.  The windows are short (end windows, 150 columns), so pass 2 is what PC_MODE_TRACE_AT
+// runs: pairs by end column, traced windows no longer than the windows themselves.  A group of more than pck::kRuleSegments
+// segments, or none of whose jobs has a side, is traced in full.
+inline int32_t seg_side_of(const Group &g, size_t s, const Floors &f) { return f.rule_side ? f.rule_side[g.seg_job[s] >> 1] : -1; }
+inline bool ruled(const Params &p, const Group &g, int mode, const Floors &f)
+{
+    if (!p.end_rule || !f.rule_side || (mode != PC_MODE_TWO_PASS && mode != PC_MODE_AUTO) || !g.two_pass || g.nseg == 0 ||
+        g.nseg > (size_t)pck::kRuleSegments || g.seg_job.size() != g.nseg || g.seg_win.size() != g.nseg || g.seg_adapter.size() != g.nseg)
+        return false;
+    for (size_t s = 0; s < g.nseg; ++s) if (seg_side_of(g, s, f) >= 0) return true;
+    return false;
+}
+// segments up to the last one of an ordered (or floored, or ruled) group: the stride of the bucket counters; 0: no such group
 inline size_t ordered_segments(const Params &p, const std::vector<Group> &groups, int mode, const Floors &f, bool *any_floored)
 {
     size_t n = 0;
     *any_floored = false;
     for (const Group &g : groups) {
-        const bool fl = floored(g, mode, f);
+        const bool fl = floored(g, mode, f) || ruled(p, g, mode, f);
         *any_floored |= fl;
         if (fl || ordered_trace_at(p, g, mode)) n = std::max(n, g.seg_begin + g.nseg);
     }

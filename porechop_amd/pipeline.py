@@ -21,11 +21,16 @@ import os
 import numpy as np
 import torch
 
-from .batch import MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS
+from .batch import MODE_AUTO, MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS
 
 # phase B is pruned (exactly: see "Exact pruning of phase B" below) from this many (sequence, side) jobs on; measured on
 # MI355X, 1 M reads: 198 jobs 192 -> 122 ms; with the 4-6 jobs of a run without barcodes tracing everything is faster
 PRUNE_MIN_JOBS = int(os.environ.get("PC_PRUNE_MIN_JOBS", "24"))
+# below that, phase B hands its rule to the end-window scan (pc_scan_device_end_rule) from this many reads on.  The route saves
+# traced cells per pair and costs six small launches per row class, one class after the other, where the traced-in-full launches
+# run two at a time: measured on MI355X with the headline's four jobs, one synchronised phase_b call takes 4.02 ms against 4.60
+# at 1 M reads, 2.88 / 2.82 at 600 k, 2.33 / 2.05 at 400 k, 1.46 / 0.82 at 100 k (profiles/end_floor_before_after.txt)
+END_RULE_MIN_READS = int(os.environ.get("PC_END_RULE_MIN_READS", "750000"))
 # up to this many adapter sets the prefilter stage of the middle scan takes ONE host round trip (survivors counted per set on
 # the device); a barcode panel's ~100 sets keep the single compaction over all of them
 LEAN_PREFILTER_GROUPS = 8
@@ -306,11 +311,15 @@ class Pipeline:
         """The bytes the end windows index: the read arena, or -- packed-only reads -- the copies of the end windows."""
         return reads.arena if reads.arena is not None else reads.ends[0]
 
-    def _scan_jobs(self, arena, jobs, mode, max_len, with_layout=False, sort_lengths=False, typ_len=0, fuse=True, floors=None):
+    def _scan_jobs(self, arena, jobs, mode, max_len, with_layout=False, sort_lengths=False, typ_len=0, fuse=True, floors=None,
+                   end_sides=None):
         """jobs: list of (adapter_index, win_off int64[n], win_len int32[n]) -> list of [n,8] views.
 
         floors (MODE_TWO_PASS): one score per job -- a pair whose best score is below it is not traced and gets the
         "no alignment" record (-1, 0, ..., 0), decided in the library between its two passes (Aligner.scan_device).
+        end_sides (MODE_AUTO over end windows): one side per job, 0 = start windows, 1 = end windows -- a pair that cannot trim
+        its read by phase B's rule (this pipeline's end_size, min_trim_size, extra_end_trim, end_threshold) gets that same
+        record instead of a traceback, decided in the same place.
 
         Jobs that scan the very same windows (same tensors) are fused two adapters at a time
         (similar lengths together), so each window is streamed from HBM once per adapter PAIR.
@@ -378,6 +387,10 @@ class Pipeline:
             if floors is not None:
                 fl = dict(floors=np.array([floors[a] for a, _ in fused], dtype=np.int32),
                           floors_b=np.array([floors[b] if b is not None else NO_FLOOR for _, b in fused], dtype=np.int32))
+            if end_sides is not None:
+                p = self.p
+                fl = dict(end_rule=(p.end_size, p.min_trim_size, p.extra_end_trim, p.end_threshold),
+                          job_side=np.array([end_sides[a] for a, _ in fused], dtype=np.int32))
             self.aligner.scan_device(arena, woff, wlen, np.array([jobs[a][0] for a, _ in fused], dtype=np.int32),
                                      starts, max_len, out, mode,
                                      job_adapter_b=np.array([jobs[b][0] if b is not None else -1 for _, b in fused],
@@ -685,6 +698,13 @@ class Pipeline:
         return self.native_reduce and hasattr(self.aligner, "phase_b_select") and getattr(self.aligner, "score_end_cell", False) and \
             self.packed_kernels()
 
+    @property
+    def can_rule_phase_b(self):
+        """Phase B hands its rule to the scan (Aligner.scan_device(end_rule=...)): needs the library's reduction, the packed
+        kernels for every pair and an aligner that offers the call.  PC_NO_END_FLOOR=1 switches it off."""
+        return self.native_reduce and getattr(self.aligner, "end_rule", False) and hasattr(self.aligner, "floor_skipped") and \
+            self.packed_kernels() and os.environ.get("PC_NO_END_FLOOR", "0") in ("", "0")
+
     def _prune_b(self, prune, njobs):
         """prune=None: the exact pruning of phase B where it pays -- a barcode panel's worth of jobs (with a handful of
         adapters the score pass, two selections and two host round trips cost more than tracing everything)."""
@@ -741,10 +761,13 @@ class Pipeline:
                                         require_two=require_two, call=call, **masked(tmask))
         return start_trim, end_trim, call.to(torch.int64).cpu().numpy()
 
-    def phase_b(self, reads: DeviceReads, matching: List[int], full_for=(), prune: Optional[bool] = None):
+    def phase_b(self, reads: DeviceReads, matching: List[int], full_for=(), prune: Optional[bool] = None,
+                end_rule: Optional[bool] = None):
         """-> (start_trim[R], end_trim[R]) int32: nanopore_read.py:166-208 for every read.
         full_for: set indices whose full-adapter identities are wanted too (barcode calling,
-        nanopore_read.py:185-187,206-208) -> third result {(set, side): float64[R]}, side 0 = start."""
+        nanopore_read.py:185-187,206-208) -> third result {(set, side): float64[R]}, side 0 = start.
+        end_rule (where the pruned route is not taken): None = the rule goes down to the scan where it pays, from
+        END_RULE_MIN_READS reads on; True / False = always / never (always: as far as can_rule_phase_b allows)."""
         R = reads.n
         p = self.p
         start_trim = torch.zeros(R, dtype=torch.int32, device=self.device)
@@ -757,7 +780,9 @@ class Pipeline:
         tmask = None
         if self.native_reduce and not full_for and R:
             sides = [w[0] for w in where]
-            if self._prune_b(prune, len(jobs)):
+            pruned_b = self._prune_b(prune, len(jobs))
+            ruled_b = not pruned_b and self.can_rule_phase_b and (R >= END_RULE_MIN_READS if end_rule is None else bool(end_rule))
+            if pruned_b:
                 def trims(records, offs, mask=None):
                     a = torch.zeros(R, dtype=torch.int32, device=self.device)
                     b = torch.zeros(R, dtype=torch.int32, device=self.device)
@@ -766,11 +791,25 @@ class Pipeline:
                     return a, b
                 out, rec_off = self._phase_b_pruned_records(reads, jobs, where, set(), 1e9, trims)
                 tmask = self._traced_mask
+            elif ruled_b:
+                # The library scans every window score-only, keeps the pairs that phase B's rule proves unable to trim out of
+                # the traced pass and answers them with the "no alignment" record, which is "no trim" in the reduction
+                # (pc_scan_device_end_rule; PC_NO_END_FLOOR=1: every pair traced, as below).  Every job alone: the
+                # single-sequence score kernels ship with the library and run 150-column windows as fast as a pair's kernel.
+                ruled = [tuple(j[:3]) + (("alone", k),) for k, j in enumerate(jobs)]
+                _, out, rec_off = self._scan_jobs(self._ends_arena(reads), ruled, MODE_AUTO, p.end_size, with_layout=True, end_sides=sides)
+                self.stats["pairs_end"] += sum(int(j[1].shape[0]) for j in jobs)
             else:
                 _, out, rec_off = self._scan_jobs(self._ends_arena(reads), jobs, MODE_TRACE, p.end_size, with_layout=True)
                 self.stats["pairs_end"] += sum(int(j[1].shape[0]) for j in jobs)
             self.aligner.phase_b_reduce(out, R, rec_off, sides, p.end_size, p.min_trim_size, p.extra_end_trim,
                                         p.end_threshold, start_trim, end_trim, **masked(tmask))
+            if ruled_b:
+                # (the pairs of this call alone; phase C waits for the trims in its first lines, so this wait costs no second one.
+                # They also stand in the running total that phase C reads for its own floors: noted as seen)
+                skipped = self.aligner.floor_skipped()[0]
+                self.stats["pairs_end_skipped_by_rule"] = self.stats.get("pairs_end_skipped_by_rule", 0) + skipped
+                self._floor_seen += skipped
             return start_trim, end_trim
         outs = self._scan_jobs(self._ends_arena(reads), jobs, MODE_TRACE, p.end_size)
         for (side, si), rec in zip(where, outs):
