@@ -203,6 +203,38 @@ int pc_align_paths(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, c
  * buflen.  -> the length it needs, without the NUL. */
 int pc_path_cigar(const uint32_t *ops, int path_len, char *buf, size_t buflen);
 
+/* Paths of MIDDLE hits: hit h is the alignment of adapter d_adapter_idx[h] of the context's table against the trimmed read
+ * [d_read_off[h], + d_read_len[h]) of the arena, MASKED as its round of mask-and-realign saw it: every base inside one of
+ * the intervals d_intervals[d_mask_base[h] .. + d_mask_count[h]) reads as '-' (Dna5 code 4, like N).  d_read_end[h] is the
+ * hit's exclusive read end, as the scan reported it.  Outputs are those of pc_align_paths, record, head and operations in
+ * TRIMMED-READ coordinates (read_first counts from the trimmed read's first base).  All pointers but `ctx` are device
+ * memory; d_records and d_heads are 16-byte aligned.
+ *   * Only a window of the read is aligned: with W, SPAN and window = W + SPAN + 1 of the adapter's own length
+ *     (pc_bounds.h), columns max(0, read_end - window) + 1 .. min(read_len, read_end + W).  Given the read end of an
+ *     alignment the whole masked read has, record, head and operations are exactly those of pc_align_paths over the
+ *     whole, explicitly masked read.  Under a scheme the packed kernels refuse the window is the
+ *     whole read.  Only bytes inside the window are read.
+ *   * d_intervals is int32 [n][2], {start, end (exclusive)} in trimmed-read coordinates, one row per hit of the call; a
+ *     caller lists the hits sorted stably by read, so that hit h at rank k within its read has d_mask_base[h] = its
+ *     read's first row and d_mask_count[h] = k.  Intervals may be empty, overlap or reach past the read.
+ *   * The host knows the widest window without reading device memory (pc_middle_paths_cols): min(max_len, the largest
+ *     window + W of the table), or max_len under a refused scheme.  ops_pitch_words >= ceil((that + longest adapter of
+ *     the table) / 16), else PC_ERR_BAD_ARG before anything is launched.  A table holding an adapter above 128 bases is
+ *     PC_ERR_BAD_ARG as well.  n == 0 is fine.
+ *   * No host round trip: a hit whose d_read_len is above max_len, whose adapter index is outside the table, whose
+ *     d_read_end is outside [0, d_read_len], whose d_mask_count is negative or whose interval run leaves the n rows is
+ *     caught by the kernel, which writes nothing for that hit, and surfaces as PC_ERR_INTERNAL at pc_sync.  So does a
+ *     d_read_end no alignment of the masked read has (the walk leaves the window).
+ *   * The trace lives in a scratch buffer of the context; slicing into launches follows pc_align_paths' rule (the same
+ *     PC_PATHS_SCRATCH_MB, read per call, never fewer than 64 hits).  Asynchronous. */
+int pc_middle_paths(pc_ctx *ctx, const void *d_arena, const int64_t *d_read_off, const int32_t *d_read_len,
+                    const int32_t *d_adapter_idx, const int32_t *d_read_end, const int64_t *d_mask_base,
+                    const int32_t *d_mask_count, const int32_t *d_intervals, int64_t n, int max_len,
+                    int32_t *d_records, int32_t *d_heads, uint32_t *d_ops, int64_t ops_pitch_words, void *stream);
+/* Host: the widest window (columns) a hit of pc_middle_paths can have over reads of up to max_len bases with the context's
+ * table and scheme; < 0: an error code. */
+int pc_middle_paths_cols(pc_ctx *ctx, int max_len);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,

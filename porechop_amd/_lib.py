@@ -26,6 +26,7 @@ EXPORTS = [
     "pc_kmer_count", "pc_kmer_select",
     "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule",
     "pc_align_paths", "pc_path_cigar",
+    "pc_middle_paths", "pc_middle_paths_cols",
 ]
 
 
@@ -93,6 +94,10 @@ def load_library():
     L.pc_align_paths.restype = c_int
     L.pc_path_cigar.argtypes = [c_vp, c_int, c_vp, ctypes.c_size_t]
     L.pc_path_cigar.restype = c_int
+    L.pc_middle_paths.argtypes = [c_vp] * 9 + [c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp]
+    L.pc_middle_paths.restype = c_int
+    L.pc_middle_paths_cols.argtypes = [c_vp, c_int]
+    L.pc_middle_paths_cols.restype = c_int
     L.pc_sync.argtypes = [c_vp, c_vp]
     L.pc_sync.restype = c_int
     L.pc_copy_windows.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_int, c_vp]

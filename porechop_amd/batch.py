@@ -139,6 +139,7 @@ class Aligner:
     trace_at = True            # MODE_TRACE_AT: the traced record of a pair whose MODE_SCORE record (its end cell) is known
     end_rule = True            # scan_device(end_rule=..., job_side=...): end windows traced only where phase B's rule can trim
     paths = True               # align_paths / align_pairs_paths: records with the alignment's path (pc_align_paths)
+    # (middle_paths, the method below, is its own flag: callers ask getattr(aligner, "middle_paths", False))
 
     def __init__(self, adapters, scores=DEFAULT_SCORES, device=-1):
         self.lib = load_library()
@@ -298,6 +299,45 @@ class Aligner:
         self.sync()
         heads = heads.cpu().numpy()
         return recs.cpu().numpy(), heads, decode_paths(heads, ops.cpu().numpy())
+
+    # ---- paths of middle hits (pc_middle_paths.hip) ---------------------------------------------------------------------
+    def middle_paths_cols(self, max_len):
+        """The widest window (columns) a hit of middle_paths can have over reads of up to max_len bases
+        (pc_middle_paths_cols: host arithmetic over the table and the scheme)."""
+        cols = self.lib.pc_middle_paths_cols(self._ctx, int(max_len))
+        if cols < 0:
+            check(cols, "pc_middle_paths_cols")
+        return int(cols)
+
+    def middle_paths(self, arena, read_off, read_len, adapter_idx, read_end, mask_base, mask_count, intervals, max_len=None,
+                     stream=None, ops_pitch=None):
+        """The paths of n MIDDLE hits (pc_middle_paths), each from a bounded window of its masked trimmed read.  CUDA
+        tensors: arena uint8[*]; per hit read_off int64[n], read_len int32[n] (the trimmed read), adapter_idx int32[n],
+        read_end int32[n] (exclusive, trimmed-read coordinates), mask_base int64[n] and mask_count int32[n] into intervals
+        int32[n, 2] (the hits' [start, end), sorted stably by read: the bases of rows mask_base .. + mask_count read as
+        '-').  max_len bounds read_len (None: its maximum, one host round trip).  -> (records int32[n, 8], heads
+        int32[n, 4], ops int32[n, pitch]) as align_paths, in trimmed-read coordinates.  Asynchronous; call sync()."""
+        import torch
+        tensors = (arena, read_off, read_len, adapter_idx, read_end, mask_base, mask_count, intervals)
+        assert all(t.is_cuda and t.is_contiguous() for t in tensors)
+        assert arena.dtype == torch.uint8 and read_off.dtype == torch.int64 and mask_base.dtype == torch.int64
+        assert all(t.dtype == torch.int32 for t in (read_len, adapter_idx, read_end, mask_count, intervals))
+        n = int(read_off.shape[0])
+        assert all(int(t.shape[0]) == n for t in tensors[2:]) and tuple(intervals.shape) == (n, 2)
+        if max_len is None:
+            max_len = int(read_len.max().item()) if n else 0
+        max_len = int(max_len)
+        pitch = max(1, (self.middle_paths_cols(max_len) + self.longest_adapter() + 15) // 16) if ops_pitch is None else int(ops_pitch)
+        dev = arena.device
+        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=dev)
+        heads = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        ops = torch.zeros((n, max(1, pitch)), dtype=torch.int32, device=dev)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.pc_middle_paths(self._ctx, arena.data_ptr(), read_off.data_ptr(), read_len.data_ptr(), adapter_idx.data_ptr(),
+                                       read_end.data_ptr(), mask_base.data_ptr(), mask_count.data_ptr(), intervals.data_ptr(), n,
+                                       max_len, records.data_ptr(), heads.data_ptr(), ops.data_ptr(), pitch, ctypes.c_void_p(s)),
+              "pc_middle_paths")
+        return records, heads, ops
 
     def floor_skipped(self, stream=None):
         """-> (pairs the last floored scan left untraced, those of all floored scans of this context) (pc_floor_skipped;

@@ -24,6 +24,7 @@
 #include "pc_bounds.h"
 #include "pc_slow.h"
 #include "pc_paths.h"
+#include "pc_middle_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
 #include "pc_prefilter_plan.h"
@@ -127,6 +128,7 @@ struct pc_ctx {
     std::vector<int64_t> slow_ad_off;        // offsets of the adapters' Dna5 codes in d_slow_ad
     DevBuf d_slow_ad, d_slow_state, d_slow_trace;
     DevBuf d_paths_trace;                    // pc_align_paths: the packed trace of one launch (pc_paths.hip)
+    DevBuf d_middle_paths_trace;             // pc_middle_paths: the same for its windows (pc_middle_paths.hip)
     std::vector<int32_t> last_job_adapter, last_job_adapter_b;
     std::vector<int64_t> last_job_start;
     int last_max_len = -1, last_mode = -1;
@@ -845,7 +847,7 @@ void pc_destroy(pc_ctx *c)
                       &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
                       &c->d_sd_entries, &c->d_sd_meta, &c->d_sd_eq, &c->d_sd_cand, &c->d_sd_count, &c->d_slow_ad, &c->d_slow_state,
-                      &c->d_slow_trace, &c->d_paths_trace};
+                      &c->d_slow_trace, &c->d_paths_trace, &c->d_middle_paths_trace};
     if (c->h_sd_count) (void)hipHostFree(c->h_sd_count);
     c->h_table_slot[0].release(); c->h_table_slot[1].release();
     for (DevBuf *b : bufs) b->release();
@@ -995,6 +997,81 @@ int pc_align_paths(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     for (int64_t first = 0; first < n; first += P) {
         a.first = first; a.count = std::min<int64_t>(P, n - first);
         if (pck::launch_paths(a, stream)) return PC_ERR_NO_DEVICE;
+    }
+    return PC_OK;
+}
+
+namespace {
+
+// pc_middle_paths: the table's longest adapter (LDS rows) and the widest window a hit can have -- min(max_len, the largest
+// window + W of the table), max_len as soon as one adapter takes the whole read (ad_window 0: compute_bounds refused)
+int middle_paths_shape(pc_ctx *c, int max_len, int &rows, int &cols)
+{
+    int rc = upload_panel(c);
+    if (rc) return rc;
+    rows = 1;
+    int64_t widest = 0;
+    for (size_t i = 0; i < c->adapters.size(); ++i) {
+        if (c->ad_len[i] > pcb::MAX_ADAPTER) return PC_ERR_BAD_ARG;     // the code table holds 128 bases per adapter
+        rows = std::max(rows, c->ad_len[i]);
+        const int64_t window = c->ad_window[i], W = window - c->ad_span[i] - 1;
+        widest = std::max(widest, window > 0 ? window + W : (int64_t)max_len);
+    }
+    cols = (int)std::min<int64_t>(max_len, widest);
+    return PC_OK;
+}
+
+}  // namespace
+
+int pc_middle_paths_cols(pc_ctx *c, int max_len)
+{
+    if (!c || max_len < 0) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rows, cols;
+    const int rc = middle_paths_shape(c, max_len, rows, cols);
+    return rc ? rc : cols;
+}
+
+int pc_middle_paths(pc_ctx *c, const void *d_arena, const int64_t *d_read_off, const int32_t *d_read_len,
+                    const int32_t *d_adapter_idx, const int32_t *d_read_end, const int64_t *d_mask_base,
+                    const int32_t *d_mask_count, const int32_t *d_intervals, int64_t n, int max_len,
+                    int32_t *d_records, int32_t *d_heads, uint32_t *d_ops, int64_t ops_pitch_words, void *stream_v)
+{
+    if (!c || n < 0 || max_len < 0 || ops_pitch_words < 0) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rows, cols;
+    int rc = middle_paths_shape(c, max_len, rows, cols);
+    if (rc) return rc;
+    if (ops_pitch_words < pcpath::ops_words(cols, c->adapters.empty() ? 0 : rows)) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_read_off || !d_read_len || !d_adapter_idx || !d_read_end || !d_mask_base || !d_mask_count ||
+        !d_intervals || !d_records || !d_heads || !d_ops) return PC_ERR_BAD_ARG;
+    if (!pcs::fits(cols, rows, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
+        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
+                c->match, c->mismatch, c->gap_open, c->gap_extend, cols, rows);
+        return PC_ERR_UNSUPPORTED_SCORES;
+    }
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    // pc_align_paths' rule: the same budget, read per call
+    size_t budget = kPathsScratchMB << 20;
+    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
+    const int groups = pcpath::row_groups(rows);
+    const size_t per_hit = (size_t)std::max(1, cols) * (size_t)groups * 4;
+    const int64_t P = pcn::slice_pairs(budget, per_hit, n);
+    if ((rc = c->d_middle_paths_trace.ensure((size_t)P * per_hit + 256))) return rc;
+    pck::MiddlePathArgs a;
+    memset(&a, 0, sizeof a);
+    a.arena = (const uint8_t *)d_arena; a.read_off = d_read_off; a.read_len = d_read_len; a.adapter_idx = d_adapter_idx;
+    a.read_end = d_read_end; a.mask_base = d_mask_base; a.mask_count = d_mask_count; a.intervals = d_intervals; a.n = n;
+    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>();
+    a.ad_window = c->d_ad_window.as<int32_t>(); a.ad_span = c->d_ad_span.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
+    a.rows = rows; a.groups = groups; a.max_len = max_len; a.max_cols = cols;
+    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
+    a.records = d_records; a.heads = d_heads; a.ops = d_ops; a.ops_pitch = ops_pitch_words;
+    a.trace = c->d_middle_paths_trace.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
+    for (int64_t first = 0; first < n; first += P) {
+        a.first = first; a.count = std::min<int64_t>(P, n - first);
+        if (pck::launch_middle_paths(a, stream)) return PC_ERR_NO_DEVICE;
     }
     return PC_OK;
 }

@@ -415,4 +415,37 @@ struct PathArgs {
 };
 int launch_paths(const PathArgs &a, void *stream);
 
+// the middle-hit path kernel of pc_middle_paths.hip: hits first .. first + count of the caller's arrays, each lane its own
+// adapter, its own window of its trimmed read and its own run of the interval table; outputs are indexed by the hit of the
+// CALL, the trace scratch by the hit of the launch
+struct MiddlePathArgs {
+    const uint8_t *arena;
+    const int64_t *read_off;     // [n] the trimmed read's first byte
+    const int32_t *read_len;     // [n] its bases
+    const int32_t *adapter_idx;
+    const int32_t *read_end;     // [n] the hit's exclusive read end, trimmed-read coordinates
+    const int64_t *mask_base;    // [n] first row of the hit's earlier intervals in `intervals`
+    const int32_t *mask_count;   // [n] how many
+    const int32_t *intervals;    // [n][2] {start, end (exclusive)}, trimmed-read coordinates
+    int64_t n;                   // hits of the call (rows of `intervals`)
+    int64_t first, count;
+    const uint32_t *ad_codes;    // [nadapters][kMaxRows] Dna5 codes
+    const int32_t *ad_len;       // [nadapters]
+    const int32_t *ad_window;    // [nadapters] pcb::Bounds::window, 0 where compute_bounds refuses
+    const int32_t *ad_span;      // [nadapters] pcb::Bounds::SPAN
+    int32_t nadapters;
+    int32_t rows, groups;        // longest adapter of the table (LDS rows) and its row groups of eight (scratch)
+    int32_t max_len;
+    int32_t max_cols;            // columns of the scratch: the widest window any hit of the call can have
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t *records;            // [n][8]
+    int32_t *heads;              // [n][4]
+    uint32_t *ops;               // [n][ops_pitch]
+    int64_t ops_pitch;
+    uint32_t *trace;             // [max_cols][groups][P] dwords
+    int64_t P;                   // hits of a launch (stride of the scratch)
+    uint32_t *err;
+};
+int launch_middle_paths(const MiddlePathArgs &a, void *stream);
+
 }  // namespace pck

@@ -179,6 +179,31 @@ def trimmed_interval(length, start_trim, end_trim):
     return s_pos, e_pos
 
 
+def middle_mask_tables(read, start, end):
+    """What Aligner.middle_paths needs to see each middle hit's read masked as its round of mask-and-realign saw it, from the
+    hit list alone (MiddleHits lists a read's hits in discovery order; masking never moves a coordinate).
+    read int64 [H], start / end int32 [H] -> (intervals int32 [H, 2], mask_base int64 [H], mask_count int32 [H]):
+    intervals are the hits' [start, end) stably sorted by read -- no interval is copied twice -- and hit h at rank k within
+    its read gets mask_base = its read's first row and mask_count = k: the rows of its read's earlier hits."""
+    H = int(read.shape[0])
+    dev = read.device
+    if H == 0:
+        return (torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+                torch.zeros(0, dtype=torch.int32, device=dev))
+    order = torch.sort(read, stable=True).indices
+    sorted_read = read[order]
+    row = torch.arange(H, dtype=torch.int64, device=dev)
+    first = torch.ones(H, dtype=torch.bool, device=dev)
+    first[1:] = sorted_read[1:] != sorted_read[:-1]
+    first_row = torch.cummax(torch.where(first, row, torch.zeros_like(row)), 0).values
+    intervals = torch.stack([start[order], end[order]], dim=1).to(torch.int32).contiguous()
+    mask_base = torch.empty(H, dtype=torch.int64, device=dev)
+    mask_base[order] = first_row
+    mask_count = torch.empty(H, dtype=torch.int32, device=dev)
+    mask_count[order] = (row - first_row).to(torch.int32)
+    return intervals, mask_base, mask_count
+
+
 def call_barcodes(nbins: int, start_scores: torch.Tensor, end_scores: torch.Tensor, barcode_threshold: float,
                   barcode_diff: float, require_two_barcodes: bool) -> np.ndarray:
     """nanopore_read.py:399-466 for every read at once (torch formulation; the GPU product path runs
@@ -1368,6 +1393,44 @@ class Pipeline:
             return empty
         return MiddleHits(torch.cat(H_read), torch.cat(H_ad), torch.cat(H_s), torch.cat(H_e), torch.cat(H_id),
                           rounds, n_align)
+
+    def middle_hit_paths(self, reads: DeviceReads, start_trim, end_trim, hits: MiddleHits):
+        """The alignment path of every middle hit of phase_c (same reads, trims and matching sets; hits.adapter indexes the
+        middle adapters of that call) -> (records int32 [H, 8], heads int32 [H, 4], ops int32 [H, pitch]) in trimmed-read
+        coordinates, row for row with `hits` (Aligner.middle_paths, one call).  The masked read of a later round is rebuilt
+        from the hit list (middle_mask_tables) and only a bounded window around the hit is aligned.
+        Every returned record must carry its hit's read_start, read_end and full identity: a difference raises."""
+        al = self.aligner
+        if not getattr(al, "middle_paths", False):
+            raise RuntimeError("this aligner returns no paths for middle hits (Aligner.middle_paths)")
+        dev = self.device
+        H = int(hits.read.shape[0])
+        if H == 0:
+            return (torch.zeros((0, RESULT_INTS), dtype=torch.int32, device=dev), torch.zeros((0, 4), dtype=torch.int32, device=dev),
+                    torch.zeros((0, 1), dtype=torch.int32, device=dev))
+        if reads.arena is None:
+            reads.materialize(al)                                    # every base of a window is needed as a byte
+        if hasattr(al, "trim_windows"):
+            toff, tlen, _ = al.trim_windows(reads.off, reads.length, start_trim, end_trim)
+        else:
+            s_pos, e_pos = trimmed_interval(reads.length, start_trim, end_trim)
+            tlen = torch.clamp(e_pos - s_pos, min=0).to(torch.int32)
+            toff = reads.off + s_pos
+        aidx = torch.tensor([self.seq_index[a[1]] for a in self.middle_adapters], dtype=torch.int32, device=dev)
+        intervals, mask_base, mask_count = middle_mask_tables(hits.read, hits.start, hits.end)
+        read_off = toff[hits.read].to(torch.int64).contiguous()
+        read_len = tlen[hits.read].to(torch.int32).contiguous()
+        recs, heads, ops = al.middle_paths(reads.arena, read_off, read_len, aidx[hits.adapter.to(torch.int64)].contiguous(),
+                                           hits.end.to(torch.int32).contiguous(), mask_base, mask_count, intervals)
+        # (the %f-rounded full identity, from the code phase_c got the hits' from)
+        full = al.middle_hits(recs, self.p.middle_threshold)[0] if hasattr(al, "middle_hits") else _identities(recs)[0]
+        same = (recs[:, 0] == hits.start) & (recs[:, 1] + 1 == hits.end) & (full == hits.identity)
+        if not bool(same.all()):
+            k = int(torch.nonzero(~same)[0])
+            raise RuntimeError("alignment path of middle hit %d (read %d, adapter %d, %d-%d, identity %r) carries another record: %r"
+                               % (k, int(hits.read[k]), int(hits.adapter[k]), int(hits.start[k]), int(hits.end[k]),
+                                  float(hits.identity[k]), recs[k].tolist()))
+        return recs, heads, ops
 
     def close(self):
         self.aligner.close()

@@ -95,6 +95,7 @@ class RunExplain:
     albacore: Optional[List[Optional[str]]] = None
     calls: Optional[List[str]] = None        # the final call, after the Albacore rule
     hit_cigars: Optional[List[str]] = None   # run(..., report_paths=True): per row of `hits`, "read_first|adapter_first|CIGAR"
+    middle_cigars: Optional[List[str]] = None   # run(..., report_middle_paths=True): per row of `middle`, the same, trimmed-read coordinates
 
     @staticmethod
     def identity(matches, length):
@@ -135,15 +136,17 @@ REPORT_COLUMNS = ["name", "length", "start_trim", "end_trim", "start_alignments"
 
 
 REPORT_PATH_COLUMNS = ["start_cigars", "end_cigars"]              # appended by run(..., report_paths=True)
+REPORT_MIDDLE_PATH_COLUMNS = ["middle_cigars"]                    # appended (last) by run(..., report_middle_paths=True)
 
 
-def report_header(paths=False):
-    return "#" + "\t".join(REPORT_COLUMNS + (REPORT_PATH_COLUMNS if paths else [])) + "\n"
+def report_header(paths=False, middle_paths=False):
+    return "#" + "\t".join(REPORT_COLUMNS + (REPORT_PATH_COLUMNS if paths else []) + (REPORT_MIDDLE_PATH_COLUMNS if middle_paths else [])) + "\n"
 
 
 def report_rows(ex: RunExplain, names, lengths):
     """The report's rows for the reads of `ex` (TSV; list columns ';'-joined, '.' when empty or not applicable).  With the
-    per-hit paths (ex.hit_cigars) two columns follow: start_cigars / end_cigars, entry for entry with the alignment columns."""
+    per-hit paths (ex.hit_cigars) two columns follow: start_cigars / end_cigars, entry for entry with the alignment columns;
+    with the middle hits' paths (ex.middle_cigars) one more, middle_cigars, entry for entry with middle_hits."""
     rows = []
     for r in range(ex.summary.shape[0]):
         starts, ends = ex.end_alignments(r)
@@ -160,6 +163,8 @@ def report_rows(ex: RunExplain, names, lengths):
             cols += [alb if alb is not None else ".", ex.calls[r]]
         if ex.hit_cigars is not None:
             cols += [";".join(xs) or "." for xs in ex.end_cigars(r)]
+        if ex.middle_cigars is not None:
+            cols.append(";".join(ex.middle_cigars[int(ex.middle_first[r]):int(ex.middle_first[r + 1])]) or ".")
         rows.append("\t".join(cols) + "\n")
     return "".join(rows)
 
@@ -202,7 +207,8 @@ def _host_explain(parts, R, pl, match_idx, sc, albacore, paths=False):
     np.cumsum(np.bincount(hits_h[:, 0], minlength=R), out=middle_first[1:])
     return RunExplain(summary, bscore, hit_first, hits, [side for side, _ in jobs], [pl.sets[si].name for _, si in jobs], sc.bin_names,
                       middle_first, hits_h[order][:, 1:4], hits_id[order],
-                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, sc.calls, cigars)
+                      [a[0] for a in pl.middle_adapter_list(match_idx)] if match_idx else [], albacore, sc.calls, cigars,
+                      None if sc.middle_cigars is None else [sc.middle_cigars[k] for k in order.tolist()])
 
 
 # (read, adapter) pairs one block of phases B / C may hold at a time: 8 ints each, a few copies -> a few GB of HBM
@@ -445,11 +451,14 @@ def _find_sets(pl, panel, reads, check_idx, opts, barcode_dir, sharded=False):
     return matching, [index_of[id(s)] for s in matching], orientation
 
 
-def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, explain_paths=False):
+def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, explain_paths=False,
+                middle_paths=None):
     """Phases B (+ barcode calls) and C for R resident reads -> (start_trim, end_trim [device int32], bin index per
     read [numpy int64, -1 = none], MiddleHits or None).
     explain: a list that receives the EndExplain of every block; phase B then runs with every pair traced
-    (Pipeline.phase_b_explain) -- the same trims and calls; explain_paths: with the path of every qualifying alignment."""
+    (Pipeline.phase_b_explain) -- the same trims and calls; explain_paths: with the path of every qualifying alignment.
+    middle_paths: a list that receives (heads, ops) of Pipeline.middle_hit_paths for every block with middle hits, in the order
+    the hits are returned in."""
     dev = pl.device
     start_trim = torch.zeros(R, dtype=torch.int32, device=dev)
     end_trim = torch.zeros(R, dtype=torch.int32, device=dev)
@@ -492,6 +501,8 @@ def _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lam
                 fast = getattr(pl.aligner, "fast_prefilter", False)
                 hb = pl.phase_c(sub, st_b, et_b, match_idx, prove=not fast, prefilter=fast)
                 if hb.read.numel():
+                    if middle_paths is not None:                     # (the block's own read numbers: before the shift)
+                        middle_paths.append(pl.middle_hit_paths(sub, st_b, et_b, hb)[1:])
                     hb.read = hb.read + b0
                     hit_parts.append(hb)
                 lap("phase_c", sync=True)
@@ -518,15 +529,19 @@ class _Scan:
     identity: Optional[np.ndarray]           # float64 [H], only for the per-read report
     bin_names: Optional[List[str]]           # None when not demultiplexing
     calls: Optional[List[str]]               # bin name per read, "none" without a call
+    middle_cigars: Optional[List[str]] = None   # per row of `hits`, "read_first|adapter_first|CIGAR" (report_middle_paths)
 
 
 def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, read_base=0,
-                  gather=None, explain_paths=False):
+                  gather=None, explain_paths=False, middle_paths=False):
     """_scan_reads for R resident reads, then everything a run needs of it on the host -> _Scan.  The hits' reads are numbered
     from read_base.  gather: called with the device tensors (start_trim, end_trim, bin index, hits [H, 4]) before they leave the
-    device -> the same four for the reads the _Scan is to cover (run() gathers every rank's there)."""
+    device -> the same four for the reads the _Scan is to cover (run() gathers every rank's there).  middle_paths: with the
+    path of every middle hit (never together with gather)."""
     dev = pl.device
-    start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain, explain_paths)
+    mp_parts = [] if middle_paths else None
+    start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain, explain_paths,
+                                                 mp_parts)
     if hasattr(pl.aligner, "sync"):
         pl.aligner.sync()
     if hits is not None and hits.read.numel():
@@ -545,7 +560,15 @@ def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=l
     if barcode_dir is not None:
         names = _barcode_bin_names(pl, match_idx, orientation)            # the same list on every rank
         calls = [names[k] if k >= 0 else "none" for k in ci]
-    return _Scan(start_trim.cpu().numpy(), end_trim.cpu().numpy(), h, identity, names, calls)
+    middle_cigars = None
+    if middle_paths:
+        from .batch import cigar, decode_paths
+        middle_cigars = []
+        for heads, ops in mp_parts:                                   # chained like the hits
+            heads = heads.cpu().numpy()
+            middle_cigars += ["%d|%d|%s" % (int(hd[1]), int(hd[2]), cigar(t)) for hd, t in zip(heads, decode_paths(heads, ops.cpu().numpy()))]
+        assert len(middle_cigars) == h.shape[0]
+    return _Scan(start_trim.cpu().numpy(), end_trim.cpu().numpy(), h, identity, names, calls, middle_cigars)
 
 
 def _concat_explain(blocks):
@@ -560,7 +583,8 @@ def _concat_explain(blocks):
                       middle_first, middle, cat("middle_identity"), b0.middle_names,
                       None if b0.albacore is None else [a for b in blocks for a in b.albacore],
                       None if b0.calls is None else [c for b in blocks for c in b.calls],
-                      None if b0.hit_cigars is None else [c for b in blocks for c in b.hit_cigars])
+                      None if b0.hit_cigars is None else [c for b in blocks for c in b.hit_cigars],
+                      None if b0.middle_cigars is None else [c for b in blocks for c in b.middle_cigars])
 
 
 def _plan_pieces(opts, barcode_dir, lengths, sc, matching, pl, match_idx):
@@ -623,14 +647,15 @@ def _stream_block_bytes():
 
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
-                 report_paths: bool = False) -> Optional[RunResult]:
+                 report_paths: bool = False, report_middle_paths: bool = False) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
     Phase A and the set-level rules run once, on the first block, which must hold the check reads.  Everything after
     that is per read in Porechop (phases B and C, barcode calls, splitting, naming), so the output files are the ones
     run() writes.  Plain FASTA files (cut where a line begins with '>') and the gzip forms of both stream the same way.
-    report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths as in run().
+    report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths and
+    report_middle_paths as in run().
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
@@ -759,7 +784,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     try:
         if report is not None:
             report_fh = open(report, "w")
-            report_fh.write(report_header(report_paths))
+            report_fh.write(report_header(report_paths, report_middle_paths))
         rs = first
         while rs is not None:
             if failure:
@@ -773,7 +798,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 res.matching_sets = [s.name for s in matching]
                 res.barcode_orientation = orientation
             ex_parts = [] if report is not None else None
-            sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts, explain_paths=report_paths)
+            sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts, explain_paths=report_paths,
+                               middle_paths=report_middle_paths)
             if barcode_dir is not None:
                 calls_all.extend(sc.calls)
             if report is not None:
@@ -1000,7 +1026,8 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
-        adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False) -> RunResult:
+        adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False,
+        report_middle_paths: bool = False) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1011,7 +1038,11 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     report_paths=True appends two columns, start_cigars and end_cigars: per entry of start_alignments / end_alignments its
     path as read_first|adapter_first|CIGAR (= X I D run lengths; the adapter plays SAM's reference), in the window
     coordinates of the entry's read_start / read_end (Pipeline.phase_b_explain(paths=True), Aligner.align_paths).  Without
-    it the report is byte for byte the one above.  Middle hits get no paths.
+    it the report is byte for byte the one above.
+    report_middle_paths=True appends ONE column, middle_cigars (after start_cigars / end_cigars when both are asked for): per
+    entry of middle_hits its path as read_first|adapter_first|CIGAR in trimmed-read coordinates, against the read masked as
+    its round of mask-and-realign saw it (Pipeline.middle_hit_paths, Aligner.middle_paths).  Without
+    it every report is byte for byte what it is without this option.
 
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
@@ -1033,13 +1064,15 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     sharded = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1     # one process per GPU
     if report_paths and report is None:
         raise UsageError("Error: --report_paths needs --report")
+    if report_middle_paths and report is None:
+        raise UsageError("Error: --report_middle_paths needs --report")
     if report is not None and sharded:
         raise UsageError("Error: the per-read report is not available in a sharded run (one process per GPU): run it in a single process")
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
-                                report=report, report_paths=report_paths)
+                                report=report, report_paths=report_paths, report_middle_paths=report_middle_paths)
         if streamed is not None:
             return streamed
 
@@ -1086,7 +1119,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
 
         ex_parts = [] if report is not None else None
         sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, ex_parts, read_base=lo_r,
-                           gather=gather if sharded else None, explain_paths=report_paths)
+                           gather=gather if sharded else None, explain_paths=report_paths, middle_paths=report_middle_paths)
         if rank != 0:
             res.start_trim, res.end_trim = sc.st, sc.et
             return res                                           # rank 0 writes
@@ -1097,7 +1130,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         if report is not None:
             res.explain = _host_explain(ex_parts, R, pl, match_idx, sc, albacore, report_paths)
             with open(report, "w") as fh:
-                fh.write(report_header(report_paths))
+                fh.write(report_header(report_paths, report_middle_paths))
                 fh.write(report_rows(res.explain, [rs.name(i) for i in range(R)], rs.lengths))
             lap("report")
 
