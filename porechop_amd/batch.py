@@ -251,6 +251,15 @@ class Aligner:
     def longest_adapter(self):
         return max([len(a) for a in self.adapters] or [0])
 
+    @staticmethod
+    def _path_outputs(dev, n, pitch, stream):
+        # -> zeroed (records, heads, ops) for n alignments on dev, and the stream handle the call runs on
+        import torch
+        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=dev)
+        heads = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+        ops = torch.zeros((n, max(1, pitch)), dtype=torch.int32, device=dev)
+        return records, heads, ops, stream if stream is not None else torch.cuda.current_stream().cuda_stream
+
     def align_paths(self, arena, win_off, win_len, adapter_idx, max_len=None, stream=None):
         """The alignments of n (window, adapter) pairs WITH their paths (pc_align_paths).  arena uint8[*], win_off int64[n],
         win_len int32[n], adapter_idx int32[n]: CUDA tensors; max_len bounds win_len (None: its maximum, one host round
@@ -267,11 +276,7 @@ class Aligner:
             max_len = int(win_len.max().item()) if n else 0
         max_len = int(max_len)
         pitch = max(1, (max_len + self.longest_adapter() + 15) // 16)
-        dev = arena.device
-        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=dev)
-        heads = torch.zeros((n, 4), dtype=torch.int32, device=dev)
-        ops = torch.zeros((n, pitch), dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        records, heads, ops, s = self._path_outputs(arena.device, n, pitch, stream)
         check(self.lib.pc_align_paths(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), adapter_idx.data_ptr(), n,
                                       max_len, records.data_ptr(), heads.data_ptr(), ops.data_ptr(), pitch, ctypes.c_void_p(s)),
               "pc_align_paths")
@@ -300,7 +305,7 @@ class Aligner:
         heads = heads.cpu().numpy()
         return recs.cpu().numpy(), heads, decode_paths(heads, ops.cpu().numpy())
 
-    # ---- paths of middle hits (pc_middle_paths.hip) ---------------------------------------------------------------------
+    # ---- paths of middle hits (pc_paths.hip) ----------------------------------------------------------------------------
     def middle_paths_cols(self, max_len):
         """The widest window (columns) a hit of middle_paths can have over reads of up to max_len bases
         (pc_middle_paths_cols: host arithmetic over the table and the scheme)."""
@@ -328,11 +333,7 @@ class Aligner:
             max_len = int(read_len.max().item()) if n else 0
         max_len = int(max_len)
         pitch = max(1, (self.middle_paths_cols(max_len) + self.longest_adapter() + 15) // 16) if ops_pitch is None else int(ops_pitch)
-        dev = arena.device
-        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=dev)
-        heads = torch.zeros((n, 4), dtype=torch.int32, device=dev)
-        ops = torch.zeros((n, max(1, pitch)), dtype=torch.int32, device=dev)
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        records, heads, ops, s = self._path_outputs(arena.device, n, pitch, stream)
         check(self.lib.pc_middle_paths(self._ctx, arena.data_ptr(), read_off.data_ptr(), read_len.data_ptr(), adapter_idx.data_ptr(),
                                        read_end.data_ptr(), mask_base.data_ptr(), mask_count.data_ptr(), intervals.data_ptr(), n,
                                        max_len, records.data_ptr(), heads.data_ptr(), ops.data_ptr(), pitch, ctypes.c_void_p(s)),

@@ -128,7 +128,7 @@ struct pc_ctx {
     std::vector<int64_t> slow_ad_off;        // offsets of the adapters' Dna5 codes in d_slow_ad
     DevBuf d_slow_ad, d_slow_state, d_slow_trace;
     DevBuf d_paths_trace;                    // pc_align_paths: the packed trace of one launch (pc_paths.hip)
-    DevBuf d_middle_paths_trace;             // pc_middle_paths: the same for its windows (pc_middle_paths.hip)
+    DevBuf d_middle_paths_trace;             // pc_middle_paths: the same for its windows, a buffer of its own
     std::vector<int32_t> last_job_adapter, last_job_adapter_b;
     std::vector<int64_t> last_job_start;
     int last_max_len = -1, last_mode = -1;
@@ -954,60 +954,17 @@ int pc_debug_value_range(pc_ctx *c, int32_t *lo, int32_t *hi)
     return PC_OK;
 }
 
-// trace scratch one launch of the path kernel may take, unless PC_PATHS_SCRATCH_MB says otherwise
-constexpr size_t kPathsScratchMB = 256;
-
-int pc_align_paths(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
-                   const int32_t *d_adapter_idx, int64_t n, int max_len, int32_t *d_records, int32_t *d_heads,
-                   uint32_t *d_ops, int64_t ops_pitch_words, void *stream_v)
-{
-    if (!c || n < 0 || max_len < 0 || ops_pitch_words < 0) return PC_ERR_BAD_ARG;
-    (void)hipSetDevice(c->device);
-    int rc = upload_panel(c);
-    if (rc) return rc;
-    int rows = 1;
-    for (int len : c->ad_len) {
-        if (len > pcb::MAX_ADAPTER) return PC_ERR_BAD_ARG;          // the code table holds 128 bases per adapter
-        rows = std::max(rows, len);
-    }
-    if (ops_pitch_words < pcpath::ops_words(max_len, c->adapters.empty() ? 0 : rows)) return PC_ERR_BAD_ARG;
-    if (n == 0) return PC_OK;
-    if (!d_arena || !d_win_off || !d_win_len || !d_adapter_idx || !d_records || !d_heads || !d_ops) return PC_ERR_BAD_ARG;
-    if (!pcs::fits(max_len, rows, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
-        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
-                c->match, c->mismatch, c->gap_open, c->gap_extend, max_len, rows);
-        return PC_ERR_UNSUPPORTED_SCORES;
-    }
-    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
-    // the budget is read per call (tests force several slices with a few hundred pairs)
-    size_t budget = kPathsScratchMB << 20;
-    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
-    const int groups = pcpath::row_groups(rows);
-    const size_t per_pair = (size_t)std::max(1, max_len) * (size_t)groups * 4;
-    const int64_t P = pcn::slice_pairs(budget, per_pair, n);
-    if ((rc = c->d_paths_trace.ensure((size_t)P * per_pair + 256))) return rc;
-    pck::PathArgs a;
-    memset(&a, 0, sizeof a);
-    a.arena = (const uint8_t *)d_arena; a.win_off = d_win_off; a.win_len = d_win_len; a.adapter_idx = d_adapter_idx;
-    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
-    a.rows = rows; a.groups = groups; a.max_len = max_len;
-    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
-    a.records = d_records; a.heads = d_heads; a.ops = d_ops; a.ops_pitch = ops_pitch_words;
-    a.trace = c->d_paths_trace.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
-    for (int64_t first = 0; first < n; first += P) {
-        a.first = first; a.count = std::min<int64_t>(P, n - first);
-        if (pck::launch_paths(a, stream)) return PC_ERR_NO_DEVICE;
-    }
-    return PC_OK;
-}
-
 namespace {
 
-// pc_middle_paths: the table's longest adapter (LDS rows) and the widest window a hit can have -- min(max_len, the largest
-// window + W of the table), max_len as soon as one adapter takes the whole read (ad_window 0: compute_bounds refused)
-int middle_paths_shape(pc_ctx *c, int max_len, int &rows, int &cols)
+// trace scratch one launch of a path kernel may take, unless PC_PATHS_SCRATCH_MB says otherwise
+constexpr size_t kPathsScratchMB = 256;
+
+// rows: the table's longest adapter (the LDS rows of both path kernels).  cols: the widest window a MIDDLE hit can have
+// over reads of up to max_len bases -- min(max_len, the largest window + W of the table), max_len as soon as one adapter
+// takes the whole read (ad_window 0: compute_bounds refused)
+int paths_shape(pc_ctx *c, int max_len, int &rows, int &cols)
 {
-    int rc = upload_panel(c);
+    const int rc = upload_panel(c);
     if (rc) return rc;
     rows = 1;
     int64_t widest = 0;
@@ -1021,14 +978,62 @@ int middle_paths_shape(pc_ctx *c, int max_len, int &rows, int &cols)
     return PC_OK;
 }
 
+// What pc_align_paths and pc_middle_paths do alike once their own argument checks have passed, for n alignments of up to
+// cols columns and rows rows: refuse what leaves int32, size a launch's slice P from the scratch budget (read per call:
+// tests force several slices with a few hundred alignments), make `scratch` hold it, fill what `a` takes from the context.
+int paths_setup(pc_ctx *c, int cols, int rows, int max_len, int64_t n, DevBuf &scratch, pck::PathArgs &a)
+{
+    if (!pcs::fits(cols, rows, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
+        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
+                c->match, c->mismatch, c->gap_open, c->gap_extend, cols, rows);
+        return PC_ERR_UNSUPPORTED_SCORES;
+    }
+    size_t budget = kPathsScratchMB << 20;
+    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
+    const int groups = pcpath::row_groups(rows);
+    const size_t per_lane = (size_t)std::max(1, cols) * (size_t)groups * 4;
+    const int64_t P = pcn::slice_pairs(budget, per_lane, n);
+    const int rc = scratch.ensure((size_t)P * per_lane + 256);
+    if (rc) return rc;
+    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
+    a.rows = rows; a.groups = groups; a.max_len = max_len;
+    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
+    a.trace = scratch.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
+    return PC_OK;
+}
+
 }  // namespace
+
+int pc_align_paths(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                   const int32_t *d_adapter_idx, int64_t n, int max_len, int32_t *d_records, int32_t *d_heads,
+                   uint32_t *d_ops, int64_t ops_pitch_words, void *stream_v)
+{
+    if (!c || n < 0 || max_len < 0 || ops_pitch_words < 0) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rows, middle_cols;
+    int rc = paths_shape(c, max_len, rows, middle_cols);
+    if (rc) return rc;
+    if (ops_pitch_words < pcpath::ops_words(max_len, c->adapters.empty() ? 0 : rows)) return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !d_adapter_idx || !d_records || !d_heads || !d_ops) return PC_ERR_BAD_ARG;
+    pck::PathArgs a{};
+    if ((rc = paths_setup(c, max_len, rows, max_len, n, c->d_paths_trace, a))) return rc;
+    a.arena = (const uint8_t *)d_arena; a.seq_off = d_win_off; a.seq_len = d_win_len; a.adapter_idx = d_adapter_idx;
+    a.records = d_records; a.heads = d_heads; a.ops = d_ops; a.ops_pitch = ops_pitch_words;
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    for (int64_t first = 0; first < n; first += a.P) {
+        a.first = first; a.count = std::min<int64_t>(a.P, n - first);
+        if (pck::launch_paths(a, stream)) return PC_ERR_NO_DEVICE;
+    }
+    return PC_OK;
+}
 
 int pc_middle_paths_cols(pc_ctx *c, int max_len)
 {
     if (!c || max_len < 0) return PC_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     int rows, cols;
-    const int rc = middle_paths_shape(c, max_len, rows, cols);
+    const int rc = paths_shape(c, max_len, rows, cols);
     return rc ? rc : cols;
 }
 
@@ -1040,37 +1045,21 @@ int pc_middle_paths(pc_ctx *c, const void *d_arena, const int64_t *d_read_off, c
     if (!c || n < 0 || max_len < 0 || ops_pitch_words < 0) return PC_ERR_BAD_ARG;
     (void)hipSetDevice(c->device);
     int rows, cols;
-    int rc = middle_paths_shape(c, max_len, rows, cols);
+    int rc = paths_shape(c, max_len, rows, cols);
     if (rc) return rc;
     if (ops_pitch_words < pcpath::ops_words(cols, c->adapters.empty() ? 0 : rows)) return PC_ERR_BAD_ARG;
     if (n == 0) return PC_OK;
     if (!d_arena || !d_read_off || !d_read_len || !d_adapter_idx || !d_read_end || !d_mask_base || !d_mask_count ||
         !d_intervals || !d_records || !d_heads || !d_ops) return PC_ERR_BAD_ARG;
-    if (!pcs::fits(cols, rows, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
-        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
-                c->match, c->mismatch, c->gap_open, c->gap_extend, cols, rows);
-        return PC_ERR_UNSUPPORTED_SCORES;
-    }
-    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
-    // pc_align_paths' rule: the same budget, read per call
-    size_t budget = kPathsScratchMB << 20;
-    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
-    const int groups = pcpath::row_groups(rows);
-    const size_t per_hit = (size_t)std::max(1, cols) * (size_t)groups * 4;
-    const int64_t P = pcn::slice_pairs(budget, per_hit, n);
-    if ((rc = c->d_middle_paths_trace.ensure((size_t)P * per_hit + 256))) return rc;
-    pck::MiddlePathArgs a;
-    memset(&a, 0, sizeof a);
-    a.arena = (const uint8_t *)d_arena; a.read_off = d_read_off; a.read_len = d_read_len; a.adapter_idx = d_adapter_idx;
+    pck::MiddlePathArgs a{};
+    if ((rc = paths_setup(c, cols, rows, max_len, n, c->d_middle_paths_trace, a))) return rc;
+    a.arena = (const uint8_t *)d_arena; a.seq_off = d_read_off; a.seq_len = d_read_len; a.adapter_idx = d_adapter_idx;
     a.read_end = d_read_end; a.mask_base = d_mask_base; a.mask_count = d_mask_count; a.intervals = d_intervals; a.n = n;
-    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>();
-    a.ad_window = c->d_ad_window.as<int32_t>(); a.ad_span = c->d_ad_span.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
-    a.rows = rows; a.groups = groups; a.max_len = max_len; a.max_cols = cols;
-    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
     a.records = d_records; a.heads = d_heads; a.ops = d_ops; a.ops_pitch = ops_pitch_words;
-    a.trace = c->d_middle_paths_trace.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
-    for (int64_t first = 0; first < n; first += P) {
-        a.first = first; a.count = std::min<int64_t>(P, n - first);
+    a.ad_window = c->d_ad_window.as<int32_t>(); a.ad_span = c->d_ad_span.as<int32_t>(); a.max_cols = cols;
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    for (int64_t first = 0; first < n; first += a.P) {
+        a.first = first; a.count = std::min<int64_t>(a.P, n - first);
         if (pck::launch_middle_paths(a, stream)) return PC_ERR_NO_DEVICE;
     }
     return PC_OK;

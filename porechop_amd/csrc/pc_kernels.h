@@ -391,12 +391,14 @@ struct SlowArgs {
 };
 int launch_slow(const SlowArgs &a, void *stream);
 
-// the path kernel of pc_paths.hip: pairs first .. first + count of the caller's arrays, each lane its own adapter of the
-// context's code table; records / heads / ops are indexed by the pair of the CALL, the trace scratch by the pair of the launch
+// the two path kernels of pc_paths.hip, one lane per alignment, each lane its own adapter of the context's code table.
+// path_kernel: (window, adapter) pairs first .. first + count of the caller's arrays; records / heads / ops are indexed by
+// the pair of the CALL, the trace scratch by the pair of the launch.  (The field order is a measured one: another cost
+// path_kernel 2 %, profiles/paths_one_cell_before_after.txt.)
 struct PathArgs {
     const uint8_t *arena;
-    const int64_t *win_off;
-    const int32_t *win_len;
+    const int64_t *seq_off;      // [n] first byte of the lane's sequence: a window, or (middle hits) a trimmed read
+    const int32_t *seq_len;      // [n] its bases
     const int32_t *adapter_idx;
     int64_t first, count;
     const uint32_t *ad_codes;    // [nadapters][kMaxRows] Dna5 codes
@@ -409,42 +411,23 @@ struct PathArgs {
     int32_t *heads;              // [n][4]
     uint32_t *ops;               // [n][ops_pitch]
     int64_t ops_pitch;
-    uint32_t *trace;             // [max_len][groups][P] dwords
-    int64_t P;                   // pairs of a launch (stride of the scratch)
+    uint32_t *trace;             // [max_len, or (middle hits) max_cols][groups][P] dwords
+    int64_t P;                   // alignments of a launch (stride of the scratch)
     uint32_t *err;
 };
 int launch_paths(const PathArgs &a, void *stream);
 
-// the middle-hit path kernel of pc_middle_paths.hip: hits first .. first + count of the caller's arrays, each lane its own
-// adapter, its own window of its trimmed read and its own run of the interval table; outputs are indexed by the hit of the
-// CALL, the trace scratch by the hit of the launch
-struct MiddlePathArgs {
-    const uint8_t *arena;
-    const int64_t *read_off;     // [n] the trimmed read's first byte
-    const int32_t *read_len;     // [n] its bases
-    const int32_t *adapter_idx;
+// middle_path_kernel: the same for middle hits, each lane its own window of its trimmed read and its own run of the
+// interval table
+struct MiddlePathArgs : PathArgs {
     const int32_t *read_end;     // [n] the hit's exclusive read end, trimmed-read coordinates
     const int64_t *mask_base;    // [n] first row of the hit's earlier intervals in `intervals`
     const int32_t *mask_count;   // [n] how many
     const int32_t *intervals;    // [n][2] {start, end (exclusive)}, trimmed-read coordinates
     int64_t n;                   // hits of the call (rows of `intervals`)
-    int64_t first, count;
-    const uint32_t *ad_codes;    // [nadapters][kMaxRows] Dna5 codes
-    const int32_t *ad_len;       // [nadapters]
     const int32_t *ad_window;    // [nadapters] pcb::Bounds::window, 0 where compute_bounds refuses
     const int32_t *ad_span;      // [nadapters] pcb::Bounds::SPAN
-    int32_t nadapters;
-    int32_t rows, groups;        // longest adapter of the table (LDS rows) and its row groups of eight (scratch)
-    int32_t max_len;
     int32_t max_cols;            // columns of the scratch: the widest window any hit of the call can have
-    int32_t match, mismatch, gap_open, gap_extend;
-    int32_t *records;            // [n][8]
-    int32_t *heads;              // [n][4]
-    uint32_t *ops;               // [n][ops_pitch]
-    int64_t ops_pitch;
-    uint32_t *trace;             // [max_cols][groups][P] dwords
-    int64_t P;                   // hits of a launch (stride of the scratch)
-    uint32_t *err;
 };
 int launch_middle_paths(const MiddlePathArgs &a, void *stream);
 

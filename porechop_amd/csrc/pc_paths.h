@@ -1,11 +1,12 @@
 // pc_paths.h -- one alignment in plain int32 coordinates that hands back its PATH: the digest every kernel of this
-// library writes, a four-int head and the path's operations, two bits each.  Written once for device (pc_paths.hip:
-// one lane per pair) and host (tests/host/test_paths.cpp replays every path base by base against the oracle).
+// library writes, a four-int head and the path's operations, two bits each -- over the whole read (align_path) or over a
+// window of its columns (align_path_window, the one DP-plus-walk body; pc_middle_paths.h says which window).  Written
+// once for device (pc_paths.hip: one lane per pair or hit) and host (tests/host/test_paths.cpp replays every path base
+// by base against the oracle; tests/host/test_middle_paths.cpp compares every windowed result with align_path over the
+// whole, explicitly masked read).
 //
-// The recurrence, tie rules, scout order and _correctTraceValue are those of pcs::align_pair (pc_slow.h), restated:
-// SURVEY.md 8a-2..a-4 read literally (seqan/align/dp_formula_affine.h:456-495, dp_formula_linear.h:150-182,
-// dp_scout.h:165-179, dp_algorithm_impl.h:1352-1369).  Affine when gap_open != gap_extend, the reference's linear-gap
-// dispatch otherwise (global_alignment_unbanded.h:217-220).  The traceback and the digest ARE pc_walk.h.
+// The cell, the scout and _correctTraceValue are pc_cell.h, the copy pcs::align_pair (pc_slow.h) uses too; the
+// traceback and the digest ARE pc_walk.h.
 //
 // What differs from pc_slow.h is the trace and what the walk leaves behind:
 //   * the pc_walk.h nibble is kept PACKED, eight adapter rows to a dword: row i sits in bits 4 ((i - 1) % 8) of the
@@ -21,16 +22,25 @@
 //
 // head = {path_len, read_first, adapter_first, opens}: steps of the path, read bases before it (the walk's a), adapter
 // bases before it (b; a or b is 0), gap steps that opened their gap (Walk::nopen).
+//
+// THE WINDOW.  align_path_window runs the DP over global columns c0 + 1 .. c1 of a read of n bases (pc_middle_paths.h says
+// which window a middle hit gets, and why the result is exact):
+//   start state c0 == 0: the reference's (M(i) = 0, H(i) = -inf).  c0 > 0: the lower-bound state of pc_bounds.h, a row-0
+//               start followed by a vertical gap: M(i) = gap_open + (i - 1) * gap_extend, H(i) = -inf (with
+//               gap_open == gap_extend that is the linear dispatch's i * gap).
+//   scout       the reference's visiting order and strict '>', from (0 at (m, c0)).  The cells of the window's last column
+//               are candidates only when that column is the read's last (c1 == n); last-row cells always are.  The end
+//               cell is not forced.
+// The walk is pcw::Walk with col0 = c0 and n_total = n: the record and head[1] (= c0 + its local column) are in the read's
+// coordinates, local columns 1 .. c1 - c0 index the trace, and "left the window" stays an error.
 #pragma once
-#include <limits.h>
 #include <stddef.h>
 #include <stdint.h>
 
-#include "pc_walk.h"
+#include "pc_cell.h"
 
 namespace pcpath {
 
-constexpr int NEG_INF = INT_MIN / 2;        // seqan/align/dp_cell.h:116-124
 enum : int { OP_EQ = 0, OP_X = 1, OP_I = 2, OP_D = 3 };
 constexpr int ROWS_PER_WORD = 8, OPS_PER_WORD = 16;
 
@@ -39,78 +49,54 @@ PC_HD int row_groups(int m) { return (m + ROWS_PER_WORD - 1) / ROWS_PER_WORD; }
 PC_HD int64_t ops_words(int64_t n, int64_t m) { return (n + m + OPS_PER_WORD - 1) / OPS_PER_WORD; }
 
 // Mem:  int &M(int i), int &H(int i)              for adapter rows i = 1..m (the column state)
-//       void put(int j, int g, uint32_t word)     the packed trace of column j = 1..n, row group g = 0..row_groups(m)-1
-//       uint32_t get(int j, int g)
-// rd(k) / ad(k): Dna5 code of the k-th (0-based) read / adapter base.
+//       void put(int j, int g, uint32_t word)     the packed trace of LOCAL column j = 1 .. c1 - c0, row group
+//       uint32_t get(int j, int g)                g = 0 .. row_groups(m) - 1
+// rd(k): Dna5 code of the k-th (0-based, GLOBAL) base of the (masked) read; only k in [c0, c1) is asked for.
+// ad(k): Dna5 code of the k-th (0-based) adapter base.
 // sink(k, word): the k-th dword of operations; each is handed out when full, the last (partial) one at the end.
-// -> 0, or 1 if the walk reported an inconsistency or did not end within n + m + 8 steps (never expected).
-// n or m == 0: the reference's failure record, a zero head, no operations.
+// -> 0, or 1 if the walk reported an inconsistency (leaving the window included) or did not end within c1 - c0 + m + 8
+// steps (never expected).  n or m == 0, or an empty window: the reference's failure record, a zero head, no operations.
 template <typename Mem, typename RdFn, typename AdFn, typename Sink>
-PC_HD int align_path(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
-                     pcw::Digest &out, int32_t head[4], Sink sink)
+PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int match, int mismatch, int gap_open,
+                            int gap_extend, Mem mem, pcw::Digest &out, int32_t head[4], Sink sink)
 {
     head[0] = 0; head[1] = 0; head[2] = 0; head[3] = 0;
-    if (n <= 0 || m <= 0) {                   // alignment.cpp:9-21: only field 0 and the score are defined
-        out.read_start = -1; out.read_end = 0; out.adapter_start = -1; out.adapter_end = 0; out.score = INT_MIN;
-        out.matches = 0; out.aligned_len = 0; out.full_len = 0;
-        return 0;
-    }
-    const bool linear = gap_open == gap_extend;        // global_alignment_unbanded.h:217-220
-    for (int i = 1; i <= m; ++i) { mem.M(i) = 0; mem.H(i) = NEG_INF; }
-    int bestM = 0, bestH = NEG_INF, bestV = NEG_INF, bestI = m, bestJ = 0;
-    for (int j = 1; j <= n; ++j) {
-        int diag = 0, upM = 0, upV = NEG_INF;          // row 0: M = 0, V = -inf
-        const int h = rd(j - 1);
-        const bool last_col = j == n;
+    const int nc = c1 - c0;
+    if (n <= 0 || m <= 0 || nc <= 0) { pcc::failure_record(out); return 0; }
+    const bool linear = gap_open == gap_extend;
+    if (c0 == 0) for (int i = 1; i <= m; ++i) { mem.M(i) = 0; mem.H(i) = pcc::NEG_INF; }
+    else for (int i = 1; i <= m; ++i) { mem.M(i) = gap_open + (i - 1) * gap_extend; mem.H(i) = pcc::NEG_INF; }
+    const bool last_is_reads = c1 == n;
+    pcc::Scout best;
+    best.start(m);
+    for (int j = 1; j <= nc; ++j) {
+        int diag = 0, upM = 0, upV = pcc::NEG_INF;     // row 0: M = 0, V = -inf
+        const int h = rd(c0 + j - 1);
+        const bool last_col = last_is_reads && j == nc;
         uint32_t word = 0;
         for (int i = 1; i <= m; ++i) {
             const int Mi = mem.M(i);
             const int sub = (h == ad(i - 1)) ? match : mismatch;
-            int S, Hs = NEG_INF, Vs = NEG_INF, nib;
-            if (linear) {
-                // strict '<' against vertical, then against horizontal: ties prefer diagonal, then vertical; every
-                // gap step is a step of its own (both open bits set: pc_walk.h then never runs a gap)
-                S = diag + sub; nib = pcw::NIB_HOPEN | pcw::NIB_VOPEN;
-                int t = upM + gap_extend;
-                if (S < t) { S = t; nib |= pcw::NIB_NOTDIAG; }
-                t = Mi + gap_extend;
-                if (S < t) { S = t; nib |= pcw::NIB_NOTDIAG | pcw::NIB_FROMH; }
-            } else {
-                nib = 0;
-                Hs = mem.H(i) + gap_extend;
-                int t = Mi + gap_open;
-                if (Hs < t) { Hs = t; nib |= pcw::NIB_HOPEN; }
-                Vs = upV + gap_extend;
-                t = upM + gap_open;
-                if (Vs < t) { Vs = t; nib |= pcw::NIB_VOPEN; }
-                S = Vs;
-                if (S < Hs) { S = Hs; nib |= pcw::NIB_FROMH; }
-                const int d = diag + sub;
-                if (S <= d) S = d; else nib |= pcw::NIB_NOTDIAG;
-                mem.H(i) = Hs;
-            }
+            const pcc::Cell c = pcc::cell(linear, diag, sub, upM, upV, Mi, mem.H(i), gap_open, gap_extend);
             diag = Mi;
-            mem.M(i) = S;
-            upM = S; upV = Vs;
+            mem.M(i) = c.S;
+            upM = c.S; upV = c.Vs;
             const int slot = (i - 1) & (ROWS_PER_WORD - 1);
-            word |= (uint32_t)nib << (4 * slot);
+            word |= (uint32_t)c.nib << (4 * slot);
             if (slot == ROWS_PER_WORD - 1 || i == m) { mem.put(j, (i - 1) / ROWS_PER_WORD, word); word = 0; }
-            if ((last_col || i == m) && S > bestM) { bestM = S; bestH = Hs; bestV = Vs; bestI = i; bestJ = j; }
+            if (last_col || i == m) best.offer(c, i, j);
         }
     }
-    // _correctTraceValue (affine only; at (m, 0) H = V = -inf != M)
-    int tie_fix = 0;
-    if (!linear) tie_fix = (bestV == bestM) ? 1 : (bestH == bestM) ? 2 : 0;
     pcw::Walk w;
-    w.start(bestI, bestJ, m, 0, n, bestM, tie_fix);
-    const int cap = n + m + 8;                         // a path has at most n + m steps: a corrupted trace ends here
+    w.start(best.I, best.J, m, c0, n, best.M, best.tie_fix(linear));
+    const int cap = nc + m + 8;                        // a path has at most nc + m steps: a corrupted trace ends here
     int overrun = 0, k = 0;
     uint32_t acc = 0;
     while (!w.done) {
         if (k >= cap) { overrun = 1; break; }
         const int c = w.col, r = w.row;
         const int nib = (int)(mem.get(c, (r - 1) / ROWS_PER_WORD) >> (4 * ((r - 1) & (ROWS_PER_WORD - 1)))) & 15;
-        const bool eq = rd(c - 1) == ad(r - 1);
+        const bool eq = rd(c0 + c - 1) == ad(r - 1);
         w.consume(nib, eq);
         const bool dcol = w.col != c, drow = w.row != r;
         const uint32_t op = (dcol && drow) ? (eq ? OP_EQ : OP_X) : (drow ? OP_D : OP_I);
@@ -120,8 +106,20 @@ PC_HD int align_path(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, in
     }
     if (k & (OPS_PER_WORD - 1)) sink(k / OPS_PER_WORD, acc);
     const int err = w.finish_counted(out) | overrun;
-    head[0] = w.nsteps; head[1] = w.col; head[2] = w.row; head[3] = w.nopen;
+    head[0] = w.nsteps; head[1] = c0 + w.col; head[2] = w.row; head[3] = w.nopen;
     return err;
+}
+
+// The alignment against the WHOLE read: the window c0 = 0, c1 = n.  With c0 = 0 the start state is the reference's
+// (M(i) = 0, H(i) = -inf), the window's last column is the read's, so its cells are scout candidates as in the
+// reference, and head[1] = w.col: every one of the window's differences vanishes, and what is left is the recurrence of
+// pcs::align_pair with a packed trace (tests/host/test_paths.cpp holds the three to one another on every case).
+// n or m == 0: the reference's failure record, a zero head, no operations.
+template <typename Mem, typename RdFn, typename AdFn, typename Sink>
+PC_HD int align_path(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
+                     pcw::Digest &out, int32_t head[4], Sink sink)
+{
+    return align_path_window(n, m, 0, n, rd, ad, match, mismatch, gap_open, gap_extend, mem, out, head, sink);
 }
 
 // (ops, path_len) -> the FORWARD run-length string ("17=1X4=2I6="), NUL-terminated when it fits.  -> the length it

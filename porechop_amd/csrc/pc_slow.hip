@@ -18,16 +18,6 @@ namespace pck {
 
 namespace {
 
-__device__ __forceinline__ int code_of(uint8_t c)
-{
-    // seqan/basic/alphabet_residue_tabs.h:113-140
-    if (c == 'A' || c == 'a') return 0;
-    if (c == 'C' || c == 'c') return 1;
-    if (c == 'G' || c == 'g') return 2;
-    if (c == 'T' || c == 't' || c == 'U' || c == 'u') return 3;
-    return 4;
-}
-
 struct LdsMem {
     int *st; int m, lane; uint8_t *tr; int64_t P, p;
     __device__ __forceinline__ int &M(int i) { return st[(i - 1) * 64 + lane]; }
@@ -60,7 +50,7 @@ __global__ __launch_bounds__(64) void slow_kernel(SlowArgs a)
     const uint8_t *ad = a.adapter;            // Dna5 codes already
     pcw::Digest d;
     int err;
-    auto rdf = [&](int k) { return code_of(rd[k]); };
+    auto rdf = [&](int k) { return pcc::dna5_code(rd[k]); };
     auto adf = [&](int k) { return (int)ad[k]; };
     if constexpr (LDS)
         err = pcs::align_pair(n, a.m, rdf, adf, a.match, a.mismatch, a.gap_open, a.gap_extend,

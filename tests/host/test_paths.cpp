@@ -7,18 +7,22 @@
 // inside the rectangle with every '=' on equal and every 'X' on unequal Dna5 codes; (c) the replay ends in the last row
 // or column, at the oracle's end cell; (d) head + path + tail is the oracle's path length; (e) the path starts in row 0
 // or column 0; (f) the operations realise the score; (g) the digest recomputed from the gapped rows H^a V^b P H^c V^d by
-// alignment.cpp's rule is the function's own; (h) the run-length formatter round-trips.
+// alignment.cpp's rule is the function's own; (h) the run-length formatter round-trips; (i) pcs::align_pair (pc_slow.h)
+// gives the same eight digest fields, and align_path_window(n, m, 0, n, ...) called directly the same digest, head and
+// operation words: the three routines over the one cell of pc_cell.h agree on every case.
 //
 //   g++ -O2 -std=c++17 -I porechop_amd/csrc -I oracle tests/host/test_paths.cpp oracle/pc_oracle.o
 //   ./a.out [cases [seed [dump]]]
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <string>
 #include <vector>
 
 #include "pc_paths.h"
+#include "pc_slow.h"
 extern "C" {
 #include "pc_oracle.h"
 }
@@ -35,6 +39,20 @@ struct Mem {
     void put(int j, int g, uint32_t w) { (*t).at((size_t)j * groups + g) = w; }
     uint32_t get(int j, int g) { return (*t).at((size_t)j * groups + g); }
 };
+
+struct SlowMem {                        // pc_slow.h's policy: one trace byte per cell
+    std::vector<int> *m, *h; std::vector<uint8_t> *t; int rows;
+    int &M(int i) { return (*m)[i]; }
+    int &H(int i) { return (*h)[i]; }
+    uint8_t &T(int j, int i) { return (*t).at((size_t)j * (rows + 1) + i); }
+};
+
+static bool same_digest(const pcw::Digest &a, const pcw::Digest &b)
+{
+    return a.read_start == b.read_start && a.read_end == b.read_end && a.adapter_start == b.adapter_start &&
+           a.adapter_end == b.adapter_end && a.score == b.score && a.matches == b.matches && a.aligned_len == b.aligned_len &&
+           a.full_len == b.full_len;
+}
 
 // alignment.cpp:6-111 over two gapped rows, as the oracle applies it (start / end = first / last column by which both rows
 // have shown a base; identities over [start, end] and over the adapter's span)
@@ -69,7 +87,7 @@ int main(int argc, char **argv)
     const long cases = argc > 1 ? atol(argv[1]) : 30000;
     std::mt19937_64 rng(argc > 2 ? atol(argv[2]) : 12345);
     auto pick = [&](int lo, int hi) { return lo + (int)(rng() % (uint64_t)(hi - lo + 1)); };
-    long done = 0, bad = 0, linear = 0, posgap = 0, gapped = 0, empty_path = 0, open_above = 0, groups_seen[5] = {0, 0, 0, 0, 0};
+    long done = 0, bad = 0, one_cell = 0, linear = 0, posgap = 0, gapped = 0, empty_path = 0, open_above = 0, groups_seen[5] = {0, 0, 0, 0, 0};
     const bool dump = argc > 3;          // a third argument: one line per case for tests/pathcheck.py ('.' = empty string)
     const char *letters = "ACGTACGTACGTACGTNacgtU-X";
     static const char LET[5] = {'A', 'C', 'G', 'T', 'N'};
@@ -92,10 +110,7 @@ int main(int argc, char **argv)
             const int s = pick(0, n - m);
             for (int k = 0; k < m; ++k) ad[k] = pick(0, 99) < 15 ? "ACGTN"[pick(0, 4)] : rd[s + k];
         } else for (char &c : ad) c = "ACGT"[pick(0, 3)];
-        // (pcs::fits, restated: pc_slow.h is not this header's)
-        long long mx = 0;
-        for (int x : sc) mx = std::max<long long>(mx, x < 0 ? -(long long)x : x);
-        if (!(mx <= (1 << 20) && m <= 4096 && ((long long)n + m + 2) * mx < (1ll << 30))) continue;
+        if (!pcs::fits(n, m, sc[0], sc[1], sc[2], sc[3])) continue;
         pc_oracle_result R;
         if (pc_oracle_align_raw(rd.c_str(), n, ad.c_str(), m, sc[0], sc[1], sc[2], sc[3], &R) != 0) continue;
         ++done;
@@ -114,6 +129,23 @@ int main(int argc, char **argv)
                                                if (k != next_word || k >= pcpath::ops_words(n, m)) sink_bad = 1; else ops[k] = w;
                                                ++next_word;
                                            });
+        // (i) the same pair through the other two entrances of the one cell
+        const char *why_one = nullptr;
+        {
+            std::vector<int> M2(m + 1), H2(m + 1);
+            std::vector<uint8_t> T2((size_t)(n + 1) * (m + 1), 0xff);
+            pcw::Digest ds;
+            if (pcs::align_pair(n, m, rdf, adf, sc[0], sc[1], sc[2], sc[3], SlowMem{&M2, &H2, &T2, m}, ds) != err || !same_digest(ds, d))
+                why_one = "(i) pcs::align_pair != align_path";
+            std::vector<uint32_t> T3(T.size(), 0xffffffffu), ops3(ops.size(), 0u);
+            pcw::Digest dw;
+            int32_t head3[4] = {-1, -1, -1, -1};
+            const int errw = pcpath::align_path_window(n, m, 0, n, rdf, adf, sc[0], sc[1], sc[2], sc[3], Mem{&M2, &H2, &T3, groups}, dw,
+                                                       head3, [&](int k, uint32_t w) { ops3.at(k) = w; });
+            if (errw != err || !same_digest(dw, d) || memcmp(head3, head, sizeof head) || ops3 != ops)
+                why_one = "(i) align_path_window(0, n) != align_path";
+        }
+        one_cell += why_one == nullptr;
         const bool lin = sc[2] == sc[3];
         linear += lin; posgap += sc[2] >= 0 || sc[3] >= 0; open_above += sc[2] > sc[3];
         const int watched[5] = {1, 7, 8, 9, 17};
@@ -133,6 +165,7 @@ int main(int argc, char **argv)
                     d.adapter_end == R.adapter_end && d.score == R.score && d.matches == R.aligned_matches &&
                     d.matches == R.full_matches && d.aligned_len == R.aligned_len && d.full_len == R.full_len;
         if (err) why = "err";
+        else if (why_one) why = why_one;
         else if (sink_bad) why = "sink order / bound";
         else if (!same) why = "(a) digest != oracle";
         else if (n == 0 || m == 0) {
@@ -210,7 +243,7 @@ int main(int argc, char **argv)
                    d.score, d.matches, d.aligned_len, d.full_len, head[0], head[1], head[2], head[3], R.read_start, R.read_end, R.adapter_start,
                    R.adapter_end, R.score, R.aligned_matches, R.full_matches, R.aligned_len, R.full_len, R.failed, R.end_i, R.end_j, R.path_len);
     }
-    printf("cases=%ld bad=%ld linear=%ld nonnegative_gap=%ld open_above_extend=%ld gapped=%ld empty_path=%ld rows1=%ld rows7=%ld rows8=%ld rows9=%ld rows17=%ld\n",
-           done, bad, linear, posgap, open_above, gapped, empty_path, groups_seen[0], groups_seen[1], groups_seen[2], groups_seen[3], groups_seen[4]);
+    printf("cases=%ld bad=%ld one_cell=%ld linear=%ld nonnegative_gap=%ld open_above_extend=%ld gapped=%ld empty_path=%ld rows1=%ld rows7=%ld rows8=%ld rows9=%ld rows17=%ld\n",
+           done, bad, one_cell, linear, posgap, open_above, gapped, empty_path, groups_seen[0], groups_seen[1], groups_seen[2], groups_seen[3], groups_seen[4]);
     return bad ? 1 : 0;
 }

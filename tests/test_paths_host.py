@@ -1,6 +1,7 @@
 """Compiles porechop_amd/csrc/pc_paths.h for the HOST, with the device's nibble packing as its memory policy, and replays
 every path it returns base by base against the oracle on 30 000 seeded cases of unrestricted schemes
-(tests/host/test_paths.cpp), under ASan and UBSan.  No GPU involved."""
+(tests/host/test_paths.cpp), under ASan and UBSan; the same program holds pcs::align_pair (pc_slow.h) and a direct
+align_path_window(n, m, 0, n, ...) to align_path on every case.  No GPU involved."""
 import os
 import subprocess
 import tempfile
@@ -23,6 +24,8 @@ def test_paths_replayed_on_the_host_against_the_oracle():
         keys = ("cases", "linear", "nonnegative_gap", "open_above_extend", "gapped", "empty_path", "rows1", "rows7", "rows8", "rows9", "rows17")
         count = {k: int(out.stdout.split(k + "=")[1].split()[0]) for k in keys}
         assert count["cases"] == 30000
+        # every case also went through pcs::align_pair and align_path_window(0, n) and gave the same answer
+        assert int(out.stdout.split("one_cell=")[1].split()[0]) == 30000
         # no class went unexercised: the linear dispatch, paths with a gap, empty paths, schemes the packed kernels refuse,
         # and adapters whose last row group of the packed trace holds 1, 7, 8, 1 (of 9) and 1 (of 17) rows
         for k in keys[1:]:

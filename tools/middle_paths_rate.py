@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Rate probe (GPU box): the paths of the middle hits of a 100 k x 8 kb batch with 1 % chimeras through
-Pipeline.middle_hit_paths (pc_middle_paths.hip: one lane per hit, a bounded window of the masked read), and that batch's
+Pipeline.middle_hit_paths (middle_path_kernel of pc_paths.hip: one lane per hit, a bounded window of the masked read), and that batch's
 phase_c (the middle scan, whose code the paths do not touch), in one process, timed by device events around each call; medians
 over the repeats, and their ratio.  A record, not a gate: nobody has measured this kernel before.
    python tools/middle_paths_rate.py [n_reads] [repeats]        (default 100 000, 5)"""
