@@ -514,6 +514,27 @@ int pc_kmer_count(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, co
 int pc_kmer_select(pc_ctx *ctx, const uint32_t *d_counts, int k, uint32_t min_count, int32_t *d_codes, uint32_t *d_cnt,
                    int64_t cap, int64_t *d_found, void *stream);
 
+/* Barcode discovery: the bases next to an aligned anchor, one code per window (csrc/pc_discover.hip, insert_code_kernel).
+ * d_records holds the n scan records (PC_RESULT_INTS each, window order) of ONE adapter -- the anchor, anchor_len bases --
+ * against the n windows (d_win_off / d_win_len over d_arena, as for every scan); side 0: start windows, the insert lies
+ * behind the anchor; side 1: end windows, it lies before it.  Window w is ANCHORED iff all of
+ *   rec[0] >= 0                                   (not the "no alignment" record)
+ *   rec[7] > 0
+ *   100 * rec[5] >= min_identity * rec[7]         (matches and full length, integers, products in 64 bits)
+ *   side 0: rec[3] == anchor_len - 1; side 1: rec[2] == 0      (the alignment reaches the anchor's inner edge)
+ * The insert's first column is col = rec[1] + 1 (side 0) or rec[0] - insert_len (side 1); read coordinates in records are
+ * inclusive.  d_codes[w] = the 2-bit code of the window's bytes [col, col + insert_len): the first base in the highest
+ * bits, A C G T/U = 0 1 2 3, either case -- pc_kmer_count's byte -> code function -- when the window is anchored, col >= 0
+ * and col + insert_len <= d_win_len[w]; otherwise, and when any of those bytes is not a base, -1.  (At insert_len = 32
+ * the code fills all 64 bits: an insert that begins with G or T is a negative number, and 32 T's are -1 itself.  Callers
+ * that tell inserts from -1 by sign stay at 31 or below, as discover() does.)  Nothing outside [d_win_off[w],
+ * d_win_off[w] + d_win_len[w]) is read, byte by byte, and every index is formed in 64 bits; windows may overlap, repeat, be
+ * empty and start at any byte.  n = 0 is a no-op.  insert_len outside 1..32, side outside 0..1, min_identity outside
+ * 0..100 or anchor_len < 1 is PC_ERR_BAD_ARG before anything is launched.  No host round trip; asynchronous on `stream`. */
+int pc_anchor_inserts(pc_ctx *ctx, const uint8_t *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                      const int32_t *d_records, int64_t n, int anchor_len, int side, int min_identity, int insert_len,
+                      int64_t *d_codes, void *stream);
+
 /* Debug builds of the 16-bit kernels (PC_CHECK_RANGE=1: packed-fp16 traced kernel, row classes 24/28/30/40;
  * PC_JIT_CHECK_RANGE=1: the run-time specialised score kernel) record the extremes of every DP value they
  * hold, in the kernel's own offset coordinates; this returns them since the last call and resets.  The

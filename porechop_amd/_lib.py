@@ -23,7 +23,7 @@ EXPORTS = [
     "pc_readset_compress", "pc_gzimage_sizes", "pc_gzimage_write", "pc_gzimage_free", "pc_gz_finish", "pc_gzip_file",
     "pc_gzstream_open", "pc_gzstream_next", "pc_gzstream_close", "pc_gz_member_start", "pc_gzstream_open_range", "pc_prefilter_packed", "pc_prefilter_packed_any", "pc_unpack_windows", "pc_prefilter_defer_count", "pc_prefilter_overflowed", "pc_trim_windows", "pc_middle_hits", "pc_group_survivors", "pc_round_consume",
     "pc_gz_sized_size", "pc_gz_sized_find_record", "pc_readset_load_gz_range",
-    "pc_kmer_count", "pc_kmer_select",
+    "pc_kmer_count", "pc_kmer_select", "pc_anchor_inserts",
     "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule",
     "pc_align_paths", "pc_path_cigar",
     "pc_middle_paths", "pc_middle_paths_cols",
@@ -216,6 +216,8 @@ def load_library():
     L.pc_kmer_count.restype = c_int
     L.pc_kmer_select.argtypes = [c_vp, c_vp, c_int, ctypes.c_uint32, c_vp, c_vp, c_i64, c_vp, c_vp]
     L.pc_kmer_select.restype = c_int
+    L.pc_anchor_inserts.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int, c_vp, c_vp]
+    L.pc_anchor_inserts.restype = c_int
     L.pc_unpack_windows.argtypes = [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_vp]
     L.pc_unpack_windows.restype = c_int
     L.pc_readset_compress.argtypes = [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_vp)]

@@ -748,6 +748,25 @@ class Aligner:
         order = np.lexsort((codes, -cnt))
         return codes[order], cnt[order]
 
+    def anchor_inserts(self, arena, win_off, win_len, records, anchor_len, side, min_identity=75, insert_len=24, stream=None):
+        """The insert_len bases right behind (side 0: start windows) or before (side 1: end windows) an anchor's alignment in
+        each of the n windows, as one 2-bit code per window (pc_anchor_inserts: the first base in the highest bits; -1 where the
+        window is not anchored, the insert does not fit the window or holds a byte that is not a base).  records int32[n, 8]:
+        the scan records of the anchor (anchor_len bases) against these windows, window order; arena uint8, win_off int64[n],
+        win_len int32[n]: CUDA tensors.  min_identity 0..100 (an integer: matches * 100 >= min_identity * full length).
+        -> int64 CUDA tensor [n].  Asynchronous."""
+        import torch
+        n = int(win_off.shape[0])
+        assert arena.is_cuda and arena.dtype == torch.uint8 and win_off.dtype == torch.int64 and win_len.dtype == torch.int32
+        assert records.is_cuda and records.dtype == torch.int32 and records.is_contiguous() and int(records.numel()) == n * RESULT_INTS
+        assert win_off.is_contiguous() and win_len.is_contiguous() and int(win_len.shape[0]) == n
+        codes = torch.empty(n, dtype=torch.int64, device=arena.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        check(self.lib.pc_anchor_inserts(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), records.data_ptr(), n,
+                                         int(anchor_len), int(side), int(min_identity), int(insert_len), codes.data_ptr(),
+                                         ctypes.c_void_p(s)), "pc_anchor_inserts")
+        return codes
+
     def debug_value_range(self):
         """(lo, hi) of the DP values the range-checking kernel builds have held since the last call."""
         lo, hi = ctypes.c_int32(), ctypes.c_int32()

@@ -1342,6 +1342,19 @@ int pc_kmer_select(pc_ctx *c, const uint32_t *d_counts, int k, uint32_t min_coun
     return pck::launch_kmer_select(d_counts, k, min_count, d_codes, d_cnt, cap, (unsigned long long *)d_found, stream) ? PC_ERR_NO_DEVICE : PC_OK;
 }
 
+int pc_anchor_inserts(pc_ctx *c, const uint8_t *d_arena, const int64_t *d_win_off, const int32_t *d_win_len, const int32_t *d_records,
+                      int64_t n, int anchor_len, int side, int min_identity, int insert_len, int64_t *d_codes, void *stream_v)
+{
+    if (!c || n < 0 || anchor_len < 1 || side < 0 || side > 1 || min_identity < 0 || min_identity > 100 || insert_len < 1 || insert_len > 32)
+        return PC_ERR_BAD_ARG;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !d_records || !d_codes) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    return pck::launch_anchor_inserts(d_arena, d_win_off, d_win_len, d_records, n, anchor_len, side, min_identity, insert_len, d_codes, stream)
+               ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
 int pc_group_survivors(pc_ctx *c, const int32_t *d_mask, int64_t n, int words, const int32_t *d_gmask, int ngroups, uint8_t *d_cand,
                        int64_t *d_counts, void *stream_v)
 {

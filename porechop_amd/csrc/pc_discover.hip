@@ -22,6 +22,8 @@
 // kmer_select_kernel: the table entries with count >= min_count, appended to a capped list through one cursor.  A wave
 // draws its slots with ONE returning atomic (ballot + popcount), so a threshold that most of a 4^12 table passes costs
 // 260 k cursor updates, not 16 M.  The cursor counts every qualifying entry whether or not it fitted.
+//
+// insert_code_kernel (barcode discovery): the bases behind an aligned anchor as one code per window; described where it stands.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -127,6 +129,49 @@ __global__ __launch_bounds__(256) void kmer_select_kernel(const uint32_t *counts
             if (slot < (unsigned long long)cap) { codes[slot] = (int32_t)c; cnt[slot] = v; }
         }
     }
+}
+
+// insert_code_kernel: barcode discovery ("Barcodes").  The scan has aligned one found sequence (the
+// anchor) against every end window; a window whose record passes the rule below is ANCHORED, and the L bases right behind
+// the anchor (start windows) or before it (end windows) are its insert, returned as one 2-bit code per window -- the
+// census's code, first base in the highest bits.  One thread per window, grid-stride: a 32-byte record and at most 32
+// byte loads, every one inside the window; latency-bound, nothing to stage.  All products and indices are 64-bit.
+__global__ __launch_bounds__(256) void insert_code_kernel(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len,
+                                                          const int32_t *records, int64_t n, int anchor_len, int side, int min_identity,
+                                                          int L, int64_t *codes)
+{
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < n; w += stride) {
+        const int32_t *rec = records + 8 * w;
+        const int64_t read_start = rec[0], read_end = rec[1], ad_start = rec[2], ad_end = rec[3], matches = rec[5], full_len = rec[7];
+        int64_t code = -1;
+        const bool anchored = read_start >= 0 && full_len > 0 && 100 * matches >= (int64_t)min_identity * full_len &&
+                              (side == 0 ? ad_end == (int64_t)anchor_len - 1 : ad_start == 0);
+        const int64_t col = side == 0 ? read_end + 1 : read_start - L;
+        if (anchored && col >= 0 && col + L <= (int64_t)win_len[w]) {
+            const uint8_t *p = arena + win_off[w] + col;
+            uint64_t v = 0;
+            uint32_t bad = 0;
+            for (int i = 0; i < L; ++i) {
+                const uint32_t c = dna5_code(p[i]);
+                bad |= c;
+                v = (v << 2) | (c & 3u);
+            }
+            if (!(bad & 4u)) code = (int64_t)v;
+        }
+        codes[w] = code;
+    }
+}
+
+int launch_anchor_inserts(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len, const int32_t *records, int64_t n,
+                          int anchor_len, int side, int min_identity, int insert_len, int64_t *codes, void *stream)
+{
+    if (n <= 0) return 0;
+    const int64_t want = (n + 255) / 256;
+    const unsigned grid = (unsigned)(want < 8192 ? want : 8192);
+    hipLaunchKernelGGL(insert_code_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, arena, win_off, win_len, records, n, anchor_len,
+                       side, min_identity, insert_len, codes);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_kmer_count(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len, int64_t n, int k, uint32_t *counts, void *stream)

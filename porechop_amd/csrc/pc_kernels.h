@@ -369,6 +369,10 @@ int launch_plan(const PlanArgs &a, void *stream);
 int launch_kmer_count(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len, int64_t n, int k, uint32_t *counts, void *stream);
 int launch_kmer_select(const uint32_t *counts, int k, uint32_t min_count, int32_t *codes, uint32_t *cnt, int64_t cap,
                        unsigned long long *found, void *stream);
+// barcode discovery: the insert_len bases behind (side 0) or before (side 1) an anchor's alignment in every window, as one
+// 2-bit code per window, -1 where the window is not anchored (arguments checked by the caller: pc_anchor_inserts)
+int launch_anchor_inserts(const uint8_t *arena, const int64_t *win_off, const int32_t *win_len, const int32_t *records, int64_t n,
+                          int anchor_len, int side, int min_identity, int insert_len, int64_t *codes, void *stream);
 
 // 2-bit plane (+ exception positions) -> bytes 'A','C','G','T' / 'N', followed by `pad` bytes of 'N' (pc_reduce.hip)
 int launch_unpack(const void *packed, int64_t nbases, const int64_t *exc_pos, int64_t nexc, void *arena, int pad, void *stream);
