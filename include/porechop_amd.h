@@ -535,7 +535,7 @@ int pc_anchor_inserts(pc_ctx *ctx, const uint8_t *d_arena, const int64_t *d_win_
                       const int32_t *d_records, int64_t n, int anchor_len, int side, int min_identity, int insert_len,
                       int64_t *d_codes, void *stream);
 
-/* Debug builds of the 16-bit kernels (PC_CHECK_RANGE=1: packed-fp16 traced kernel, row classes 24/28/30/40;
+/* Debug builds of the 16-bit kernels (PC_CHECK_RANGE=1: packed-fp16 traced kernel, every row class it has;
  * PC_JIT_CHECK_RANGE=1: the run-time specialised score kernel) record the extremes of every DP value they
  * hold, in the kernel's own offset coordinates; this returns them since the last call and resets.  The
  * exactness argument needs |value| <= 2040 in the fp16 kernels and <= 32000 in the int16 ones. */

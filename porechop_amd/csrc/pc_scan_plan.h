@@ -213,7 +213,7 @@ inline int build_table(const Panel &ad, const Params &p, const int32_t *job_adap
     // 24-mers' launch.  Ascending by rows, groups below kSmallTiles are merged into the next larger small group (its rows,
     // padded variant: a shorter adapter sits bottom-aligned under padding rows, as in any tile of two different adapters)
     // until the merged group is large enough; the extra rows are cheap next to an idle chip.  Results do not depend on the
-    // row class a pair runs in (tests/test_gpu_parity.py: ragged / padded classes).
+    // row class a pair runs in (tests/test_gpu_row_classes.py: every class launched alone, against the oracle).
     if (!p.opt.no_merge_small) {
         const int64_t kSmallTiles = 2048;
         std::vector<std::pair<int, int>> keys;

@@ -394,7 +394,7 @@ for (a, b) in [(0, 1), (2, 3), (1, -1)]:
 print("DIGEST", h.hexdigest(), porechop_amd.load_library().pc_trace_ops_x100(al._ctx))
 '''
     outs = []
-    # PC_CHECK_RANGE=1: row classes 24/28/30/40 run the build with the on-device assertion |value| <= 2040
+    # PC_CHECK_RANGE=1: every row class of trace16_kernel runs the build with the on-device assertion |value| <= 2040
     for extra, arg in (({"PC_CHECK_RANGE": "1"}, "check"), ({"PC_DISABLE_F16": "1"}, "nocheck")):
         res = subprocess.run([sys.executable, "-c", code, arg], capture_output=True, text=True, timeout=1200,
                              env=dict(os.environ, **extra), cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
