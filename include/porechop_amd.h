@@ -101,6 +101,11 @@ int pc_scores_supported(int match, int mismatch, int gap_open, int gap_extend, i
 int pc_create(pc_ctx **ctx, int device);
 void pc_destroy(pc_ctx *ctx);
 
+/* The scoring scheme of the calls that follow; may be called on a live context, between any two calls.  Nothing is
+ * uploaded here: a changed scheme only marks the panel dirty, and the NEXT call that needs the panel re-derives all of it
+ * under the new scheme -- the adapters' windows and spans, which adapters take the plain-int32 kernel -- uploads it, and
+ * drops the cached tile table and prefilter plan (it waits for the device first: earlier calls may still read the old
+ * tables).  Magnitudes above 2^20 are refused and leave the scheme as it was. */
 int pc_set_scores(pc_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend);
 
 /* Upload the adapter panel (the strings of porechop/adapters.py ADAPTERS start/end sequences

@@ -155,6 +155,13 @@ class Aligner:
         arr = (ctypes.c_char_p * max(1, len(self.adapters)))(*self.adapters)
         check(self.lib.pc_set_adapters(self._ctx, arr, len(self.adapters)), "pc_set_adapters")
 
+    def set_scores(self, scores):
+        """Replace the scoring scheme (match, mismatch, gap_open, gap_extend) of the live context (pc_set_scores): the
+        adapter table and everything derived from it is worked out again at the next call."""
+        scores = tuple(int(s) for s in scores)
+        check(self.lib.pc_set_scores(self._ctx, *scores), "pc_set_scores")
+        self.scores = scores
+
     def close(self):
         if self._ctx:
             self.lib.pc_destroy(self._ctx)
