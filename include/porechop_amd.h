@@ -179,6 +179,18 @@ int pc_scan_device_end_rule(pc_ctx *ctx, const void *d_arena, const int64_t *d_w
 /* Pairs pc_scan_device_floored or pc_scan_device_end_rule left untraced: in the last such call of this context, and in all of them.  Waits for `stream`.  Either pointer may be NULL. */
 int pc_floor_skipped(pc_ctx *ctx, void *stream, int64_t *last_call, int64_t *total);
 
+/* The score pass of pc_scan_device_floored computes the adapter rows that no alignment reaching its pair's floor can reach
+ * only behind a column that announces such an alignment (csrc/pc_bounds.h, row_skip_plan): records of pairs at or above
+ * their floor, pc_floor_skipped and everything pass 2 sees are what they are without it.  PC_NO_ROW_SKIP=1 in the
+ * environment (read per call) switches it off.  A debug switch, off by default: while it is on, every wave of such a launch
+ * adds, once, two numbers to two counters of the context: the 4-column blocks its fast path ran (`column_pairs`: blocks, the
+ * name is historical) and those among them in which the lower rows were computed.  A stretch of blocks entered from the
+ * one-column path starts with the lower rows on whatever the reads hold; its blocks are counted only from the first one
+ * that triggers or lets that first window run out, so that a tile in which nothing ever triggers counts 0 of n, not W_low / 4
+ * of n per stretch.  pc_row_skip_blocks waits for `stream`, reads the counters (either pointer may be NULL) and clears them. */
+int pc_set_row_skip_debug(pc_ctx *ctx, int enabled);
+int pc_row_skip_blocks(pc_ctx *ctx, void *stream, int64_t *column_pairs, int64_t *lower_rows_on);
+
 /* Alignment PATHS: pair p aligns window [d_win_off[p], + d_win_len[p]) of the arena with adapter d_adapter_idx[p] of the
  * context's table and gets its record (d_records[p][8]), a head (d_heads[p][4]) and the operations of its path
  * (d_ops[p][ops_pitch_words]).  All pointers but `ctx` are device memory; d_records and d_heads are 16-byte aligned.
@@ -573,6 +585,12 @@ void pc_jit_shutdown(void);
  * written, 1 = already there, < 0 = this pair / scheme has no specialised kernel, or the compile or write failed. */
 int pc_jit_precompile(const char *adapter_a, const char *adapter_b, int match, int mismatch, int gap_open,
                       int gap_extend, const char *cache_dir);
+/* The pair's second kernel, which the score pass of pc_scan_device_floored runs where the pair has one: its fast path
+ * computes the adapter rows below a row r0 only where an alignment that reaches the launch's floors can be (see
+ * pc_set_row_skip_debug above).  Same arguments and answers; 2 = the pair has no such kernel (packed int16 lanes, or no
+ * row that would pay). */
+int pc_jit_precompile_row_skip(const char *adapter_a, const char *adapter_b, int match, int mismatch, int gap_open,
+                               int gap_extend, const char *cache_dir);
 /* Kernels this process compiled with hiprtc / took from a kernel cache on disk so far. */
 void pc_jit_stats(int64_t *compiled, int64_t *from_disk);
 

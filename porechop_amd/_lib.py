@@ -24,7 +24,7 @@ EXPORTS = [
     "pc_gzstream_open", "pc_gzstream_next", "pc_gzstream_close", "pc_gz_member_start", "pc_gzstream_open_range", "pc_prefilter_packed", "pc_prefilter_packed_any", "pc_unpack_windows", "pc_prefilter_defer_count", "pc_prefilter_overflowed", "pc_trim_windows", "pc_middle_hits", "pc_group_survivors", "pc_round_consume",
     "pc_gz_sized_size", "pc_gz_sized_find_record", "pc_readset_load_gz_range",
     "pc_kmer_count", "pc_kmer_select", "pc_anchor_inserts",
-    "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule",
+    "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule", "pc_set_row_skip_debug", "pc_row_skip_blocks", "pc_jit_precompile_row_skip",
     "pc_align_paths", "pc_path_cigar",
     "pc_middle_paths", "pc_middle_paths_cols",
 ]
@@ -90,6 +90,10 @@ def load_library():
     L.pc_scan_device_end_rule.restype = c_int
     L.pc_floor_skipped.argtypes = [c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     L.pc_floor_skipped.restype = c_int
+    L.pc_set_row_skip_debug.argtypes = [c_vp, c_int]
+    L.pc_set_row_skip_debug.restype = c_int
+    L.pc_row_skip_blocks.argtypes = [c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
+    L.pc_row_skip_blocks.restype = c_int
     L.pc_align_paths.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_vp, c_i64, c_vp]
     L.pc_align_paths.restype = c_int
     L.pc_path_cigar.argtypes = [c_vp, c_int, c_vp, ctypes.c_size_t]
@@ -139,6 +143,8 @@ def load_library():
     L.pc_jit_shutdown.restype = None
     L.pc_jit_precompile.argtypes = [c_cp, c_cp, c_int, c_int, c_int, c_int, c_cp]
     L.pc_jit_precompile.restype = c_int
+    L.pc_jit_precompile_row_skip.argtypes = L.pc_jit_precompile.argtypes
+    L.pc_jit_precompile_row_skip.restype = c_int
     L.pc_jit_stats.argtypes = [ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
     L.pc_jit_stats.restype = None
     L.pc_prefilter_max_edits.argtypes = [c_int, ctypes.c_double]

@@ -4,7 +4,8 @@ The whole-read score pass runs a kernel specialised for one adapter pair (csrc/p
 constant (porechop/adapters.py:77-463), and the batch pipeline scans the start and end sequence of one adapter set
 in one pass (Pipeline._scan_jobs pairs the jobs of a set), so the kernels a run needs are known when the library is
 built: one per set.  `python -m porechop_amd.aot` (called by __graft_entry__.build() and `make kernels`) compiles
-them with hiprtc -- no GPU needed -- into porechop_amd/kernel_cache/, which the library consults before it ever
+them with hiprtc -- no GPU needed -- each with its row-skipping variant for floored scans where it has one (csrc/pc_bounds.h,
+row_skip_plan; the three-wave kernels: csrc/pc_jit.cpp derive), into porechop_amd/kernel_cache/, which the library consults before it ever
 compiles at run time.  Anything else (custom adapters, other scoring schemes, leftover singles paired with each
 other) is compiled once at run time and kept in the user's cache directory (PC_JIT_CACHE_DIR / ~/.cache/porechop_amd).
 """
@@ -76,7 +77,10 @@ def _build_one(args):
     a, b, scores, cache_dir = args
     from ._lib import load_library
     lib = load_library()
-    return lib.pc_jit_precompile(a.encode(), (b or "").encode(), *scores, cache_dir.encode())
+    r = lib.pc_jit_precompile(a.encode(), (b or "").encode(), *scores, cache_dir.encode())
+    # ... and the pair's row-skipping variant, which the floored whole-read scans run (2: the pair has none)
+    k = lib.pc_jit_precompile_row_skip(a.encode(), (b or "").encode(), *scores, cache_dir.encode())
+    return r if (r < 0 or k == 2) else (k if k < 0 else min(r, k))
 
 
 def prebuild(cache_dir: str = CACHE_DIR, scores=DEFAULT_SCORES, workers: Optional[int] = None, pairs=None, quiet=False):

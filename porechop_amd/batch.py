@@ -356,6 +356,20 @@ class Aligner:
         check(self.lib.pc_floor_skipped(self._ctx, ctypes.c_void_p(s), ctypes.byref(last), ctypes.byref(total)), "pc_floor_skipped")
         return int(last.value), int(total.value)
 
+    def set_row_skip_debug(self, enabled=True):
+        """Count, per launch of a floored scan's score pass, the column pairs of the fast path and those with the rows below
+        r0 computed (pc_set_row_skip_debug; read with row_skip_blocks)."""
+        check(self.lib.pc_set_row_skip_debug(self._ctx, 1 if enabled else 0), "pc_set_row_skip_debug")
+
+    def row_skip_blocks(self, stream=None):
+        """-> (column pairs the fast path of the row-skipping launches ran since the last call, those with the lower rows on)
+        (pc_row_skip_blocks; waits for the stream and clears the counters)."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        n, on = ctypes.c_int64(0), ctypes.c_int64(0)
+        check(self.lib.pc_row_skip_blocks(self._ctx, ctypes.c_void_p(s), ctypes.byref(n), ctypes.byref(on)), "pc_row_skip_blocks")
+        return int(n.value), int(on.value)
+
     def set_length_hint(self, typical_len):
         """Typical window length of the following whole-read scans (0 = about uniform): load balancing of the
         score pass only, never results (pc_set_length_hint)."""

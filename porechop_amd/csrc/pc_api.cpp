@@ -108,6 +108,7 @@ struct pc_ctx {
     DevBuf d_units;              // unit_prefix tables of the launches whose windows are cut into more than kMaxChunks chunks
     int len_hint = 0;            // pc_set_length_hint
     bool int16_only = false;     // pc_set_int16_only: never use the packed-fp16 kernel variants
+    bool row_skip_debug = false; // pc_set_row_skip_debug: the row-skipping score launches count their column pairs
     // the prefilter: the plan (pc_prefilter_plan.h) of the last (adapter list, edit bounds, route), its tables on the device
     struct PfCache {
         std::vector<int32_t> key;            // adapters..., max_edits..., route; empty: the device holds no plan
@@ -235,8 +236,8 @@ int upload_panel(pc_ctx *c)
     return PC_OK;
 }
 
-// The scan's environment switches, all read here, once per process -- except PC_FORCE_CHUNKS, PC_NO_SCORE_FORK and
-// PC_NO_END_FLOOR, which are read for every call (tests change them between calls).
+// The scan's environment switches, all read here, once per process -- except PC_FORCE_CHUNKS, PC_NO_SCORE_FORK,
+// PC_NO_END_FLOOR and PC_NO_ROW_SKIP, which are read for every call (tests change them between calls).
 pcn::Options scan_options()
 {
     static const pcn::Options once = [] {
@@ -254,6 +255,7 @@ pcn::Options scan_options()
     if (const char *f = getenv("PC_FORCE_CHUNKS")) o.force_chunks = atoi(f);
     o.no_score_fork = getenv("PC_NO_SCORE_FORK") != nullptr;
     if (const char *e = getenv("PC_NO_END_FLOOR")) o.no_end_floor = *e && *e != '0';
+    if (const char *e = getenv("PC_NO_ROW_SKIP")) o.no_row_skip = *e && *e != '0';
     return o;
 }
 
@@ -336,6 +338,8 @@ int build_tiles(pc_ctx *c, const pcn::Params &p, const int32_t *job_adapter, con
 // pairs below their score floor, as two 64-bit counters behind the error words of d_err (bytes 0..23): those of the last floored
 // call, and all since the context was made (pc_floor_skipped)
 constexpr size_t kFloorCounterAt = 32;
+// behind them (bytes 48..63): the row-skip debug counters (pc_set_row_skip_debug / pc_row_skip_blocks)
+constexpr size_t kRowSkipCounterAt = 48;
 
 // HIP-event timing of a region of launches (pc_set_timing / pc_get_timing): begin() records on the stream where the region
 // starts, end() where it ends, and files the pair under its kind.  c_ == null: untimed.
@@ -378,6 +382,8 @@ struct ScanCall {
     int32_t *out;
     hipStream_t stream;
     pcn::Floors floors;
+    const int32_t *job_adapter = nullptr, *job_adapter_b = nullptr;          // the caller's job list (host), for the launches' floors
+    int njobs = 0;
     pcr::EndRule rule;                   // of a call with an end rule (floors.rule_side says for which jobs)
     int64_t npairs;
     bool linear;
@@ -404,7 +410,18 @@ void plan_scan(pc_ctx *c, ScanCall &s)
     const std::vector<pcn::Group> &groups = c->table.groups;
     s.scratch = pcn::scratch_layout(s.p, groups, s.max_len, s.mode);
     s.fork = s.scratch.n_single >= 2 && s.stream != c->stream && !s.p.opt.no_trace_fork;
+    bool skip_ok = false;                // the group being planned may skip rows (pcn::row_skip_allowed)
     auto lookup = [&](int lo, int hi, double cells) {
+        // a floored group owes exact records only to pairs that reach their floor: where the pair has the row-skipping kernel
+        // and the launch's floors give it thresholds, that one (pc_bounds.h row_skip_plan)
+        if (skip_ok) {
+            pcj::Spec *sk = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only, true);
+            pcj::SpecArgs probe;
+            if (sk && pcj::row_skip_args(sk, c->match, c->mismatch, c->gap_open, c->gap_extend,
+                                         pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, lo),
+                                         pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, hi), probe))
+                return pcn::SpecKernel{sk, sk->blocks_per_cu};
+        }
         pcj::Spec *sp = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only);
         return pcn::SpecKernel{sp, sp ? sp->blocks_per_cu : 0};
     };
@@ -412,6 +429,7 @@ void plan_scan(pc_ctx *c, ScanCall &s)
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const pcn::Group &g = groups[gi];
         if (!g.two_pass || s.mode == PC_MODE_TRACE_AT) continue;           // (TRACE_AT: the end cells are the caller's)
+        skip_ok = pcn::row_skip_allowed(s.p, g, s.mode, s.floors);
         size_t need = 0;
         s.score_plan[gi] = pcn::plan_score_launches(s.p, g, s.max_len, s.npairs, pcn::group_chunks_for(s.p, g, s.max_len), lookup, &need);
         s.k1_ints = std::max(s.k1_ints, need);
@@ -583,6 +601,14 @@ int score_pass(pc_ctx *c, ScanCall &s, size_t gi, const pck::ScanArgs &a, bool r
             // a score-only request over whole windows: the kernel writes the records itself (no planner launch)
             sa.rec_out = (records && L.chunks == 1) ? s.out : nullptr;
             sa.unit_prefix = unit_prefix;
+            // the row-skipping kernel -- plan_scan chose it for this launch's floors -- gets its thresholds (pc_bounds.h row_skip_plan)
+            if (((const pcj::Spec *)L.spec)->r0 < ((const pcj::Spec *)L.spec)->R) {
+                if (!pcj::row_skip_args((const pcj::Spec *)L.spec, c->match, c->mismatch, c->gap_open, c->gap_extend,
+                                        pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, L.adapter_lo),
+                                        pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, L.adapter_hi), sa))
+                    return PC_ERR_BAD_ARG;
+                if (c->row_skip_debug) sa.skip_count = (unsigned long long *)((char *)c->d_err.p + kRowSkipCounterAt);
+            }
             if (pcj::launch((const pcj::Spec *)L.spec, sa, grid, stream_k)) return PC_ERR_NO_DEVICE;
         } else {
             pck::ScanArgs b = a;
@@ -741,6 +767,7 @@ int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const 
     s.arena = d_arena; s.win_off = d_win_off; s.win_len = d_win_len; s.max_len = max_len; s.mode = mode; s.out = d_out;
     s.stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
     s.floors.a = job_floor; s.floors.b = job_floor_b;
+    s.job_adapter = job_adapter; s.job_adapter_b = job_adapter_b; s.njobs = njobs;
     s.linear = pcb::is_linear(c->gap_open, c->gap_extend);
     s.p = plan_params(c);
     if (rule && job_side && !s.p.opt.no_end_floor) {
@@ -941,6 +968,27 @@ int pc_floor_skipped(pc_ctx *c, void *stream_v, int64_t *last_call, int64_t *tot
     return PC_OK;
 }
 
+
+int pc_set_row_skip_debug(pc_ctx *c, int enabled)
+{
+    if (!c) return PC_ERR_BAD_ARG;
+    c->row_skip_debug = enabled != 0;
+    return PC_OK;
+}
+
+int pc_row_skip_blocks(pc_ctx *c, void *stream_v, int64_t *column_pairs, int64_t *lower_rows_on)
+{
+    if (!c || (!column_pairs && !lower_rows_on)) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipStreamSynchronize(stream));
+    unsigned long long v[2] = {0, 0};
+    HIP_TRY(hipMemcpy(v, (char *)c->d_err.p + kRowSkipCounterAt, 16, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset((char *)c->d_err.p + kRowSkipCounterAt, 0, 16));
+    if (column_pairs) *column_pairs = (int64_t)v[0];
+    if (lower_rows_on) *lower_rows_on = (int64_t)v[1];
+    return PC_OK;
+}
 
 int pc_debug_value_range(pc_ctx *c, int32_t *lo, int32_t *hi)
 {
@@ -1616,6 +1664,14 @@ int pc_jit_precompile(const char *adapter_a, const char *adapter_b, int match, i
     if (!adapter_a || !*adapter_a) return PC_ERR_BAD_ARG;
     const std::string a = adapter_a, b = (adapter_b && *adapter_b) ? adapter_b : adapter_a;
     return pcj::precompile(a, b, match, mismatch, gap_open, gap_extend, cache_dir ? cache_dir : "");
+}
+
+int pc_jit_precompile_row_skip(const char *adapter_a, const char *adapter_b, int match, int mismatch, int gap_open, int gap_extend,
+                               const char *cache_dir)
+{
+    if (!adapter_a || !*adapter_a) return PC_ERR_BAD_ARG;
+    const std::string a = adapter_a, b = (adapter_b && *adapter_b) ? adapter_b : adapter_a;
+    return pcj::precompile(a, b, match, mismatch, gap_open, gap_extend, cache_dir ? cache_dir : "", true);
 }
 
 void pc_jit_stats(int64_t *compiled, int64_t *from_disk)

@@ -122,6 +122,122 @@ inline SpecPlan spec_plan(int match, int mismatch, int gap_open, int gap_extend,
     return p;
 }
 
+// ---- Row skip of the specialised score kernel's fast path (pc_jit_source.h, PC_SKIP) ----------------------------------
+//
+// A floored two-pass call (pc_scan_device_floored) answers a pair whose best score is below its floor F with "no
+// alignment"; its score record is never shown.  Pass 1 therefore owes exact end cells only to pairs that reach F.
+//
+// Setting.  R register rows 1..R, the shorter adapter of a pair bottom-aligned under `pad` rows that keep M = 0 like
+// row 0.  The scheme has match > 0, mismatch <= match, gap_open < 0, gap_extend < 0 (anything else is refused; g =
+// min(|gap_open|, |gap_extend|) is the least any gap character costs).  r0 is an even register row, pad < r0 < R.  Per
+// half, with m its real rows and F its floor,
+//     theta = F - match * (R - r0)                               and it must be > 0 (refused otherwise),
+//     W_low = (R - r0) + max over the halves of floor(max(0, match * m - F) / g).
+// The variant computes rows <= r0 in every column, and rows > r0 only in the columns j'' .. j'' + W_low behind a column
+// j'' with M(r0, j'') >= theta in either half (more columns do no harm: see 1); where it switches them on, their values
+// of the column before are -infinity or whatever an earlier window left.  Call what it computes M^.
+//
+//  1. M^ <= M everywhere.  Rows <= r0 never read a row below them, so they are exact.  Below r0 every value is a maximum
+//     over a SUBSET of the paths the full recurrence maximises over (each computed cell is fed true row-r0 values and
+//     values of computed cells or -infinity), and each of those paths is a real one.
+//  2. Every candidate end cell c -- last row, or last column at any row -- with M(c) >= F has M^(c) = M(c).  If c lies in
+//     a row <= r0 there is nothing to show.  Otherwise take an optimal path to c.  It starts with score 0 in row 0 (or a
+//     padding row, which is the same thing) or in column 0.
+//       (a) It starts in column 0 in a row > r0: then it has at most R - r0 - 1 diagonals and scores at most
+//           match * (R - r0 - 1) < match * (R - r0) < F because theta > 0.  Contradiction.  (This is the host's "column-0
+//           condition": theta > 0 for every half.)
+//       (b) So it has cells in row r0; let (r0, j'') be the last one.  The prefix up to it, in whatever state it is there
+//           (a vertical gap running through row r0 included: V <= M), scores <= M(r0, j'').  The rest passes at most
+//           R - r0 rows, earns at most `match` per row and nothing from gaps, so M(r0, j'') >= F - match * (R - r0) =
+//           theta: column j'' switches the lower rows on.
+//       (c) The path goes on to (r0 + 1, j'') -- vertically -- or to (r0 + 1, j'' + 1) -- diagonally.  Both are fed from
+//           row r0's values of columns j'' - 1 and j'' (T of the diagonal neighbour, V and T of the upper one), which are
+//           exact, and lie in columns that are switched on.
+//       (d) Behind column j'' the path has at most R - r0 diagonal steps, and h horizontal gap characters with
+//           match * m - g * h >= F, so it ends at a column <= j'' + (R - r0) + floor((match * m - F) / g) <= j'' + W_low:
+//           every cell of it below row r0 lies in a computed column, and by induction along the path M^ of each such
+//           cell is at least the path's score there.  With 1, M^(c) = M(c).
+//  3. Consequences.  max over the candidates of M^ equals that of M whenever the latter is >= F, and then the sets of cells
+//     attaining it agree, so strict '>' in visiting order picks the same end cell: the records of pairs >= F are bit-identical.
+//     A pair below F stays below F (1), is counted by pc_floor_skipped and answered by plan_kernel exactly as before.
+//  Chunked launches: a cell >= F has its whole path inside W <= SPAN columns, so the lead-in argument above stands; a chunk's
+//  first tracked column is reached through the one-column path, which computes every row, and entering the fast path from
+//  it switches the lower rows on for W_low columns (a path may have left row r0 in any column the one-column path ran).
+//
+// The rule for r0 (row_skip_r0) is a function of the kernel's recipe alone -- r0 is a compile-time constant of the ONE
+// kernel per adapter pair -- and has no part in exactness: the smallest even row above the padding for which the share
+// of column pairs with the lower rows on stays under 1 / 64 in a model of uniform random bases at the floor of a 90 %
+// identity threshold (--middle_threshold's default, Pipeline.identity_score_bound), F = floor(m * (0.9 * match - 0.1 *
+// max(|mismatch|, |gap_open|, |gap_extend|))): per half the chance
+// that an ungapped m'-row prefix (m' = the half's real rows down to r0) loses at most match * m' - theta, times 128 cells per
+// column pair and half, times the W_low / 2 + 1 column pairs a window lasts.  R (no skipping path in the kernel) if no
+// row at least four above the last one qualifies.  The model leaves gapped prefixes out, which are some ten times as
+// frequent, and a lower threshold triggers more often: either costs time, never exactness.  Measured on the headline
+// (profiles/score_row_skip_before_after.txt): the rule's row, 20 for both pairs, is the fastest of 14 .. 24.
+// At most kRowSkipMaxLower rows are left below r0: the variant keeps them in LDS, 512 bytes per row and workgroup, and
+// twelve one-wave workgroups (three waves per SIMD) share a CU's 160 KiB, so that 16 rows (8 KiB) beside the kernel's
+// tables (at most 100 * K + 1536 bytes, K <= 28 in that register class) leave the occupancy to the registers, as it was.
+// pc_jit.cpp gives the variant to three-wave kernels only and checks these bytes again.
+constexpr int kRowSkipMaxLower = 16;
+struct RowSkip { bool ok; int theta_lo, theta_hi, w_low; };
+inline bool row_skip_scheme(int match, int mismatch, int gap_open, int gap_extend)
+{
+    return match > 0 && mismatch <= match && gap_open < 0 && gap_extend < 0 && !is_linear(gap_open, gap_extend);
+}
+// thresholds and window for one launch: F_lo / F_hi are the halves' floors (the lowest floor of any job the launch serves)
+inline RowSkip row_skip_plan(int match, int mismatch, int gap_open, int gap_extend, int R, int r0, int m_lo, int m_hi,
+                             long F_lo, long F_hi)
+{
+    RowSkip p = {false, 0, 0, 0};
+    if (!row_skip_scheme(match, mismatch, gap_open, gap_extend)) return p;
+    if (m_lo < 1 || m_hi < 1 || m_lo > R || m_hi > R || (m_lo != R && m_hi != R)) return p;
+    const int pad = R - (m_lo < m_hi ? m_lo : m_hi);
+    if (r0 < 2 || (r0 & 1) || r0 >= R || r0 <= pad) return p;
+    const long below = (long)match * (R - r0);
+    const long t_lo = F_lo - below, t_hi = F_hi - below;
+    if (t_lo <= 0 || t_hi <= 0) return p;                                    // 2 (a): the column-0 condition
+    // a floor nothing can reach never triggers; one beyond what the lane type adds exactly must not reach the kernel
+    if (F_lo > (long)match * m_lo || F_hi > (long)match * m_hi) return p;
+    const long g = -gap_open < -gap_extend ? -(long)gap_open : -(long)gap_extend;
+    const long h_lo = ((long)match * m_lo - F_lo) / g, h_hi = ((long)match * m_hi - F_hi) / g;
+    const long w = (R - r0) + (h_lo > h_hi ? h_lo : h_hi);
+    if (w > (1L << 20)) return p;
+    p.ok = true; p.theta_lo = (int)t_lo; p.theta_hi = (int)t_hi; p.w_low = (int)w;
+    return p;
+}
+inline long row_skip_nominal_floor(int match, int mismatch, int gap_open, int gap_extend, int m)
+{
+    long P = -mismatch > -gap_open ? -(long)mismatch : -(long)gap_open;
+    if (-(long)gap_extend > P) P = -(long)gap_extend;
+    const long f = ((long)m * (9L * match - P)) / 10;                 // floor: the product is >= 0 where it is used
+    return f;
+}
+inline int row_skip_r0(int match, int mismatch, int gap_open, int gap_extend, int R, int m_lo, int m_hi)
+{
+    if (!row_skip_scheme(match, mismatch, gap_open, gap_extend) || match == mismatch) return R;
+    const long F_lo = row_skip_nominal_floor(match, mismatch, gap_open, gap_extend, m_lo);
+    const long F_hi = row_skip_nominal_floor(match, mismatch, gap_open, gap_extend, m_hi);
+    if (F_lo <= 0 || F_hi <= 0) return R;
+    const int first = R - kRowSkipMaxLower > 2 ? (R - kRowSkipMaxLower + 1) / 2 * 2 : 2;   // even, and R - first <= kRowSkipMaxLower
+    for (int r0 = first; r0 <= R - 4; r0 += 2) {
+        const RowSkip p = row_skip_plan(match, mismatch, gap_open, gap_extend, R, r0, m_lo, m_hi, F_lo, F_hi);
+        if (!p.ok) continue;
+        double rate = 0;
+        for (int half = 0; half < 2; ++half) {
+            const int mp = (half ? m_hi : m_lo) - (R - r0);                  // real rows down to r0
+            const long theta = half ? p.theta_hi : p.theta_lo;
+            const long kmax = ((long)match * mp - theta) / ((long)match - mismatch);   // mismatches an ungapped prefix can afford
+            if (kmax < 0) continue;
+            double term = 1.0, sum = 0;                                      // C(mp, k) * 0.75^k * 0.25^(mp - k), from k = 0
+            for (int i = 0; i < mp; ++i) term *= 0.25;
+            for (long k = 0; k <= kmax && k <= mp; ++k) { sum += term; term *= 3.0 * (double)(mp - k) / (double)(k + 1); }
+            rate += 128.0 * sum;
+        }
+        if (rate * (p.w_low / 2 + 1) <= 1.0 / 64) return r0;
+    }
+    return R;
+}
+
 inline bool compute_bounds(int match, int mismatch, int gap_open, int gap_extend, int m, Bounds &b)
 {
     if (!scores_supported(match, mismatch, gap_open, gap_extend, m > 0 ? m : 1)) return false;

@@ -105,7 +105,7 @@ struct Entry {
     bool compiled_ok = false;
     std::atomic<bool> compile_done{false};
     std::thread worker;
-    int R = 0, K = 0, m_lo = 0, m_hi = 0, waves = 2;
+    int R = 0, K = 0, m_lo = 0, m_hi = 0, waves = 2, r0 = 0;
     bool f16 = false;
     long kren = 0;
 };
@@ -122,6 +122,7 @@ struct Recipe {                                // everything the compile step ne
     int R, m_lo, m_hi, eps, waves;
     bool f16;
     long kren, cen;
+    bool row_skip = false;                     // the variant whose fast path skips the rows below r0 (a kernel of its own per pair)
 };
 
 // Everything about a kernel that follows from its recipe without compiling anything: the hiprtc options (they
@@ -129,7 +130,7 @@ struct Recipe {                                // everything the compile step ne
 struct Derived {
     std::vector<std::string> opts;
     std::vector<int> combos;
-    int K = 0, waves = 2;
+    int K = 0, waves = 2, r0 = 0;
 };
 
 Derived derive(const Recipe &rc)
@@ -161,14 +162,29 @@ Derived derive(const Recipe &rc)
     std::string init;
     for (int row = 0; row < R; ++row) { init += std::to_string(combo_of_row[row]); if (row + 1 < R) init += ","; }
     const char *chk = getenv("PC_JIT_CHECK_RANGE");
+    const bool check_range = chk && *chk && *chk != '0';
+    // the row its row-skipping fast path tests (pc_bounds.h): packed fp16 only, and not in the range-recording build, which
+    // takes the one-column path throughout.  Three-wave kernels only: the longer pairs' kernels (two waves, or one with rows
+    // parked in AGPRs) have no room for the lower part beside their rows, and their few workgroups per CU would pay for the
+    // lower rows' LDS with occupancy.  PC_JIT_R0 overrides the rule (measurements; an unusable value means none)
+    const bool may_skip = rc.row_skip && rc.f16 && !check_range && waves == 3;
+    d.r0 = may_skip ? pcb::row_skip_r0(rc.match, rc.mismatch, rc.gap_open, rc.gap_extend, R, rc.m_lo, rc.m_hi) : R;
+    if (const char *e = getenv("PC_JIT_R0")) {
+        const int v = atoi(e), pad = R - std::min(rc.m_lo, rc.m_hi);
+        if (may_skip) d.r0 = (v >= 2 && !(v & 1) && v < R && v > pad) ? v : R;
+    }
+    // the kernel's LDS (tables, three look-up tables, 512 bytes per lower row) times the twelve workgroups of a CU at three
+    // waves per SIMD must fit its 160 KiB, or the variant would run at a lower occupancy than the plain kernel: then none
+    if (d.r0 < R && 12L * (100L * K + 1536 + 512L * (R - d.r0)) > 160L * 1024) d.r0 = R;
     d.opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
               "-DPC_R=" + std::to_string(R), "-DPC_K=" + std::to_string(K), "-DPC_COMBO_INIT=" + init,
               std::string("-DPC_F16=") + (rc.f16 ? "1" : "0"), "-DPC_EPS=" + std::to_string(rc.eps),
               "-DPC_OE=(" + std::to_string(rc.gap_open + rc.eps) + ")", "-DPC_CEN=(" + std::to_string(rc.cen) + ")",
               "-DPC_KREN=" + std::to_string(rc.kren),
               std::string("-DPC_WAVES=") + (getenv("PC_JIT_WAVES") ? getenv("PC_JIT_WAVES") : std::to_string(waves)),
-              std::string("-DPC_CHECK_RANGE=") + ((chk && *chk && *chk != '0') ? "1" : "0"),
+              std::string("-DPC_CHECK_RANGE=") + (check_range ? "1" : "0"),
               std::string("-DPC_DUAL=") + (rc.ad_lo != rc.ad_hi ? "1" : "0")};
+    if (d.r0 < R) d.opts.push_back("-DPC_R0=" + std::to_string(d.r0));        // (the plain kernel's options are what they were)
     return d;
 }
 
@@ -360,7 +376,7 @@ bool hiprtc_compile(const std::vector<std::string> &opts, std::vector<char> &cod
 
 void fill_entry(Entry *e, const Recipe &rc, const Derived &d)
 {
-    e->R = rc.R; e->K = d.K; e->m_lo = rc.m_lo; e->m_hi = rc.m_hi; e->f16 = rc.f16; e->waves = d.waves; e->kren = rc.kren;
+    e->R = rc.R; e->K = d.K; e->m_lo = rc.m_lo; e->m_hi = rc.m_hi; e->f16 = rc.f16; e->waves = d.waves; e->r0 = d.r0; e->kren = rc.kren;
     e->table = substitution_table(rc, d);           // empty: a table term outside the lane type's exact range (never expected)
 }
 
@@ -407,7 +423,7 @@ void finalize_entry(Entry *e, bool verbose)
         return;
     }
     Spec *sp = new Spec();
-    sp->R = e->R; sp->K = e->K; sp->m_lo = e->m_lo; sp->m_hi = e->m_hi; sp->f16 = e->f16; sp->waves = e->waves;
+    sp->R = e->R; sp->K = e->K; sp->m_lo = e->m_lo; sp->m_hi = e->m_hi; sp->f16 = e->f16; sp->waves = e->waves; sp->r0 = e->r0;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
     if (hipModuleLoadData(&mod, e->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, "pc_spec_score") != hipSuccess) {
@@ -464,7 +480,7 @@ struct JoinAtExit { ~JoinAtExit() { wait_idle(true); } } g_join_at_exit;
 }  // namespace
 
 Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open,
-          int gap_extend, double cells, bool int16_only)
+          int gap_extend, double cells, bool int16_only, bool row_skip)
 {
     if (disabled()) return nullptr;
     const int m_lo = (int)ad_lo.size(), m_hi = (int)ad_hi.size();
@@ -491,7 +507,12 @@ Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int ma
     }
     const long cen = plan.cen;
     char keybuf[64];
-    snprintf(keybuf, sizeof keybuf, "|%d|%d,%d,%d,%d|%d", device, match, mismatch, gap_open, gap_extend, f16 ? 1 : 0);
+    if (row_skip) {
+        // the row-skipping variant exists for packed fp16 and where the rule finds a row (a function of the recipe alone)
+        const Recipe probe{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, plan.cen, true};
+        if (!f16 || derive(probe).r0 >= R) return nullptr;
+    }
+    snprintf(keybuf, sizeof keybuf, "|%d|%d,%d,%d,%d|%d%s", device, match, mismatch, gap_open, gap_extend, f16 ? 1 : 0, row_skip ? "|skip" : "");
     const std::string key = ad_lo + "|" + ad_hi + keybuf;
     std::lock_guard<std::mutex> lk(g_mu);
     Entry *&slot = g_cache[key];
@@ -505,7 +526,7 @@ Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int ma
         finalize_entry(e, verbose);
         return e->spec;
     }
-    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, cen};
+    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, cen, row_skip};
     // a kernel that is already on disk (built with the library for the static panel, or compiled by an earlier
     // process on this machine) costs a file read and a module load: use it from the first launch on
     if (!e->disk_checked) {
@@ -537,7 +558,7 @@ Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int ma
 }
 
 int precompile(const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open, int gap_extend,
-               const std::string &dir)
+               const std::string &dir, bool row_skip)
 {
     const int m_lo = (int)ad_lo.size(), m_hi = (int)ad_hi.size();
     const int R = m_lo > m_hi ? m_lo : m_hi;
@@ -546,8 +567,9 @@ int precompile(const std::string &ad_lo, const std::string &ad_hi, int match, in
     const char *force_int = getenv("PC_JIT_INT16");
     const pcb::SpecPlan plan = pcb::spec_plan(match, mismatch, gap_open, gap_extend, R, force_int && *force_int && *force_int != '0');
     if (!plan.ok) return -1;
-    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, -gap_extend, 2, plan.f16, plan.kren, plan.cen};
+    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, -gap_extend, 2, plan.f16, plan.kren, plan.cen, row_skip};
     const Derived d = derive(rc);
+    if (row_skip && d.r0 >= R) return 2;                       // the pair has no row-skipping variant
     const std::string where = dir.empty() ? intree_cache_dir() : dir;
     std::vector<char> code;
     if (cache_read(where, d.opts, code)) return 1;
@@ -563,6 +585,19 @@ void stats(long *compiled, long *from_disk)
 {
     if (compiled) *compiled = g_n_compiled.load();
     if (from_disk) *from_disk = g_n_disk.load();
+}
+
+bool row_skip_args(const Spec *sp, int match, int mismatch, int gap_open, int gap_extend, int32_t floor_lo, int32_t floor_hi, SpecArgs &a)
+{
+    a.skip_thr2 = 0; a.skip_w = 0;
+    if (!sp || !sp->f16 || sp->r0 <= 0 || sp->r0 >= sp->R || floor_lo == INT32_MIN || floor_hi == INT32_MIN) return false;
+    const pcb::RowSkip p = pcb::row_skip_plan(match, mismatch, gap_open, gap_extend, sp->R, sp->r0, sp->m_lo, sp->m_hi, floor_lo, floor_hi);
+    if (!p.ok) return false;
+    // what M(r0, j) + r0 * eps must exceed: an integer of magnitude <= match * m + R * eps, exact in fp16 by spec_plan's gate
+    const int eps = -gap_extend;
+    a.skip_thr2 = half_bits(p.theta_lo + sp->r0 * eps - 1) | (half_bits(p.theta_hi + sp->r0 * eps - 1) << 16);
+    a.skip_w = p.w_low;
+    return true;
 }
 
 int launch(const Spec *sp, const SpecArgs &a, int grid, void *stream)

@@ -11,6 +11,7 @@ namespace pcj {
 struct Spec {
     int R = 0, K = 0, m_lo = 0, m_hi = 0;
     int waves = 2;               // resident waves per SIMD the register allocation is asked to allow
+    int r0 = 0;                  // the row-skipping variant: the register row it tests (pcb::row_skip_r0), < R; the plain kernel: R
     int blocks_per_cu = 8;       // resident 64-thread workgroups per CU (runtime occupancy query: registers and LDS)
     bool f16 = false;            // packed-fp16 variant (5 ops per cell pair) vs packed-int16 (6)
     void *module = nullptr, *function = nullptr;
@@ -32,20 +33,31 @@ struct SpecArgs {
     int32_t *rec_out;            // PC_MODE_SCORE with whole windows (chunks == 1): the pairs' 8-int score records, written by the
                                  // kernel itself -- (-2, J, I, 0, score, 0, 0, 0) at rec_out[p * 8] -- instead of by the planner
     const int32_t *unit_prefix;  // [ntiles + 1] or null: the real (tile, chunk) units only (pck::launch_unit_prefix)
+    // row skip (pcb::row_skip_plan): skip_w = W_low, 0 = every row in every column; skip_thr2 = the halves' packed-fp16 terms
+    // theta + r0 * eps - 1 (pcj::row_skip_args fills both); skip_count: null, or the debug counters (column pairs, pairs with the lower rows on)
+    uint32_t skip_thr2; int32_t skip_w;
+    unsigned long long *skip_count;
 };
 
 bool disabled();
+// row_skip: the pair's second kernel, whose fast path computes the rows below r0 only where a launch's thresholds ask for them
+// (pc_bounds.h row_skip_plan; Spec::r0 < R).  It must be launched with row_skip_args' answer; nullptr where the pair has none.
 // nullptr when specialisation is unavailable for this pair, or not yet worth its compile: `cells`
 // (the launch's work) is added to the pair's running total, and the kernel is compiled once that
 // total reaches PC_JIT_MIN_CELLS (caller uses the generic kernels until then).
 // int16_only: the packed-int16 variant (6 ops per cell pair) even where packed fp16 is exact (pc_set_int16_only).
 Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open,
-          int gap_extend, double cells, bool int16_only = false);
+          int gap_extend, double cells, bool int16_only = false, bool row_skip = false);
 int launch(const Spec *sp, const SpecArgs &a, int grid, void *stream);
+// The row skip of one launch of `sp` under the halves' score floors (INT32_MIN: none): fills a.skip_thr2 / a.skip_w and answers
+// true, or leaves them zero -- the kernel has no skipping path (int16 lanes, the range-recording build, no row qualifies), a
+// half has no floor, or pcb::row_skip_plan refuses.
+bool row_skip_args(const Spec *sp, int match, int mismatch, int gap_open, int gap_extend, int32_t floor_lo, int32_t floor_hi, SpecArgs &a);
 // Ahead-of-time build of one pair's kernel into a kernel cache directory ("" = the in-tree one next to the library).
 // Needs hiprtc, not a device.  0 = compiled and written, 1 = was already there, < 0 = no such kernel / failure.
+// row_skip: the pair's row-skipping variant instead; 2 = the pair has none.
 int precompile(const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open, int gap_extend,
-               const std::string &dir);
+               const std::string &dir, bool row_skip = false);
 // kernels compiled by hiprtc / taken from a kernel cache on disk by this process so far
 void stats(long *compiled, long *from_disk);
 // Asynchronous specialisation: compiles run on a worker thread and launches keep using the generic

@@ -56,7 +56,8 @@ namespace pcj {
 
 // defines prepended by pc_jit.cpp: PC_DUAL (1: the two adapters differ), PC_R, PC_K (multiple of 4), PC_COMBO_INIT (R comma-separated
 // ints), PC_F16, PC_EPS (= -gap_extend), PC_OE (= gap_open + PC_EPS), PC_CEN (C), PC_KREN,
-// PC_WAVES (resident waves per SIMD the register allocation must allow), PC_CHECK_RANGE (0/1)
+// PC_WAVES (resident waves per SIMD the register allocation must allow), PC_CHECK_RANGE (0/1); the row-skipping variant
+// of a pair (a kernel of its own: pc_bounds.h row_skip_plan) also gets PC_R0, the register row it tests
 static const char *kSpecSource = R"PCJIT(
 typedef unsigned int u32;
 typedef long long i64;
@@ -124,9 +125,19 @@ struct SpecArgs {
     int *rec_out;             // score-only request over whole windows: [npairs][8] records (-2, J, I, 0, score, 0, 0, 0), else null
     const int *unit_prefix;   // [ntiles + 1] or null: tile t owns units [unit_prefix[t], unit_prefix[t + 1]) -- the chunks that hold columns
                               // of its longest window (a 4 Mb read among 20 kb reads: 2 048 chunks per tile, ten of them real for most)
+    // row skip (pc_bounds.h row_skip_plan; floored two-pass calls only): skip_w = W_low > 0 switches it on; skip_thr2 = the packed
+    // terms theta + r0 * eps - 1 of the two halves, which M(r0, j) + r0 * eps has to exceed for the rows below r0 to be computed
+    u32 skip_thr2; int skip_w;
+    unsigned long long *skip_count;   // null, or two counters: column pairs of the fast path, and those with the lower rows on
 };
 struct FastT { static constexpr bool fast = true; };
 struct SlowT { static constexpr bool fast = false; };
+template <int N> struct RowsT { static constexpr int rows = N; };
+// PC_R0: the register row r0 the row skip tests (even, < PC_R), or PC_R: this kernel has no skipping path
+#ifndef PC_R0
+#define PC_R0 PC_R
+#endif
+#define PC_SKIP (PC_F16 && !PC_CHECK_RANGE && (PC_R0) < (PC_R))
 
 __device__ static const unsigned char COMBO[PC_R] = { PC_COMBO_INIT };
 
@@ -141,6 +152,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
     __shared__ uint4 s_tab[25 * K / 4];
     // (all three tables hold row offsets in BYTES, at most 24 * 16 * K / 4 < 2^16: a row's address is one add)
     __shared__ unsigned short lut_lo[256], lut_hi[256];
+#if PC_SKIP
+    __shared__ uint2 s_low[(PC_R - (PC_R0)) * 64];           // (T~, U) of the rows below r0 during a stretch of fast-path blocks (row skip)
+#endif
 #if PC_DUAL
     // two DIFFERENT adapters only ever share a tile whose halves read the same windows (pc_api.cpp
     // build_tiles): one byte stream per lane, and the byte -> table row lookup is a single read
@@ -255,6 +269,11 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
             o = __shfl_xor(nmin, s); nmin = o < nmin ? o : nmin;
             o = __shfl_xor(tfmax, s); tfmax = o > tfmax ? o : tfmax;
         }
+#if PC_SKIP
+        // (the extents are wave-uniform, but come out of a shuffle: said so, the fast path's tests and the window's state
+        // below are scalar branches and scalar registers, not exec masks and copies of every row's registers)
+        nmax = __builtin_amdgcn_readfirstlane(nmax); nmin = __builtin_amdgcn_readfirstlane(nmin); tfmax = __builtin_amdgcn_readfirstlane(tfmax);
+#endif
         // Every stream of the tile ends in the SAME column (equal-length windows: the 150-column end windows of phase B's
         // score pass, the uniform reads of the benchmark): the column loop then stops exactly there and the last column's
         // cells are scanned straight from the registers.  Otherwise (ragged tiles) a lane that ends parks the state its last
@@ -461,8 +480,14 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         // keeps its register from column pair to column pair and the allocator has nothing to rotate.
         // Only for blocks in which every stream of the tile tracks the columns and none ends (the caller's
         // fast path, which converts U on entry).
-        auto column2 = [&](const u32 (&S1)[K], const u32 (&S2)[K], u32 &c1, u32 &c2) {
-            constexpr int NU = (R + 1) / 2;                                    // units: row pairs, then an odd last row alone
+        //
+        // Row skip (PC_SKIP, a launch with skip_w > 0): the column pair runs over the upper r0 = PC_R0 rows only and
+        // leaves what the rows below need of row r0 -- if_va = V~(r0 - 1, j) (register rows: the even row of the last pair),
+        // if_x0 / if_x1 = T~(r0 - 1, j) / T~(r0, j), if_vb = V~(r0 - 1, j + 1); T~(., j + 1) is in T[] -- see lower_col.
+        u32 if_x0 = NEG2, if_x1 = NEG2, if_va = NEG2, if_vb = NEG2;
+        auto column2 =[&](auto rows, const u32 (&S1)[K], const u32 (&S2)[K], u32 &c1, u32 &c2) {
+            constexpr int RU = decltype(rows)::rows;                           // the rows it runs over: R, or the upper r0 (row skip)
+            constexpr int NU = (RU + 1) / 2;                                    // units: row pairs, then an odd last row alone
             const u32 topA = pk_add(top, EPS2), topB = pk_add(topA, EPS2);     // T~(0,j), T~(0,j+1)
             u32 X[R], dA[R];                                                   // column j; chain A's d of the rows in flight
 #define PC_M3 "v_pk_maximum3_f16"
@@ -504,23 +529,23 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #define PC_B_PAIR PC_B2 PC_B1 PC_B5 PC_B3 PC_NOP PC_B4 PC_NOP PC_B6 PC_B8 PC_B7 PC_NOP PC_B9
 #define PC_B_ODD PC_B2 PC_B1 PC_NOP PC_B3 PC_NOP PC_B4 PC_NOP PC_B8
             auto dterm = [&](u32 &d, u32 diag, u32 s) { asm volatile(PC_ADD " %[d], %[g], %[s]" : [d] "=v"(d) : [g] "v"(diag), [s] "v"(s)); };
-            u32 VbA = NEG2, VbB = NEG2;
+            u32 VbA = NEG2, VbB = NEG2, vbl = NEG2;
             // ---- chain A alone: its first unit (rows 0 and 1); T(-2, .) = -infinity, T(-1, .) = the top row
             dterm(dA[0], top, S1[COMBO[0]]);
-            if constexpr (R > 1) dterm(dA[1], T[0], S1[COMBO[1]]);
+            if constexpr (RU > 1) dterm(dA[1], T[0], S1[COMBO[1]]);
             {
                 u32 va;
-                if constexpr (R >= 4) {
+                if constexpr (RU >= 4) {
                     asm volatile(PC_A_PAIR(PC_A7, PC_A8)
                                  : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1]), [da2] "=&v"(dA[2]), [da3] "=&v"(dA[3])
                                  : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
                                    [ua0] "v"(U[0]), [ua1] "v"(U[1]), [to1] "v"(T[1]), [sa2] "v"(S1[COMBO[2]]), [sa3] "v"(S1[COMBO[3]]), [ta2] "v"(T[2]));
-                } else if constexpr (R == 3) {
+                } else if constexpr (RU == 3) {
                     asm volatile(PC_A_PAIR(PC_A7, PC_NOP)
                                  : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1]), [da2] "=&v"(dA[2])
                                  : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
                                    [ua0] "v"(U[0]), [ua1] "v"(U[1]), [to1] "v"(T[1]), [sa2] "v"(S1[COMBO[2]]));
-                } else if constexpr (R == 2) {
+                } else if constexpr (RU == 2) {
                     asm volatile(PC_A_PAIR("", PC_NOP)
                                  : [va] "=&v"(va), [ta0] "=&v"(X[0]), [ta1] "=&v"(X[1])
                                  : [vpa] "v"(VbA), [tf] "v"(NEG2), [tg] "v"(topA), [oe] "s"(OE2), [da0] "v"(dA[0]), [da1] "v"(dA[1]),
@@ -536,7 +561,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
             // (its d' go where the rows' old T was: in-out, so that the register stays the row's)
             auto dterm_b = [&](u32 &t, u32 diag, u32 s) { asm volatile(PC_ADD " %[t], %[g], %[s]" : [t] "+v"(t) : [g] "v"(diag), [s] "v"(s)); };
             dterm_b(T[0], topA, S2[COMBO[0]]);
-            if constexpr (R > 1) dterm_b(T[1], X[0], S2[COMBO[1]]);
+            if constexpr (RU > 1) dterm_b(T[1], X[0], S2[COMBO[1]]);
 #pragma clang loop unroll(full)
             for (int u = 1; u < NU; ++u) {
                 const int e = 2 * u, f = e - 2;                                // A: rows e, e+1; B: rows f, f+1
@@ -546,17 +571,17 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                    [ub0] "+v"(U[f]), [ub1] "+v"(U[f + 1]), [db2] "+v"(T[e])
 #define PC_AB_IN   [vpa] "v"(VbA), [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [tg] "v"(X[f + 1]), \
                    [oe] "s"(OE2), [da0] "v"(dA[e]), [ua0] "v"(U[e]), [sb2] "v"(S2[COMBO[f + 2]])
-                if (e + 3 < R) {
+                if (e + 3 < RU) {
                     asm volatile(PC_AB(PC_A7I, PC_A8)
                                  : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1]), [da2] "=&v"(dA[e + 2]), [da3] "=&v"(dA[e + 3])
                                  : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]),
                                    [sa2] "v"(S1[COMBO[e + 2]]), [sa3] "v"(S1[COMBO[e + 3]]), [ta2] "v"(T[e + 2]));
-                } else if (e + 2 < R) {
+                } else if (e + 2 < RU) {
                     asm volatile(PC_AB(PC_A7I, "")
                                  : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1]), [da2] "=&v"(dA[e + 2])
                                  : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]),
                                    [sa2] "v"(S1[COMBO[e + 2]]));
-                } else if (e + 1 < R) {
+                } else if (e + 1 < RU) {
                     asm volatile(PC_AB(PC_NOP, "")
                                  : PC_AB_OUT, [ta1] "=&v"(X[e + 1]), [db3] "+v"(T[e + 1])
                                  : PC_AB_IN, [da1] "v"(dA[e + 1]), [ua1] "v"(U[e + 1]), [sb3] "v"(S2[COMBO[f + 3]]));
@@ -567,13 +592,17 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #undef PC_AB_IN
                 VbA = va; VbB = vb;
             }
-            c1 = pk_sub(X[R - 1], topA);               // column j's last row
+            c1 = pk_sub(X[RU - 1], topA);               // column j's last row
             // ---- chain B alone: its last unit
             {
                 constexpr int f = 2 * (NU - 1);
                 const u32 tbm2 = f ? T[f - 2] : NEG2, tbm1 = f ? T[f - 1] : topB;
                 u32 vb;
-                if constexpr (f + 1 < R) {
+                if constexpr (RU < R) {                        // row r0's interface of column j for the rows below (row skip)
+                    static_assert(RU % 2 == 0 && RU >= 2, "r0 is even");
+                    if_x0 = X[RU - 2]; if_x1 = X[RU - 1]; if_va = VbA;
+                }
+                if constexpr (f + 1 < RU) {
                     asm volatile(PC_B_PAIR
                                  : [vb] "=&v"(vb), [tb0] "+v"(T[f]), [tb1] "+v"(T[f + 1]), [ub0] "+v"(U[f]), [ub1] "+v"(U[f + 1])
                                  : [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [tg] "v"(X[f + 1]), [oe] "s"(OE2));
@@ -582,8 +611,10 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                                  : [vb] "=&v"(vb), [tb0] "+v"(T[f]), [ub0] "+v"(U[f])
                                  : [vpb] "v"(VbB), [tbm2] "v"(tbm2), [tbm1] "v"(tbm1), [tf] "v"(X[f]), [oe] "s"(OE2));
                 }
+                vbl = vb;
             }
-            c2 = pk_sub(T[R - 1], topB);
+            if constexpr (RU < R) if_vb = vbl;
+            c2 = pk_sub(T[RU - 1], topB);
             top = topB;
 #undef PC_M3
 #undef PC_NOP
@@ -622,7 +653,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         // no s_nop, and the two chains give the VALU independent work (profiles/r01_ubench_row.txt:
         // 22.4 instead of 23.75 cycles per row at two waves per SIMD).  Only for blocks in which every
         // stream of the tile tracks the columns and none ends (the caller's fast path).
-        auto column2 = [&](const u32 (&S1)[K], const u32 (&S2)[K], u32 &c1, u32 &c2) {
+        auto column2 = [&](auto, const u32 (&S1)[K], const u32 (&S2)[K], u32 &c1, u32 &c2) {
             constexpr int L = 3, KP = 2;
             const u32 topA = pk_add(top, EPS2), topB = pk_add(topA, EPS2);     // T~(0,j), T~(0,j+1)
             u32 dhA[R], dhB[R];
@@ -729,12 +760,91 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         u32 nxt_lo = q_lo.y, nxt_hi = q_hi.y;
         u32 SA[K], SB[K], SC[K], SD[K];
         fetch_S(SA, cur_lo & 0xFF, cur_hi & 0xFF);
+        // a new maximum somewhere in the NC columns from jb on (nb: the packed maximum over them and best2): resolve the
+        // column, in visiting order (strict '>', the earlier column wins)
+        auto take_maxima = [&](auto ncols, const u32 (&cs)[4], const u32 nb, const int jb) {
+            constexpr int NC = decltype(ncols)::rows;
+            if (nmax <= 65000) {
+                u32 b = best2, ps = pos2;
+#pragma clang loop unroll(full)
+                for (int k = 0; k < NC; ++k) {
+                    const u32 m = pk_maxq(b, cs[k]);
+                    const u32 f = pk_minu(m ^ b, ONE2);              // 1 in the halves where column k is a new maximum
+                    const u32 jk = (u32)(jb + k) * 0x00010001u;
+                    ps = pk_madu(f, pk_subu(jk, ps), ps);            // their column becomes jb + k
+                    b = m;
+                }
+                best2 = b; pos2 = ps; packed_ahead = true;
+            } else {                                                  // columns beyond u16: the plain way
+#pragma clang loop unroll(full)
+                for (int k = 0; k < NC; ++k) {
+                    const int cl = lo16(cs[k]) - R * PC_EPS, ch = hi16(cs[k]) - R * PC_EPS;
+                    if (cl > bs_lo) { bs_lo = cl; bi_lo = a.m_lo; bj_lo = jb + k; }
+                    if (ch > bs_hi) { bs_hi = ch; bi_hi = a.m_hi; bj_hi = jb + k; }
+                }
+                best2 = nb;
+            }
+        };
+#if PC_SKIP
+        // ---- row skip (the proposition and its proof: pc_bounds.h row_skip_plan).  A floored call owes exact records only to
+        // pairs whose score reaches the floor F, and an alignment that does has M(r0, j) >= theta where it leaves register
+        // row r0.  A stretch of fast-path blocks therefore runs column2 over the upper r0 rows alone, tests once per column
+        // pair whether some stream has M(r0, .) >= theta, and computes the rows below only in the skip_w columns behind such
+        // a column (and behind the stretch's first column: the one-column path before it computes every row and tests
+        // nothing).  For the length of a stretch the rows below live in LDS (s_low: T~ and U per row and lane, U = H~(r, j - 1)
+        // as on the one-column path), so that the column pair has their registers; while they are off they hold -infinity.
+        // Whatever reads them as they stand after the stretch (the one-column path, the parked and the uniform last column)
+        // reads lower bounds, which is all a cell below F needs.
+        const int skip_w = a.skip_w > 0 ? a.skip_w : 0x3FFFFFFF;   // (a launch without a window: every row in every column)
+        int low_until = 0;                                    // the rows below r0 are computed in the stretch's columns <= low_until
+        bool low_on = false;                                  // ... and have been since they last held -infinity
+        // (debug counters: 4-column blocks of the fast path, and those among them with the lower rows on -- both without the
+        // blocks of a stretch's first window as long as nothing has triggered in it: they are on whatever the reads hold)
+        u32 n_pair = 0, n_low = 0;
+        int count_from = 0x7FFFFFFF;
+        // the rows below r0 over the block's four columns, one pass over the rows: column k's diagonal term of the first of them
+        // comes from dg[k] = T~(r0, j0 + k - 1), its V from vv[k] = V~(r0 + 1, j0 + k); the substitution terms are read from
+        // the table again (this is the rare part: the column pairs' four sets need not stay in registers for it)
+        auto lower_block = [&](u32 (&dg)[4], u32 (&vv)[4], u32 (&cs)[4]) {
+            const char *srow[4];
+#pragma clang loop unroll(full)
+            for (int k = 0; k < 4; ++k) {
+                const u32 bl = (cur_lo >> (8 * k)) & 0xFF;
+#if PC_DUAL
+                srow[k] = (const char *)s_tab + (u32)lut_one[bl];
+#else
+                const u32 bh = (cur_hi >> (8 * k)) & 0xFF;
+                srow[k] = (const char *)s_tab + ((u32)lut_lo[bl] + (u32)lut_hi[one_stream ? bl : bh]);
+#endif
+            }
+            u32 t[4] = {NEG2, NEG2, NEG2, NEG2};
+#pragma clang loop unroll(full)
+            for (int r = PC_R0; r < R; ++r) {
+                const uint2 tu = s_low[(r - PC_R0) * 64 + lane];
+                u32 h = tu.y, tl = tu.x;                                              // H~(r, j0 - 1), T~(r, j0 - 1)
+#pragma clang loop unroll(full)
+                for (int k = 0; k < 4; ++k) {
+                    h = pk_maxq(h, tl);                                               // H~(r, j0 + k)
+                    const u32 sk = *(const u32 *)(srow[k] + 4 * COMBO[r]);
+                    const u32 dnext = tl;                                             // T~(r, j0 + k - 1): the next row's diagonal
+                    tl = pk_add(pk_maxq(pk_maxq(pk_add(dg[k], sk), h), vv[k]), OE2);  // T~(r, j0 + k)
+                    vv[k] = pk_maxq(vv[k], tl);
+                    dg[k] = dnext;
+                    t[k] = tl;
+                }
+                s_low[(r - PC_R0) * 64 + lane] = make_uint2(tl, h);                   // U = H~(r, j0 + 3): the one-column convention
+            }
+            u32 tk = top;                                     // (top is T~(0, j0 + 3) now)
+#pragma clang loop unroll(full)
+            for (int k = 3; k >= 0; --k) { cs[k] = pk_sub(t[k], tk); tk = pk_sub(tk, EPS2); }
+        };
+#endif
         int jj = 0;                                           // columns since the last renormalisation
         bool u_ahead = false;                                 // wave-uniform, packed fp16 only: U[] already holds the coming column's H (column2)
-        for (int j0 = 1; j0 <= nmax; j0 += 4) {
-            // the dword this block hands on at its end is the one two blocks ahead (0-based column j0 + 7); when
-            // that opens a new 16-column block, the old one is used up -- its last dword is already in nxt -- and
-            // the new one is requested here, a whole 4-column block of arithmetic before it is needed
+        // the dword a block hands on at its end is the one two blocks ahead (0-based column j0 + 7); when
+        // that opens a new 16-column block, the old one is used up -- its last dword is already in nxt -- and
+        // the new one is requested at the block's head, a whole 4-column block of arithmetic before it is needed
+        auto block_head = [&](const int j0) {
             const int kq = ((j0 + 7) >> 2) & 3;
             if (kq == 0) {
                 q_lo = load_q(w_lo, n_lo, j0 + 7);
@@ -747,6 +857,90 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 top = pk_sub(top, DK);
                 jj = 0;
             }
+        };
+        auto block_tail = [&](const int j0) {
+            const int kq = ((j0 + 7) >> 2) & 3;
+            jj += 4;
+            cur_lo = nxt_lo; cur_hi = nxt_hi;
+            nxt_lo = pick_dw(q_lo, kq);
+            if (!one_stream) nxt_hi = pick_dw(q_hi, kq);
+        };
+        for (int j0 = 1; j0 <= nmax; j0 += 4) {
+            block_head(j0);
+#if PC_SKIP
+            if (j0 > tfmax && j0 + 3 < nmin) {
+                // a stretch of fast-path blocks: the upper rows' U one column ahead, the rows below r0 into LDS -- with a window:
+                // a path may have left row r0 in any column the one-column path ran
+                if (packed_ahead) unpack_best();
+                best2 = packbest(bs_lo, bs_hi);
+                pos2 = ((u32)bj_lo & 0xFFFFu) | ((u32)bj_hi << 16);
+#pragma clang loop unroll(full)
+                for (int r = 0; r < PC_R0; ++r) U[r] = pk_maxq(U[r], T[r]);
+#pragma clang loop unroll(full)
+                for (int r = PC_R0; r < R; ++r) s_low[(r - PC_R0) * 64 + lane] = make_uint2(T[r], U[r]);
+                low_until = j0 + 3 + skip_w; low_on = true;
+                count_from = 0x7FFFFFFF;
+                for (;;) {
+                    // (three sets of substitution terms in flight, not four; row r0's interface of the first column pair
+                    // stays in registers over the second)
+                    fetch_S(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
+                    fetch_S(SC, (cur_lo >> 16) & 0xFF, (cur_hi >> 16) & 0xFF);
+                    const u32 tprev = T[PC_R0 - 1];           // T~(r0, j0 - 1)
+                    u32 t0, t1, t2, t3;                       // M(r0, .) + r0 * eps of the four columns
+                    column2(RowsT<PC_R0>{}, SA, SB, t0, t1);
+                    const u32 p_x0 = if_x0, p_x1 = if_x1, p_va = if_va, p_vb = if_vb, p_m0 = T[PC_R0 - 2], p_m1 = T[PC_R0 - 1];
+                    fetch_S(SD, cur_lo >> 24, cur_hi >> 24);
+                    fetch_S(SA, nxt_lo & 0xFF, nxt_hi & 0xFF);
+                    column2(RowsT<PC_R0>{}, SC, SD, t2, t3);
+                    const u32 tr = pk_max(pk_max(pk_max(t0, t1), pk_max(t2, t3)), a.skip_thr2);
+                    if (__any(tr != a.skip_thr2)) { low_until = j0 + 3 + skip_w; if (j0 < count_from) count_from = j0; }
+                    if (j0 <= low_until) {
+                        u32 dg[4] = {tprev, p_x1, p_m1, if_x1};
+                        u32 vv[4] = {pk_maxq(pk_maxq(p_va, p_x0), p_x1), pk_maxq(pk_maxq(p_vb, p_m0), p_m1),
+                                     pk_maxq(pk_maxq(if_va, if_x0), if_x1), pk_maxq(pk_maxq(if_vb, T[PC_R0 - 2]), T[PC_R0 - 1])};
+                        u32 cs[4];
+                        lower_block(dg, vv, cs);
+                        low_on = true;
+                        if (j0 >= count_from) ++n_low;
+                        const u32 nb = pk_max(pk_max(best2, pk_max(cs[0], cs[1])), pk_max(cs[2], cs[3]));
+                        if (__any(nb != best2)) take_maxima(RowsT<4>{}, cs, nb, j0);
+                    } else if (low_on) {                      // the window has run out: nothing stale for a later one to read
+#pragma clang loop unroll(full)
+                        for (int r = PC_R0; r < R; ++r) s_low[(r - PC_R0) * 64 + lane] = make_uint2(NEG2, NEG2);
+                        low_on = false;
+                        if (j0 < count_from) count_from = j0;
+                    }
+                    block_tail(j0);
+                    j0 += 4;
+                    if (!(j0 + 3 < nmin)) break;
+                    const int kq = ((j0 + 7) >> 2) & 3;
+                    if (kq == 0) {
+                        q_lo = load_q(w_lo, n_lo, j0 + 7);
+                        if (!one_stream) q_hi = load_q(w_hi, n_hi, j0 + 7);
+                    }
+                    if (jj >= PC_KREN) {                          // the renormalisation, with the rows below r0 where they are
+                        const u32 DK = pack2(PC_KREN * PC_EPS);
+#pragma clang loop unroll(full)
+                        for (int r = 0; r < PC_R0; ++r) { T[r] = pk_sub(T[r], DK); U[r] = pk_sub(U[r], DK); }
+#pragma clang loop unroll(full)
+                        for (int r = PC_R0; r < R; ++r) {
+                            const uint2 tu = s_low[(r - PC_R0) * 64 + lane];
+                            s_low[(r - PC_R0) * 64 + lane] = make_uint2(pk_sub(tu.x, DK), pk_sub(tu.y, DK));
+                        }
+                        top = pk_sub(top, DK);
+                        jj = 0;
+                    }
+                }
+                // the stretch is over: the rows below r0 back into their registers, as they stand (the upper rows' U needs no
+                // conversion: the one-column path computes max(U, T), which is U)
+#pragma clang loop unroll(full)
+                for (int r = PC_R0; r < R; ++r) { const uint2 tu = s_low[(r - PC_R0) * 64 + lane]; T[r] = tu.x; U[r] = tu.y; }
+                if (count_from < j0) n_pair += (u32)(j0 - count_from) / 4;
+                if (j0 > nmax) break;
+                block_head(j0);
+            }
+            {
+#else
             if (!PC_CHECK_RANGE && j0 > tfmax && j0 + 3 < nmin) {
                 u32 c0, c1, c2, c3;
 #if PC_F16
@@ -759,36 +953,16 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 fetch_S(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
                 fetch_S(SC, (cur_lo >> 16) & 0xFF, (cur_hi >> 16) & 0xFF);
                 fetch_S(SD, cur_lo >> 24, cur_hi >> 24);
-                column2(SA, SB, c0, c1);
+                column2(RowsT<R>{}, SA, SB, c0, c1);
                 fetch_S(SA, nxt_lo & 0xFF, nxt_hi & 0xFF);
-                column2(SC, SD, c2, c3);
+                column2(RowsT<R>{}, SC, SD, c2, c3);
                 const u32 nb = pk_max(pk_max(best2, pk_max(c0, c1)), pk_max(c2, c3));
                 if (__any(nb != best2)) {
-                    // a new maximum somewhere in the block: resolve the column, in visiting order (strict '>',
-                    // the earlier column wins)
                     const u32 cs[4] = {c0, c1, c2, c3};
-                    if (nmax <= 65000) {
-                        u32 b = best2, ps = pos2;
-#pragma clang loop unroll(full)
-                        for (int k = 0; k < 4; ++k) {
-                            const u32 m = pk_maxq(b, cs[k]);
-                            const u32 f = pk_minu(m ^ b, ONE2);              // 1 in the halves where column k is a new maximum
-                            const u32 jk = (u32)(j0 + k) * 0x00010001u;
-                            ps = pk_madu(f, pk_subu(jk, ps), ps);            // their column becomes j0 + k
-                            b = m;
-                        }
-                        best2 = b; pos2 = ps; packed_ahead = true;
-                    } else {                                                  // columns beyond u16: the plain way
-#pragma clang loop unroll(full)
-                        for (int k = 0; k < 4; ++k) {
-                            const int cl = lo16(cs[k]) - R * PC_EPS, ch = hi16(cs[k]) - R * PC_EPS;
-                            if (cl > bs_lo) { bs_lo = cl; bi_lo = a.m_lo; bj_lo = j0 + k; }
-                            if (ch > bs_hi) { bs_hi = ch; bi_hi = a.m_hi; bj_hi = j0 + k; }
-                        }
-                        best2 = nb;
-                    }
+                    take_maxima(RowsT<4>{}, cs, nb, j0);
                 }
             } else {
+#endif
 #if PC_CHECK_RANGE
 #define PC_NOTE note_range();
 #else
@@ -815,10 +989,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 best2 = packbest(bs_lo, bs_hi);
                 pos2 = ((u32)bj_lo & 0xFFFFu) | ((u32)bj_hi << 16);
             }
-            jj += 4;
-            cur_lo = nxt_lo; cur_hi = nxt_hi;
-            nxt_lo = pick_dw(q_lo, kq);
-            if (!one_stream) nxt_hi = pick_dw(q_hi, kq);
+            block_tail(j0);
         }
         if (packed_ahead) unpack_best();
         // ---- the reads' last columns, all lanes at once: rolled re-run of the column from the parked
@@ -873,6 +1044,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 }
             }
         }
+#if PC_SKIP
+        if (a.skip_count && lane == 0 && n_pair) { atomicAdd(a.skip_count, (unsigned long long)n_pair); atomicAdd(a.skip_count + 1, (unsigned long long)n_low); }
+#endif
 #if PC_CHECK_RANGE
         {
             const int hi = lo16(vmax) > hi16(vmax) ? lo16(vmax) : hi16(vmax);

@@ -32,6 +32,7 @@ struct Options {
     bool no_score_fork = false;         // PC_NO_SCORE_FORK (per call): a score-only call's launches on one stream
     int force_chunks = 0;               // PC_FORCE_CHUNKS (per call); < 1: by the fill
     bool no_end_floor = false;          // PC_NO_END_FLOOR (per call): an end rule handed to the scan is ignored
+    bool no_row_skip = false;           // PC_NO_ROW_SKIP (per call): the score pass of a floored call computes every row in every column
 };
 
 // What the rules below need to know of the context.
@@ -562,6 +563,24 @@ inline bool floored(const Group &g, int mode, const Floors &f)
     for (size_t s = 0; s < g.nseg; ++s) if (seg_floor_of(g, s, f) != INT32_MIN) return true;
     return false;
 }
+// The score pass of a floored group may skip the adapter rows no alignment that reaches its floor can reach (pcb::row_skip_plan;
+// the specialised packed-fp16 kernel only).  A launch scans one adapter per half for every job that names it, so its floor for
+// adapter `ad` is the lowest floor of those jobs, and INT32_MIN -- no skipping -- as soon as one of them has none.  Not for a
+// ruled group (its test is not a plain floor), nor for PC_MODE_SCORE or an unfloored call, which return true scores.
+inline int32_t launch_floor(const int32_t *job_adapter, const int32_t *job_adapter_b, int njobs, const Floors &f, int ad)
+{
+    int64_t lowest = INT64_MAX;
+    for (int j = 0; j < njobs; ++j) {
+        if (job_adapter[j] == ad) lowest = std::min<int64_t>(lowest, f.a ? f.a[j] : INT32_MIN);
+        if (job_adapter_b && job_adapter_b[j] == ad) lowest = std::min<int64_t>(lowest, f.b ? f.b[j] : INT32_MIN);
+    }
+    return lowest == INT64_MAX ? INT32_MIN : (int32_t)lowest;
+}
+inline bool row_skip_allowed(const Params &p, const Group &g, int mode, const Floors &f)
+{
+    return !p.opt.no_row_skip && !f.rule_side && floored(g, mode, f);
+}
+
 // A call with an end rule (pc_scan_device_end_rule) takes the same route with another test: between the passes the pairs of
 // which pc_end_rule.h proves, from their score records and window lengths, that they cannot trim their read are answered by
 // the planner and put behind the others.  The windows are short (end windows, 150 columns), so pass 2 is what PC_MODE_TRACE_AT

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Compile the run-time specialised kernel source OFFLINE (hipcc -S) for one adapter pair, to look
-at its ISA / register use without a GPU.   python tools/dump_spec.py [--int16] [AD_LO AD_HI] > x.s"""
+at its ISA / register use without a GPU.   python tools/dump_spec.py [--int16] [--r0=N] [AD_LO AD_HI] > x.s
+--r0=N: with the row-skipping fast path at register row N (the library's rule: pcb::row_skip_r0)."""
 import os, re, subprocess, sys, tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 src = open(os.path.join(HERE, "..", "porechop_amd", "csrc", "pc_jit_source.h")).read()
@@ -26,6 +27,7 @@ lim = 2040 if f16 else 32000
 kren = min((2 * lim - (high - low) - (R + 6) * eps) // eps // 4 * 4, 1 << 20)
 defs = ["-DPC_R=%d" % R, "-DPC_K=%d" % K, "-DPC_COMBO_INIT=" + ",".join(map(str, rows)), "-DPC_F16=%d" % f16,
         "-DPC_EPS=%d" % eps, "-DPC_OE=(%d)" % (go + eps), "-DPC_CEN=(%d)" % (low + lim), "-DPC_KREN=%d" % kren, "-DPC_WAVES=%s" % __import__("os").environ.get("PC_JIT_WAVES", "2"), "-DPC_CHECK_RANGE=%d" % ("--check" in sys.argv), "-DPC_DUAL=%d" % (lo != hi)]
+defs += ["-DPC_R0=" + a[5:] for a in sys.argv[1:] if a.startswith("--r0=")]
 with tempfile.TemporaryDirectory() as d:
     p = os.path.join(d, "k.hip")
     open(p, "w").write("#include <hip/hip_runtime.h>\n" + src)
