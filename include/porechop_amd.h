@@ -108,6 +108,31 @@ void pc_destroy(pc_ctx *ctx);
  * tables).  Magnitudes above 2^20 are refused and leave the scheme as it was. */
 int pc_set_scores(pc_ctx *ctx, int match, int mismatch, int gap_open, int gap_extend);
 
+/* IUPAC wildcards in ADAPTERS, a property of the context; off by default, and with it off every byte this library returns
+ * is what it was before the mode existed.  With it on an adapter letter stands for a set of bases (csrc/pc_letters.h, the
+ * one copy of the rule): A C G T, U = T, R = AG, Y = CT, S = CG, W = AT, K = GT, M = AC, B = CGT, D = AGT, H = ACT,
+ * V = ACG, N = ACGT, either case, any other byte the empty set.  Read bytes stay Dna5: a cell scores `match` iff the read
+ * base is one of A/C/G/T(U) and lies in the adapter letter's set, `mismatch` otherwise -- a read's N, '-' or IUPAC letter
+ * matches nothing, not even adapter N, so a stretch masked by mask-and-realign is never a hit.  Recurrence, tie rules,
+ * scout, traceback, digest and the two identities are unchanged; in a path '=' is a match under this rule.
+ *   * An adapter of A/C/G/T/U alone gives the same records in both modes.  Every kernel takes the rule from a table of the
+ *     rows' sets uploaded with the panel: trace16_kernel's substitution table, scan_kernel's wildcard variants, the specialised
+ *     score kernels' tables (letters told apart by set; the in-memory kernel cache is keyed by the mode, the generated options
+ *     of adapters without degenerate letters are unchanged), the plain-int32 and path kernels.  All modes, floors and the end
+ *     rule work as without wildcards.  Under a scheme with max(match - mismatch, match) > 2048 scan_kernel's wildcard variants
+ *     are not exact and are not launched at all: the adapters with other letters take the plain-int32 kernel (said once on
+ *     stderr; PC_MODE_SCORE is then refused for them), every other adapter of the context the kernels it takes without
+ *     wildcards, which are exact for it.
+ *   * The prefilter stays a proof: a row's Eq bit is set for every base of its set, a piece with a degenerate letter has
+ *     no seeds, and pc_prefilter_packed answers PC_ERR_UNSUPPORTED_SCORES for a list it cannot seed completely, as ever.
+ *   * Like pc_set_scores this only marks the panel dirty: the next call that needs the panel re-derives and uploads it and
+ *     drops the cached tile table and prefilter plan.  May be toggled on a live context between any two calls.
+ *   * The per-call adapterAlignment symbol below never uses wildcards.
+ * pc_letter_set: the 5-bit set over read codes 0..4 (A, C, G, T/U, other) of an adapter byte in either mode -- off: the
+ * byte's own Dna5 code alone (N == N); on: the table above, bit 4 never set.  0 for a byte outside 0..255. */
+int pc_set_wildcards(pc_ctx *ctx, int enabled);
+int pc_letter_set(int byte, int wildcards);
+
 /* Upload the adapter panel (the strings of porechop/adapters.py ADAPTERS start/end sequences
  * or any other): adapter index i in the calls below refers to seqs[i]. */
 int pc_set_adapters(pc_ctx *ctx, const char *const *seqs, int nadapters);

@@ -27,6 +27,7 @@ EXPORTS = [
     "pc_scan_device_floored", "pc_floor_skipped", "pc_scan_device_end_rule", "pc_set_row_skip_debug", "pc_row_skip_blocks", "pc_jit_precompile_row_skip",
     "pc_align_paths", "pc_path_cigar",
     "pc_middle_paths", "pc_middle_paths_cols",
+    "pc_set_wildcards", "pc_letter_set",
 ]
 
 
@@ -110,6 +111,10 @@ def load_library():
     L.pc_set_length_hint.restype = c_int
     L.pc_set_int16_only.argtypes = [c_vp, c_int]
     L.pc_set_int16_only.restype = c_int
+    L.pc_set_wildcards.argtypes = [c_vp, c_int]
+    L.pc_set_wildcards.restype = c_int
+    L.pc_letter_set.argtypes = [c_int, c_int]
+    L.pc_letter_set.restype = c_int
     L.pc_set_timing.argtypes = [c_vp, c_int]
     L.pc_set_timing.restype = c_int
     L.pc_get_timing.argtypes = [c_vp, c_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]

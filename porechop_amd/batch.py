@@ -131,6 +131,20 @@ def render_alignment(read, adapter, head, opstring):
     return "\n".join(("".join(top), "".join(mid), "".join(bot)))
 
 
+def letter_set(byte, wildcards):
+    """The set of read codes (bit k: Dna5 code k = A, C, G, T/U, other) an adapter byte matches, with IUPAC wildcards on or
+    off.  The table is the library's (csrc/pc_letters.h through pc_letter_set): there is no second copy of it here."""
+    if isinstance(byte, (str, bytes)):
+        byte = ord(byte)
+    key = (int(byte), bool(wildcards))
+    if key not in _LETTER_SETS:
+        _LETTER_SETS[key] = int(load_library().pc_letter_set(key[0], 1 if key[1] else 0))
+    return _LETTER_SETS[key]
+
+
+_LETTER_SETS = {}                # (byte, mode) -> set, as the library answered
+
+
 class Aligner:
     """One GPU context: a scoring scheme + an adapter panel + scratch buffers."""
     fast_prefilter = True      # prefilter_rows is the device's exact prefilter (callers may put it in front of the middle scan)
@@ -141,12 +155,14 @@ class Aligner:
     paths = True               # align_paths / align_pairs_paths: records with the alignment's path (pc_align_paths)
     # (middle_paths, the method below, is its own flag: callers ask getattr(aligner, "middle_paths", False))
 
-    def __init__(self, adapters, scores=DEFAULT_SCORES, device=-1):
+    def __init__(self, adapters, scores=DEFAULT_SCORES, device=-1, wildcards=False):
         self.lib = load_library()
         self._ctx = ctypes.c_void_p()
         check(self.lib.pc_create(ctypes.byref(self._ctx), device), "pc_create")
         self.scores = tuple(int(s) for s in scores)
         check(self.lib.pc_set_scores(self._ctx, *self.scores), "pc_set_scores")
+        self.wildcards = False
+        self.set_wildcards(wildcards)
         self.set_adapters(adapters)
 
     def set_adapters(self, adapters):
@@ -161,6 +177,14 @@ class Aligner:
         scores = tuple(int(s) for s in scores)
         check(self.lib.pc_set_scores(self._ctx, *scores), "pc_set_scores")
         self.scores = scores
+
+    def set_wildcards(self, enabled=True):
+        """IUPAC wildcards in the adapters of the live context (pc_set_wildcards; off by default): an adapter letter stands for
+        its set of bases, a read base that is not A/C/G/T/U matches nothing.  Everything derived from the panel is worked out
+        again at the next call.  Every DP kernel takes the adapters as sets, the specialised score kernels included (compiled per
+        pair as ever; declined only where the letter pairs outgrow the register plan)."""
+        check(self.lib.pc_set_wildcards(self._ctx, 1 if enabled else 0), "pc_set_wildcards")
+        self.wildcards = bool(enabled)
 
     def close(self):
         if self._ctx:

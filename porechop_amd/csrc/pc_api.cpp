@@ -77,8 +77,12 @@ struct pc_ctx {
     int match = 3, mismatch = -6, gap_open = -5, gap_extend = -2;
     std::vector<std::string> adapters;
     std::vector<int> ad_len, ad_window, ad_span;
+    bool wildcards = false;                  // pc_set_wildcards: adapter letters are IUPAC sets (pc_letters.h)
+    bool wild_packed = false;                // upload_panel: wildcards are on AND the scheme fits scan_kernel's wildcard compare, so the
+                                             // launches of this context take the wildcard variants; otherwise the plain ones (the
+                                             // degenerate adapters then run the plain-int32 kernel, the others are exact as they are)
     bool panel_dirty = true;
-    DevBuf d_ad_codes, d_ad_len, d_ad_window, d_ad_span;
+    DevBuf d_ad_codes, d_ad_sets, d_ad_len, d_ad_window, d_ad_span;    // d_ad_sets: d_ad_codes' layout, pcl::letter_set per row
     DevBuf d_slab, d_fin, d_k1, d_woff2, d_wlen2, d_col0, d_ntot, d_frow, d_fscore, d_tcols, d_perm, d_bucket_cnt, d_bucket_slot[2], d_err;
     // the tile table lives in one of two slots: a new table is built (on the context's own stream) in the slot
     // the scans two tables ago used, so building never waits for the scans in flight on the current one
@@ -111,7 +115,7 @@ struct pc_ctx {
     bool row_skip_debug = false; // pc_set_row_skip_debug: the row-skipping score launches count their column pairs
     // the prefilter: the plan (pc_prefilter_plan.h) of the last (adapter list, edit bounds, route), its tables on the device
     struct PfCache {
-        std::vector<int32_t> key;            // adapters..., max_edits..., route; empty: the device holds no plan
+        std::vector<int32_t> key;            // adapters..., max_edits..., route, wildcards; empty: the device holds no plan
         pcp::Plan plan;
     } pf;
     DevBuf d_pf_tables, d_pf_meta;           // exhaustive kernel: Eq tables + piece metadata
@@ -126,7 +130,7 @@ struct pc_ctx {
     pcn::Table table;                        // the plan of the last job list (pc_scan_plan.h): groups, plain-int32 jobs, total
     bool slow_scheme = false;                // the scoring scheme itself is outside the packed kernels' exact range
     std::vector<char> ad_slow;               // per adapter: takes the plain-int32 kernel
-    std::vector<int64_t> slow_ad_off;        // offsets of the adapters' Dna5 codes in d_slow_ad
+    std::vector<int64_t> slow_ad_off;        // offsets of the adapters' letter sets (one byte per row) in d_slow_ad
     DevBuf d_slow_ad, d_slow_state, d_slow_trace;
     DevBuf d_paths_trace;                    // pc_align_paths: the packed trace of one launch (pc_paths.hip)
     DevBuf d_middle_paths_trace;             // pc_middle_paths: the same for its windows, a buffer of its own
@@ -161,12 +165,20 @@ int upload_panel(pc_ctx *c)
     if (!c->panel_dirty) return PC_OK;
     const int n = (int)c->adapters.size();
     std::vector<uint32_t> codes((size_t)std::max(n, 1) * pcb::MAX_ADAPTER, 5u);
+    std::vector<uint32_t> sets(codes.size(), 0u);
     c->ad_len.assign(std::max(n, 1), 0);
     c->ad_window.assign(std::max(n, 1), 0);
     c->ad_span.assign(std::max(n, 1), 0);
     int maxm = 1;
     // Adapters above pcb::MAX_ADAPTER bases, and every adapter under a scheme outside the packed kernels' exact range,
-    // take the plain-int32 kernel (pc_slow.hip): the reference accepts any adapter and any four integers.
+    // take the plain-int32 kernel (pc_slow.hip): the reference accepts any adapter and any four integers.  With wildcards on the
+    // packed kernels read the adapters as sets (trace16_kernel's table, scan_kernel's wildcard variants: pc_kernels.hip); the
+    // variants' compare needs 2^kWildShift >= max(match - mismatch, match), and under a scheme beyond that an adapter with a
+    // letter the mode reads differently (anything but A/C/G/T/U) takes the plain-int32 kernel too.
+    int wild_slow = 0;
+    std::vector<char> wild(std::max(n, 1), 0);        // per adapter: it holds a letter the mode reads differently
+    const bool wild_fits = std::max((long long)c->match - c->mismatch, (long long)c->match) <= (1ll << pck::kWildShiftHost);
+    c->wild_packed = c->wildcards && wild_fits;
     c->ad_slow.assign(std::max(n, 1), 0);
     c->slow_ad_off.assign(std::max(n, 1) + 1, 0);
     std::vector<uint8_t> raw;
@@ -175,10 +187,19 @@ int upload_panel(pc_ctx *c)
         if ((int)s.size() > pcs::MAX_ADAPTER) return PC_ERR_ADAPTER_TOO_LONG;
         c->ad_len[i] = (int)s.size();
         c->slow_ad_off[i] = (int64_t)raw.size();
-        for (char ch : s) raw.push_back((uint8_t)dna5((unsigned char)ch));
+        bool degenerate = false;
+        for (char ch : s) {
+            raw.push_back((uint8_t)pcl::letter_set((uint8_t)ch, c->wildcards));
+            degenerate |= c->wildcards && pcl::degenerate((uint8_t)ch);
+        }
+        if (degenerate) wild[i] = 1;
+        if (degenerate && !wild_fits) { c->ad_slow[i] = 1; ++wild_slow; }
         if ((int)s.size() > pcb::MAX_ADAPTER) { c->ad_slow[i] = 1; continue; }
         maxm = std::max(maxm, (int)s.size());
-        for (size_t k = 0; k < s.size(); ++k) codes[(size_t)i * pcb::MAX_ADAPTER + k] = (uint32_t)dna5((unsigned char)s[k]);
+        for (size_t k = 0; k < s.size(); ++k) {
+            codes[(size_t)i * pcb::MAX_ADAPTER + k] = (uint32_t)dna5((unsigned char)s[k]);
+            sets[(size_t)i * pcb::MAX_ADAPTER + k] = pcl::letter_set((uint8_t)s[k], c->wildcards);
+        }
     }
     c->slow_ad_off[std::max(n, 1)] = (int64_t)raw.size();
     if (!pcs::fits(0, 0, c->match, c->mismatch, c->gap_open, c->gap_extend)) return PC_ERR_UNSUPPORTED_SCORES;
@@ -197,10 +218,18 @@ int upload_panel(pc_ctx *c)
     {
         // said once per process and cause: the answers are the reference's either way, but a user should know that the run left the
         // fast kernels (PC_QUIET=1 silences it)
-        static bool told_scheme = false, told_adapter = false;
+        static bool told_scheme = false, told_adapter = false, told_wild = false;
         static const bool quiet = [] { const char *e = getenv("PC_QUIET"); return e && *e && *e != '0'; }();
         int longest_slow = 0;
-        for (int i = 0; i < n; ++i) if (c->ad_slow[i] && !c->slow_scheme) longest_slow = std::max(longest_slow, c->ad_len[i]);
+        for (int i = 0; i < n; ++i)
+            if (c->ad_slow[i] && !c->slow_scheme && (!wild[i] || c->ad_len[i] > pcb::MAX_ADAPTER)) longest_slow = std::max(longest_slow, c->ad_len[i]);
+        if (wild_slow > 0 && !c->slow_scheme && !told_wild && !quiet) {
+            told_wild = true;
+            fprintf(stderr, "porechop_amd: wildcards are on and match - mismatch = %d is beyond what the packed kernels' wildcard compare holds "
+                            "(%d): the alignments of the %d adapter(s) with letters other than A/C/G/T/U run the plain-int32 kernel -- the same "
+                            "answers, roughly a hundred times slower per cell, and none of the exact prunings\n",
+                    c->match - c->mismatch, 1 << pck::kWildShiftHost, wild_slow);
+        }
         if (c->slow_scheme && n > 0 && !told_scheme && !quiet) {
             told_scheme = true;
             fprintf(stderr, "porechop_amd: scoring scheme %d,%d,%d,%d is outside the packed 16-bit kernels' exact range (they need match > 0, "
@@ -220,10 +249,11 @@ int upload_panel(pc_ctx *c)
     // (Only when the panel or the scores change.)
     HIP_TRY(hipDeviceSynchronize());
     int rc;
-    if ((rc = c->d_ad_codes.ensure(codes.size() * 4)) || (rc = c->d_ad_len.ensure(c->ad_len.size() * 4)) ||
+    if ((rc = c->d_ad_codes.ensure(codes.size() * 4)) || (rc = c->d_ad_sets.ensure(sets.size() * 4)) || (rc = c->d_ad_len.ensure(c->ad_len.size() * 4)) ||
         (rc = c->d_ad_window.ensure(c->ad_window.size() * 4)) || (rc = c->d_ad_span.ensure(c->ad_span.size() * 4)))
         return rc;
     HIP_TRY(hipMemcpy(c->d_ad_codes.p, codes.data(), codes.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_ad_sets.p, sets.data(), sets.size() * 4, hipMemcpyHostToDevice));
     if ((rc = c->d_slow_ad.ensure(raw.size() + 16))) return rc;
     if (!raw.empty()) HIP_TRY(hipMemcpy(c->d_slow_ad.p, raw.data(), raw.size(), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(c->d_ad_len.p, c->ad_len.data(), c->ad_len.size() * 4, hipMemcpyHostToDevice));
@@ -415,14 +445,15 @@ void plan_scan(pc_ctx *c, ScanCall &s)
         // a floored group owes exact records only to pairs that reach their floor: where the pair has the row-skipping kernel
         // and the launch's floors give it thresholds, that one (pc_bounds.h row_skip_plan)
         if (skip_ok) {
-            pcj::Spec *sk = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only, true);
+            pcj::Spec *sk = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only, true, c->wildcards);
             pcj::SpecArgs probe;
             if (sk && pcj::row_skip_args(sk, c->match, c->mismatch, c->gap_open, c->gap_extend,
                                          pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, lo),
                                          pcn::launch_floor(s.job_adapter, s.job_adapter_b, s.njobs, s.floors, hi), probe))
                 return pcn::SpecKernel{sk, sk->blocks_per_cu};
         }
-        pcj::Spec *sp = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only);
+        pcj::Spec *sp = pcj::get(c->device, c->adapters[lo], c->adapters[hi], c->match, c->mismatch, c->gap_open, c->gap_extend, cells, c->int16_only,
+                                 false, c->wildcards);
         return pcn::SpecKernel{sp, sp ? sp->blocks_per_cu : 0};
     };
     s.score_plan.assign(groups.size(), {});
@@ -501,6 +532,8 @@ pck::ScanArgs group_args(const pc_ctx *c, const ScanCall &s, size_t gi)
     a.arena = (const uint8_t *)s.arena;
     a.win_off = s.win_off; a.win_len = s.win_len;
     a.ad_codes = c->d_ad_codes.as<uint32_t>();
+    a.ad_sets = c->d_ad_sets.as<uint32_t>();
+    a.wild = c->wild_packed ? 1 : 0;
     a.ad_len = c->d_ad_len.as<int32_t>();
     a.tiles = c->d_tiles_slot[c->slot].as<pck::Tile>() + g.tile_begin;
     a.ntiles = (int32_t)g.tile_count;
@@ -869,7 +902,7 @@ void pc_destroy(pc_ctx *c)
     }
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    DevBuf *bufs[] = {&c->d_ad_codes, &c->d_ad_len, &c->d_ad_window, &c->d_ad_span, &c->d_tiles_slot[0], &c->d_tiles_slot[1],
+    DevBuf *bufs[] = {&c->d_ad_codes, &c->d_ad_sets, &c->d_ad_len, &c->d_ad_window, &c->d_ad_span, &c->d_tiles_slot[0], &c->d_tiles_slot[1],
                       &c->d_runs_slot[0], &c->d_runs_slot[1], &c->d_slab, &c->d_fin, &c->d_k1, &c->d_woff2,
                       &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
@@ -893,6 +926,24 @@ int pc_set_scores(pc_ctx *c, int match, int mismatch, int gap_open, int gap_exte
         c->panel_dirty = true;
     }
     return PC_OK;
+}
+
+int pc_set_wildcards(pc_ctx *c, int enabled)
+{
+    if (!c) return PC_ERR_BAD_ARG;
+    // everything derived from the panel's letters is redone by the next call (upload_panel: the letter sets, which adapters leave
+    // the packed kernels, the tile table; the prefilter plan's key holds the mode itself)
+    if ((enabled != 0) != c->wildcards) {
+        c->wildcards = enabled != 0;
+        c->panel_dirty = true;
+    }
+    return PC_OK;
+}
+
+int pc_letter_set(int byte, int wildcards)
+{
+    if (byte < 0 || byte > 255) return 0;
+    return (int)pcl::letter_set((uint8_t)byte, wildcards != 0);
 }
 
 int pc_set_int16_only(pc_ctx *c, int enabled)
@@ -1043,7 +1094,7 @@ int paths_setup(pc_ctx *c, int cols, int rows, int max_len, int64_t n, DevBuf &s
     const int64_t P = pcn::slice_pairs(budget, per_lane, n);
     const int rc = scratch.ensure((size_t)P * per_lane + 256);
     if (rc) return rc;
-    a.ad_codes = c->d_ad_codes.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
+    a.ad_sets = c->d_ad_sets.as<uint32_t>(); a.ad_len = c->d_ad_len.as<int32_t>(); a.nadapters = (int32_t)c->adapters.size();
     a.rows = rows; a.groups = groups; a.max_len = max_len;
     a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
     a.trace = scratch.as<uint32_t>(); a.P = P; a.err = c->d_err.as<uint32_t>();
@@ -1484,6 +1535,7 @@ int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     std::vector<int32_t> key(adapters, adapters + nadapters);
     key.insert(key.end(), max_edits, max_edits + nadapters);
     key.push_back((int32_t)route);
+    key.push_back(c->wildcards ? 1 : 0);
     if (key != c->pf.key) {
         // PC_PF_NO_SEEDS=1: exhaustive kernel only; PC_PF_MULTI_Q=1 / PC_PF_SINGLE_Q=1 force the seed-length choice (read once per process)
         static const pcp::Options options = [] {
@@ -1493,7 +1545,7 @@ int prefilter_impl(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
             return o;
         }();
         pcp::Plan fresh;
-        if (pcp::build(c->adapters, adapters, max_edits, nadapters, route, options, fresh)) return PC_ERR_BAD_ARG;
+        if (pcp::build(c->adapters, adapters, max_edits, nadapters, route, options, fresh, c->wildcards)) return PC_ERR_BAD_ARG;
         if (route == pcp::Route::PlaneSeeds && !fresh.launches.empty() && !fresh.seeds_only) return PC_ERR_UNSUPPORTED_SCORES;
         c->pf.key.clear();                    // from here on the device's tables are no longer the cached plan's
         const int rc = upload_plan(c, fresh, stream);

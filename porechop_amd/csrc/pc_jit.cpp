@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "pc_bounds.h"
+#include "pc_letters.h"
 #include "pc_jit_source.h"
 
 namespace pcj {
@@ -123,6 +124,7 @@ struct Recipe {                                // everything the compile step ne
     bool f16;
     long kren, cen;
     bool row_skip = false;                     // the variant whose fast path skips the rows below r0 (a kernel of its own per pair)
+    bool wildcards = false;                    // the adapters' letters are IUPAC sets (pc_letters.h): same source, other letter pairs and table
 };
 
 // Everything about a kernel that follows from its recipe without compiling anything: the hiprtc options (they
@@ -133,17 +135,21 @@ struct Derived {
     int K = 0, waves = 2, r0 = 0;
 };
 
+constexpr int kPadLetter = 32, kLetters = 33;    // a letter is a 5-bit set, or the padding row
+
 Derived derive(const Recipe &rc)
 {
     Derived d;
     const int R = rc.R;
-    // letters per register row of each half (bottom-aligned): 0..4 = Dna5 code, 5 = padding row
-    std::vector<int> lo(R, 5), hi(R, 5);
-    for (int i = 0; i < rc.m_lo; ++i) lo[R - rc.m_lo + i] = dna5((unsigned char)rc.ad_lo[i]);
-    for (int i = 0; i < rc.m_hi; ++i) hi[R - rc.m_hi + i] = dna5((unsigned char)rc.ad_hi[i]);
+    // letters per register row of each half (bottom-aligned): the row's set of read codes (pc_letters.h: one code without
+    // wildcards, so rows are told apart exactly as their Dna5 codes were and the options of such adapters are what they have
+    // always been), kPadLetter = padding row
+    std::vector<int> lo(R, kPadLetter), hi(R, kPadLetter);
+    for (int i = 0; i < rc.m_lo; ++i) lo[R - rc.m_lo + i] = (int)pcl::letter_set((uint8_t)rc.ad_lo[i], rc.wildcards);
+    for (int i = 0; i < rc.m_hi; ++i) hi[R - rc.m_hi + i] = (int)pcl::letter_set((uint8_t)rc.ad_hi[i], rc.wildcards);
     std::vector<int> combo_of_row(R);
     for (int row = 0; row < R; ++row) {
-        const int c = lo[row] * 6 + hi[row];
+        const int c = lo[row] * kLetters + hi[row];
         int k = -1;
         for (size_t i = 0; i < d.combos.size(); ++i) if (d.combos[i] == c) k = (int)i;
         if (k < 0) { k = (int)d.combos.size(); d.combos.push_back(c); }
@@ -194,13 +200,13 @@ std::vector<uint32_t> substitution_table(const Recipe &rc, const Derived &d)
 {
     std::vector<uint32_t> table((size_t)25 * d.K, 0);
     auto term = [&](int letter, int code) -> int {
-        const int sub = letter == 5 ? 0 : (letter == code ? rc.match : rc.mismatch);
+        const int sub = letter == kPadLetter ? 0 : (pcl::matches((unsigned)letter, code) ? rc.match : rc.mismatch);
         return sub - rc.gap_open + rc.eps;
     };
     for (int cl = 0; cl < 5; ++cl)
         for (int ch = 0; ch < 5; ++ch)
             for (size_t k = 0; k < d.combos.size(); ++k) {
-                const int l = term(d.combos[k] / 6, cl), h = term(d.combos[k] % 6, ch);
+                const int l = term(d.combos[k] / kLetters, cl), h = term(d.combos[k] % kLetters, ch);
                 // the table terms are values the kernel adds in its lane type: they must be exact there too
                 // (spec_plan's gate bounds match, mismatch and open for the fp16 variant; asserted here, where they are formed)
                 const int lim = rc.f16 ? pcb::kF16Limit : 32000;
@@ -480,7 +486,7 @@ struct JoinAtExit { ~JoinAtExit() { wait_idle(true); } } g_join_at_exit;
 }  // namespace
 
 Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open,
-          int gap_extend, double cells, bool int16_only, bool row_skip)
+          int gap_extend, double cells, bool int16_only, bool row_skip, bool wildcards)
 {
     if (disabled()) return nullptr;
     const int m_lo = (int)ad_lo.size(), m_hi = (int)ad_hi.size();
@@ -506,13 +512,26 @@ Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int ma
         return nullptr;
     }
     const long cen = plan.cen;
-    char keybuf[64];
+    char keybuf[96];
     if (row_skip) {
         // the row-skipping variant exists for packed fp16 and where the rule finds a row (a function of the recipe alone)
-        const Recipe probe{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, plan.cen, true};
+        const Recipe probe{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, plan.cen, true, wildcards};
         if (!f16 || derive(probe).r0 >= R) return nullptr;
     }
-    snprintf(keybuf, sizeof keybuf, "|%d|%d,%d,%d,%d|%d%s", device, match, mismatch, gap_open, gap_extend, f16 ? 1 : 0, row_skip ? "|skip" : "");
+    if (wildcards) {
+        // degenerate letters make more distinct letter pairs (K) and so more registers: beyond the largest plan Dna5 letters
+        // can ask for (128 rows, 36 pairs) there is no room, and the generic kernel runs
+        const Recipe probe{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, plan.cen, false, true};
+        // (and K itself stays within the 36 pairs Dna5 letters can make: the one-wave plan parks rows, not table terms)
+        const int K = derive(probe).K;
+        if (K > 36 || 2 * R + 4 * K > 2 * pcb::MAX_ADAPTER + 4 * 36) {
+            if (verbose) fprintf(stderr, "porechop_amd: no specialised kernel: too many distinct letter pairs for the register plan\n");
+            return nullptr;
+        }
+    }
+    // (the mode is part of the key: ACGN has the same code object in both modes and another table)
+    snprintf(keybuf, sizeof keybuf, "|%d|%d,%d,%d,%d|%d%s%s", device, match, mismatch, gap_open, gap_extend, f16 ? 1 : 0, row_skip ? "|skip" : "",
+             wildcards ? "|wild" : "");
     const std::string key = ad_lo + "|" + ad_hi + keybuf;
     std::lock_guard<std::mutex> lk(g_mu);
     Entry *&slot = g_cache[key];
@@ -526,7 +545,7 @@ Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int ma
         finalize_entry(e, verbose);
         return e->spec;
     }
-    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, cen, row_skip};
+    const Recipe rc{ad_lo, ad_hi, match, mismatch, gap_open, gap_extend, R, m_lo, m_hi, eps, 2, f16, kren, cen, row_skip, wildcards};
     // a kernel that is already on disk (built with the library for the static panel, or compiled by an earlier
     // process on this machine) costs a file read and a module load: use it from the first launch on
     if (!e->disk_checked) {

@@ -46,8 +46,11 @@ bool disabled();
 // (the launch's work) is added to the pair's running total, and the kernel is compiled once that
 // total reaches PC_JIT_MIN_CELLS (caller uses the generic kernels until then).
 // int16_only: the packed-int16 variant (6 ops per cell pair) even where packed fp16 is exact (pc_set_int16_only).
+// wildcards: the adapters' letters are IUPAC sets (pc_letters.h).  The source is the same; rows are told apart by set, the table
+// scores by pcl::matches, and the mode is part of the in-memory key (ACGN: one code object, two tables).  More distinct letter
+// pairs mean a larger PC_K and more registers; beyond the 36 pairs or the largest plan Dna5 letters can ask for, nullptr.
 Spec *get(int device, const std::string &ad_lo, const std::string &ad_hi, int match, int mismatch, int gap_open,
-          int gap_extend, double cells, bool int16_only = false, bool row_skip = false);
+          int gap_extend, double cells, bool int16_only = false, bool row_skip = false, bool wildcards = false);
 int launch(const Spec *sp, const SpecArgs &a, int grid, void *stream);
 // The row skip of one launch of `sp` under the halves' score floors (INT32_MIN: none): fills a.skip_thr2 / a.skip_w and answers
 // true, or leaves them zero -- the kernel has no skipping path (int16 lanes, the range-recording build, no row qualifies), a

@@ -98,6 +98,9 @@ struct ScanArgs {
                                      // the chunks that hold columns of its longest window (launch_unit_prefix)
     int32_t skip_marked;             // traced pass 2 of a floored call: a pair whose force_row is kSkipRow has its record already
                                      // (plan_kernel) and is not there for the kernel; a tile of such pairs only is left at once
+    const uint32_t *ad_sets;         // [nadapters][128] per row the set of read codes it matches (pc_letters.h), in the context's mode:
+                                     // trace16_kernel's table build, the counted traceback, the wildcard variants of scan_kernel
+    int32_t wild;                    // 1: launch_trace / launch_score take scan_kernel's wildcard variants (kWildShift)
 };
 // unit_prefix of a chunked score pass: one wave per tile takes the tile's longest window, a block scans the counts
 int launch_unit_prefix(const Tile *tiles, int ntiles, const int32_t *win_len, int chunk_len, int32_t *real, int32_t *prefix, void *stream);
@@ -317,6 +320,7 @@ inline bool trace16_has(int rows)
 inline int trace_words_per_col(int rows) { return (rows + 3) / 4; }   // NW: dwords of trace per column and lane
 
 // launchers (pc_kernels.hip); stream is a hipStream_t passed as void*
+constexpr int kWildShiftHost = 11;   // = kWildShift of pc_kernels.hip: scan_kernel's wildcard compare needs match - mismatch, match <= 2^11
 int launch_trace(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
 int launch_score(const ScanArgs &a, int rows, bool pad, int grid, void *stream);
 int launch_trace16(const ScanArgs &a, int rows, int grid, void *stream);   // packed-fp16 traced scan (needs a.f16_*)
@@ -378,7 +382,7 @@ int launch_anchor_inserts(const uint8_t *arena, const int64_t *win_off, const in
 int launch_unpack(const void *packed, int64_t nbases, const int64_t *exc_pos, int64_t nexc, void *arena, int pad, void *stream);
 
 // the plain-int32 kernel of pc_slow.hip: windows first_window .. first_window + count of the caller's table against ONE
-// adapter (m Dna5 codes at `adapter`), records to out[(out_base + i) * 8]; state == nullptr: column state in LDS (m <= 128)
+// adapter (m sets of read codes at `adapter`: pc_letters.h), records to out[(out_base + i) * 8]; state == nullptr: column state in LDS (m <= 128)
 struct SlowArgs {
     const uint8_t *arena;
     const int64_t *win_off;
@@ -405,7 +409,7 @@ struct PathArgs {
     const int32_t *seq_len;      // [n] its bases
     const int32_t *adapter_idx;
     int64_t first, count;
-    const uint32_t *ad_codes;    // [nadapters][kMaxRows] Dna5 codes
+    const uint32_t *ad_sets;     // [nadapters][kMaxRows] per row the set of read codes it matches (pc_letters.h)
     const int32_t *ad_len;       // [nadapters]
     int32_t nadapters;
     int32_t rows, groups;        // longest adapter of the table (LDS rows) and its row groups of eight (scratch)

@@ -106,7 +106,18 @@ template <int R, bool PAD> struct Cfg {
     static constexpr int kNV = (kMode == CONST_REGS) ? R : 1;                       // VGPR array extent
 };
 
-template <int R, bool PAD, bool TRACE>
+// The compare of a read code with a row.  Plain: both sides carry code * D, y = h2 - vc is 0 on equal codes and >= D (as an
+// unsigned lane) otherwise.  WILD (IUPAC wildcards, pc_letters.h): the byte LUT delivers the one-hot of the read code shifted
+// up by kWildShift bits (the unknown code in bit 4 + kWildShift), the row constant is the complement of the row's set --
+// always with the unknown bit; all ones for a padding row -- and y = h2 & vc is 0 on a match and >= 2^kWildShift otherwise.
+// z = min(y, dm) is then what it is in the plain form, provided 2^kWildShift >= max(D, match) (the host checks: pc_api.cpp).
+constexpr int kWildShift = kWildShiftHost;       // 11: 5 + kWildShift <= 16
+template <bool WILD> __device__ __forceinline__ u32 row_compare(u32 h2, u32 vc)
+{
+    if constexpr (WILD) return h2 & vc; else return pk_sub(h2, vc);
+}
+
+template <int R, bool PAD, bool TRACE, bool WILD = false>
 __device__ __forceinline__ void column_step(u32 (&T)[R], u32 (&U)[R], u32 h2,
                                             const u32 (&cs)[Cfg<R, PAD>::kNS], const u32 (&cv)[Cfg<R, PAD>::kNV],
                                             const uint2 *lds_const, const KConst &k, const u32 topD, const u32 topT,
@@ -123,7 +134,7 @@ __device__ __forceinline__ void column_step(u32 (&T)[R], u32 (&U)[R], u32 h2,
             const uint2 c = lds_const[r]; vc = c.x; dm = c.y;
         } else if constexpr (MODE == CONST_REGS) { vc = cv[r]; dm = cs[r]; }
         else { vc = cs[r]; dm = k.D2; }
-        const u32 y = pk_sub(h2, vc);
+        const u32 y = row_compare<WILD>(h2, vc);
         const u32 z = pk_minu(y, dm);
         const u32 Hs = pk_max(U[r], T[r]);
         const u32 d = pk_sub(dq, z);
@@ -251,8 +262,8 @@ __device__ __forceinline__ void traceback_pairs(const ScanArgs &a, const u32 *sl
             const int cl = wk_lo.col, rl = wk_lo.row, ch = wk_hi.col, rh = wk_hi.row;
             wk_lo.step(nb_lo, go_lo);
             wk_hi.step(nb_hi, go_hi);
-            if (wk_lo.ndiag != d_lo) seen_lo += dna5_code(w_lo[cl - 1]) == (int)a.ad_codes[ad_lo * 128 + rl - 1] ? 1 : 0;
-            if (wk_hi.ndiag != d_hi) seen_hi += dna5_code(w_hi[ch - 1]) == (int)a.ad_codes[ad_hi * 128 + rh - 1] ? 1 : 0;
+            if (wk_lo.ndiag != d_lo) seen_lo += (int)((a.ad_sets[ad_lo * 128 + rl - 1] >> dna5_code(w_lo[cl - 1])) & 1u);
+            if (wk_hi.ndiag != d_hi) seen_hi += (int)((a.ad_sets[ad_hi * 128 + rh - 1] >> dna5_code(w_hi[ch - 1])) & 1u);
         } else {
             wk_lo.step(nb_lo, go_lo);
             wk_hi.step(nb_hi, go_hi);
@@ -290,7 +301,7 @@ template <bool B> struct BoolTag { static constexpr bool value = B; };
 
 // Register budget: 3 resident waves per SIMD (<= 168 VGPRs) up to 34 rows, 2 (<= 256) up to 72 --
 // the traced variants of 33..34 and 68..72 rows land a few registers above that without the hint.
-template <int R, bool PAD, bool TRACE>
+template <int R, bool PAD, bool TRACE, bool WILD = false>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R <= 34) ? 3 : (R > 0 && R <= 72) ? 2 : 1))) void scan_kernel(ScanArgs a)
 {
     constexpr bool GEN = (R == 0);
@@ -306,7 +317,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
 
     const int lane = threadIdx.x;
     const int D = a.match - a.mismatch;
-    for (int c = lane; c < 256; c += 64) lut[c] = (uint16_t)(dna5_code(c) * D);
+    for (int c = lane; c < 256; c += 64) lut[c] = WILD ? (uint16_t)((1u << dna5_code(c)) << kWildShift) : (uint16_t)(dna5_code(c) * D);
 
     KConst k;
     k.A2 = pack2(a.match); k.AO2 = pack2(a.match - a.gap_open); k.E2 = pack2(a.gap_extend);
@@ -346,8 +357,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
         const int NW = (rows + 3) >> 2;      // trace dwords per column per lane
         const int m_lo = a.ad_len[tile.adapter_lo];
         const int m_hi = a.ad_len[tile.adapter_hi];
-        const u32 *codes_lo = a.ad_codes + (int64_t)tile.adapter_lo * pcb::MAX_ADAPTER;
-        const u32 *codes_hi = a.ad_codes + (int64_t)tile.adapter_hi * pcb::MAX_ADAPTER;
+        const u32 *codes_lo = (WILD ? a.ad_sets : a.ad_codes) + (int64_t)tile.adapter_lo * pcb::MAX_ADAPTER;
+        const u32 *codes_hi = (WILD ? a.ad_sets : a.ad_codes) + (int64_t)tile.adapter_hi * pcb::MAX_ADAPTER;
         const int pad_lo = rows - m_lo, pad_hi = rows - m_hi;     // top padding rows of each half
         if (pad_lo < 0 || pad_hi < 0 || (GEN && rows > a.gen_max_rows)) {   // host bug
             if (lane == 0) atomicAdd(a.err, 1u);
@@ -372,8 +383,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
         for (int r = lane; r < rows; r += 64) {
             const int il = r - pad_lo, ih = r - pad_hi;
             const u32 rl = codes_lo[il >= 0 ? il : 0], rh = codes_hi[ih >= 0 ? ih : 0];
-            const u32 cl = il >= 0 ? rl * (u32)D : 6u * (u32)D;
-            const u32 ch = ih >= 0 ? rh * (u32)D : 6u * (u32)D;
+            u32 cl, ch;
+            if constexpr (WILD) {        // (codes_* point into the table of sets)
+                cl = il >= 0 ? ((~rl & 31u) | 16u) << kWildShift : 0xFFFFu;
+                ch = ih >= 0 ? ((~rh & 31u) | 16u) << kWildShift : 0xFFFFu;
+            } else {
+                cl = il >= 0 ? rl * (u32)D : 6u * (u32)D;
+                ch = ih >= 0 ? rh * (u32)D : 6u * (u32)D;
+            }
             const u32 dl = il >= 0 ? (u32)D : (u32)a.match;
             const u32 dh = ih >= 0 ? (u32)D : (u32)a.match;
             lds_const[r] = make_uint2(cl | (ch << 16), dl | (dh << 16));
@@ -520,7 +537,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
                 for (int r = 0; r < rows; ++r) {
                     const uint2 old = lds_col[r * 64 + lane];      // (T, U) of column j-1
                     const uint2 c = lds_const[r];
-                    const u32 z = pk_minu(pk_sub(h2, c.x), c.y);
+                    const u32 z = pk_minu(row_compare<WILD>(h2, c.x), c.y);
                     const u32 d = pk_sub(dq, z);
                     const u32 Hx = pk_add(old.y, k.E2);
                     const u32 Hs = pk_max(Hx, old.x);
@@ -567,7 +584,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
                 topT = pk_add(topT, k.EPS2);                        // T(0,j)
                 ++jj;
                 const u32 topT_col = topT;
-                column_step<RS, PAD, TR>(T, U, h2, cs, cv, lds_const, k, topD, topT_col, trw, tie01);
+                column_step<RS, PAD, TR, WILD>(T, U, h2, cs, cv, lds_const, k, topD, topT_col, trw, tie01);
                 if constexpr (TR) {
 #pragma unroll
                     for (int w = 0; w < (RS + 3) / 4; ++w) trace_dst[w * 64] = trw[w];
@@ -581,7 +598,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu((R > 0 && R 
                     for (int r = 0; r < R; ++r) {
                         const uint2 old = (fin_lo || fin_hi) ? fin[r * 64 + lane] : make_uint2(0u, 0u);
                         const uint2 c = lds_const[r];
-                        const u32 z = pk_minu(pk_sub(h2, c.x), c.y);
+                        const u32 z = pk_minu(row_compare<WILD>(h2, c.x), c.y);
                         const u32 d = pk_sub(dq, z);
                         const u32 Hs = pk_max(old.y, old.x);
                         const u32 Vs = pk_max(Vprev, Tup);
@@ -768,8 +785,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
         const Tile tile = a.tiles[t];
         const int m_lo = a.ad_len[tile.adapter_lo];
         const int m_hi = a.ad_len[tile.adapter_hi];
-        const u32 *codes_lo = a.ad_codes + (int64_t)tile.adapter_lo * pcb::MAX_ADAPTER;
-        const u32 *codes_hi = a.ad_codes + (int64_t)tile.adapter_hi * pcb::MAX_ADAPTER;
+        const u32 *sets_lo = a.ad_sets + (int64_t)tile.adapter_lo * pcb::MAX_ADAPTER;     // per row the read codes it matches (pc_letters.h)
+        const u32 *sets_hi = a.ad_sets + (int64_t)tile.adapter_hi * pcb::MAX_ADAPTER;
         const int pad_lo = R - m_lo, pad_hi = R - m_hi;           // top padding rows of each half
         if (pad_lo < 0 || pad_hi < 0) {                           // host bug
             if (lane == 0) atomicAdd(a.err, 1u);
@@ -799,8 +816,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(R <= 30 ? PC
             int sl = 0, sh = 0;
             if (r < R) {
                 const int il = r - pad_lo, ih = r - pad_hi;
-                if (il >= 0) sl = ((int)codes_lo[il] == cl) ? a.match : a.mismatch;
-                if (ih >= 0) sh = ((int)codes_hi[ih] == ch) ? a.match : a.mismatch;
+                if (il >= 0) sl = ((sets_lo[il] >> cl) & 1u) ? a.match : a.mismatch;
+                if (ih >= 0) sh = ((sets_hi[ih] >> ch) & 1u) ? a.match : a.mismatch;
             }
             s_tab[pair * STRIDE + r] = hpack2x(sl - a.gap_open + eps, sh - a.gap_open + eps);
             if constexpr (CHECK) {
@@ -1300,21 +1317,21 @@ int launch_unit_prefix(const Tile *tiles, int ntiles, const int32_t *win_len, in
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-template <bool TRACE>
-static int launch_scan(const ScanArgs &a0, int rows, bool pad, int grid, void *stream)
+template <bool TRACE, bool WILD>
+static int launch_scan_variant(const ScanArgs &a0, int rows, bool pad, int grid, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     ScanArgs a = a0;
     a.one2 = 0x00010001u; a.two2 = 0x00020002u; a.sixteen2 = 0x00100010u;
-#define PC_EXACT(RR) case RR: hipLaunchKernelGGL((scan_kernel<RR, false, TRACE>), dim3(grid), dim3(64), 0, s, a); break;
-#define PC_PADDED(RR) case RR: hipLaunchKernelGGL((scan_kernel<RR, true, TRACE>), dim3(grid), dim3(64), 0, s, a); break;
+#define PC_EXACT(RR) case RR: hipLaunchKernelGGL((scan_kernel<RR, false, TRACE, WILD>), dim3(grid), dim3(64), 0, s, a); break;
+#define PC_PADDED(RR) case RR: hipLaunchKernelGGL((scan_kernel<RR, true, TRACE, WILD>), dim3(grid), dim3(64), 0, s, a); break;
     if (rows == 0) {
         // generic: dynamic LDS = per-row constants + the DP column of 64 lanes
         const size_t lds = (size_t)a.gen_max_rows * 8 + (size_t)a.gen_max_rows * 64 * 8;
-        if (hipFuncSetAttribute((const void *)scan_kernel<0, true, TRACE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        if (hipFuncSetAttribute((const void *)scan_kernel<0, true, TRACE, WILD>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds) != hipSuccess)
             return -2;
-        hipLaunchKernelGGL((scan_kernel<0, true, TRACE>), dim3(grid), dim3(64), lds, s, a);
+        hipLaunchKernelGGL((scan_kernel<0, true, TRACE, WILD>), dim3(grid), dim3(64), lds, s, a);
     } else if (!pad) {
         switch (rows) {
             PC_EXACT(22) PC_EXACT(24) PC_EXACT(28) PC_EXACT(32)
@@ -1331,6 +1348,13 @@ static int launch_scan(const ScanArgs &a0, int rows, bool pad, int grid, void *s
 #undef PC_EXACT
 #undef PC_PADDED
     return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// a.wild: the wildcard variants (a context with IUPAC wildcards on); otherwise the instantiations there have always been
+template <bool TRACE>
+static int launch_scan(const ScanArgs &a, int rows, bool pad, int grid, void *stream)
+{
+    return a.wild ? launch_scan_variant<TRACE, true>(a, rows, pad, grid, stream) : launch_scan_variant<TRACE, false>(a, rows, pad, grid, stream);
 }
 
 int launch_trace(const ScanArgs &a, int rows, bool pad, int grid, void *stream) { return launch_scan<true>(a, rows, pad, grid, stream); }

@@ -15,8 +15,10 @@
 //   * every step of the walk is classified from (col, row) before and after Walk::consume and leaves as an operation.
 //
 // Operations (the adapter plays the role SAM gives the reference, the window that of the query):
-//   0 '='  diagonal step over equal Dna5 codes (N == N is equal)      2 'I'  read base against a gap (horizontal step)
-//   1 'X'  diagonal step over unequal codes                           3 'D'  adapter base against a gap (vertical step)
+//   0 '='  diagonal step over a match (pc_letters.h)                  2 'I'  read base against a gap (horizontal step)
+//   1 'X'  diagonal step that is not a match                          3 'D'  adapter base against a gap (vertical step)
+// A match is pcl::matches(adapter letter's set, read code): with one-code sets equal Dna5 codes (N == N is equal), with
+// IUPAC wildcards a read base A/C/G/T inside the adapter letter's set.
 // They leave in the order the traceback visits them -- FROM THE END CELL TO THE PATH'S FIRST CELL -- sixteen to a dword,
 // the first in the lowest bits; nothing is ever reversed here.  path_cigar() below reads the dwords backwards.
 //
@@ -38,6 +40,7 @@
 #include <stdint.h>
 
 #include "pc_cell.h"
+#include "pc_letters.h"
 
 namespace pcpath {
 
@@ -52,13 +55,13 @@ PC_HD int64_t ops_words(int64_t n, int64_t m) { return (n + m + OPS_PER_WORD - 1
 //       void put(int j, int g, uint32_t word)     the packed trace of LOCAL column j = 1 .. c1 - c0, row group
 //       uint32_t get(int j, int g)                g = 0 .. row_groups(m) - 1
 // rd(k): Dna5 code of the k-th (0-based, GLOBAL) base of the (masked) read; only k in [c0, c1) is asked for.
-// ad(k): Dna5 code of the k-th (0-based) adapter base.
+// ad(k): the set of read codes the k-th (0-based) adapter letter matches (pcl::letter_set; pcl::code_set of a Dna5 code).
 // sink(k, word): the k-th dword of operations; each is handed out when full, the last (partial) one at the end.
 // -> 0, or 1 if the walk reported an inconsistency (leaving the window included) or did not end within c1 - c0 + m + 8
 // steps (never expected).  n or m == 0, or an empty window: the reference's failure record, a zero head, no operations.
 template <typename Mem, typename RdFn, typename AdFn, typename Sink>
-PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int match, int mismatch, int gap_open,
-                            int gap_extend, Mem mem, pcw::Digest &out, int32_t head[4], Sink sink)
+PC_HD int align_path_window_sets(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int match, int mismatch, int gap_open,
+                                 int gap_extend, Mem mem, pcw::Digest &out, int32_t head[4], Sink sink)
 {
     head[0] = 0; head[1] = 0; head[2] = 0; head[3] = 0;
     const int nc = c1 - c0;
@@ -76,7 +79,7 @@ PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int 
         uint32_t word = 0;
         for (int i = 1; i <= m; ++i) {
             const int Mi = mem.M(i);
-            const int sub = (h == ad(i - 1)) ? match : mismatch;
+            const int sub = pcl::matches(ad(i - 1), h) ? match : mismatch;
             const pcc::Cell c = pcc::cell(linear, diag, sub, upM, upV, Mi, mem.H(i), gap_open, gap_extend);
             diag = Mi;
             mem.M(i) = c.S;
@@ -96,7 +99,7 @@ PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int 
         if (k >= cap) { overrun = 1; break; }
         const int c = w.col, r = w.row;
         const int nib = (int)(mem.get(c, (r - 1) / ROWS_PER_WORD) >> (4 * ((r - 1) & (ROWS_PER_WORD - 1)))) & 15;
-        const bool eq = rd(c0 + c - 1) == ad(r - 1);
+        const bool eq = pcl::matches(ad(r - 1), rd(c0 + c - 1));
         w.consume(nib, eq);
         const bool dcol = w.col != c, drow = w.row != r;
         const uint32_t op = (dcol && drow) ? (eq ? OP_EQ : OP_X) : (drow ? OP_D : OP_I);
@@ -110,6 +113,15 @@ PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int 
     return err;
 }
 
+// ad(k): Dna5 code of the k-th adapter base -- the reference's equality, N == N included.
+template <typename Mem, typename RdFn, typename AdFn, typename Sink>
+PC_HD int align_path_window(int n, int m, int c0, int c1, RdFn rd, AdFn ad, int match, int mismatch, int gap_open,
+                            int gap_extend, Mem mem, pcw::Digest &out, int32_t head[4], Sink sink)
+{
+    return align_path_window_sets(n, m, c0, c1, rd, [&](int k) { return pcl::code_set(ad(k)); }, match, mismatch, gap_open,
+                                  gap_extend, mem, out, head, sink);
+}
+
 // The alignment against the WHOLE read: the window c0 = 0, c1 = n.  With c0 = 0 the start state is the reference's
 // (M(i) = 0, H(i) = -inf), the window's last column is the read's, so its cells are scout candidates as in the
 // reference, and head[1] = w.col: every one of the window's differences vanishes, and what is left is the recurrence of
@@ -120,6 +132,13 @@ PC_HD int align_path(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, in
                      pcw::Digest &out, int32_t head[4], Sink sink)
 {
     return align_path_window(n, m, 0, n, rd, ad, match, mismatch, gap_open, gap_extend, mem, out, head, sink);
+}
+
+template <typename Mem, typename RdFn, typename AdFn, typename Sink>
+PC_HD int align_path_sets(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
+                          pcw::Digest &out, int32_t head[4], Sink sink)
+{
+    return align_path_window_sets(n, m, 0, n, rd, ad, match, mismatch, gap_open, gap_extend, mem, out, head, sink);
 }
 
 // (ops, path_len) -> the FORWARD run-length string ("17=1X4=2I6="), NUL-terminated when it fits.  -> the length it

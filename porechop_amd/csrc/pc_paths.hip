@@ -1,5 +1,5 @@
 // pc_paths.hip -- alignment PATHS, one LANE per alignment, 64 to a one-wave block, any scoring scheme pcs::fits accepts,
-// adapters of the context's code table (up to 128 bases), each lane its own.  Two kernels over one routine:
+// adapters of the context's table of letter sets (up to 128 bases; pc_letters.h), each lane its own.  Two kernels over one routine:
 //   path_kernel         a (window, adapter) pair against the whole window: pcpath::align_path (pc_paths.h), the very
 //                       function tests/host/test_paths.cpp replays base by base against the oracle;
 //   middle_path_kernel  a middle hit: pcpath::align_path_window over a window of a few hundred columns of the hit's
@@ -68,13 +68,13 @@ __global__ __launch_bounds__(64) void path_kernel(PathArgs a)
         return;
     }
     const uint8_t *rd = a.arena + a.seq_off[q];
-    const uint32_t *ad = a.ad_codes + (int64_t)ai * kMaxRows;      // Dna5 codes, one per dword
+    const uint32_t *ad = a.ad_sets + (int64_t)ai * kMaxRows;       // the rows' sets of read codes (pc_letters.h), one per dword
     uint32_t *ops = a.ops + q * a.ops_pitch;
     const int64_t pitch = a.ops_pitch;
     pcw::Digest d;
     int32_t head[4];
-    const int err = pcpath::align_path(
-        n, m, [&](int k) { return pcc::dna5_code(rd[k]); }, [&](int k) { return (int)ad[k]; }, a.match, a.mismatch, a.gap_open,
+    const int err = pcpath::align_path_sets(
+        n, m, [&](int k) { return pcc::dna5_code(rd[k]); }, [&](int k) { return ad[k]; }, a.match, a.mismatch, a.gap_open,
         a.gap_extend, PathMem{dyn, a.rows, lane, a.trace, (int64_t)a.groups, a.P, p}, d, head,
         [&](int k, uint32_t w) { if (k < pitch) ops[k] = w; });
     store_path(a.records, a.heads, a.err, q, d, head, err);
@@ -109,13 +109,13 @@ __global__ __launch_bounds__(64) void middle_path_kernel(MiddlePathArgs a)
         return;
     }
     const uint8_t *rd = a.arena + a.seq_off[q];
-    const uint32_t *ad = a.ad_codes + (int64_t)ai * kMaxRows;      // Dna5 codes, one per dword
+    const uint32_t *ad = a.ad_sets + (int64_t)ai * kMaxRows;       // the rows' sets of read codes (pc_letters.h), one per dword
     const int2 *iv = (const int2 *)a.intervals + mb;
     uint32_t *ops = a.ops + q * a.ops_pitch;
     const int64_t pitch = a.ops_pitch;
     pcw::Digest d;
     int32_t head[4];
-    const int err = pcpath::align_path_window(
+    const int err = pcpath::align_path_window_sets(
         n, m, c0, c1,
         [&](int k) {
             int code = pcc::dna5_code(rd[k]);
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(64) void middle_path_kernel(MiddlePathArgs a)
             }
             return code;
         },
-        [&](int k) { return (int)ad[k]; }, a.match, a.mismatch, a.gap_open, a.gap_extend,
+        [&](int k) { return ad[k]; }, a.match, a.mismatch, a.gap_open, a.gap_extend,
         PathMem{dyn, a.rows, lane, a.trace, (int64_t)a.groups, a.P, p}, d, head,
         [&](int k, uint32_t w) { if (k < pitch) ops[k] = w; });
     store_path(a.records, a.heads, a.err, q, d, head, err);

@@ -5,6 +5,11 @@
 // pieces the seed stage takes and with which seed length, and every table word of both stages.  No HIP, no environment, no
 // context: pc_api.cpp uploads a Plan and launches over it; tests/host/test_prefilter_plan.cpp interprets one on the CPU
 // against the oracle.  These rules decide whether a cleared mask bit is still a proof.
+//
+// Which read codes an adapter row matches is pc_letters.h.  With IUPAC wildcards (`wildcards`, the context's mode) a row's Eq bit
+// is set for every base of its set and for nothing else; an edit is then a column that is not a match under that rule, which is
+// what max_edits bounds.  A piece that holds a degenerate letter has no seeds.  On the plane a read's non-base is held as 'A'
+// and so matches every row whose set holds A: more matches than the rule gives, never fewer -- a cleared bit stays a proof.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -12,6 +17,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "pc_letters.h"
 
 namespace pcp {
 
@@ -87,14 +94,14 @@ inline bool seedable(const Piece &pc, int *q)
     return pc.k >= 0 && pc.k < pc.len && parts <= 8 && *q >= 6;
 }
 
-// Eq words of Dna5 codes 0..4: the piece in the TOP bits (row r at bit 32 - len + r), the bits below it wildcards
-inline void eq_words(const std::string &ad, const Piece &pc, uint32_t out[5])
+// Eq words of Dna5 codes 0..4: the piece in the TOP bits (row r at bit 32 - len + r), the bits below it match-all
+inline void eq_words(const std::string &ad, const Piece &pc, uint32_t out[5], bool wildcards = false)
 {
     const uint32_t wild = pc.len >= 32 ? 0u : (0xFFFFFFFFu >> pc.len);
     for (int code = 0; code < 5; ++code) {
         uint32_t e = wild;
         for (int r = 0; r < pc.len; ++r)
-            if (dna5((unsigned char)ad[pc.begin + r]) == code) e |= 1u << (32 - pc.len + r);
+            if (pcl::matches(pcl::letter_set((uint8_t)ad[pc.begin + r], wildcards), code)) e |= 1u << (32 - pc.len + r);
         out[code] = e;
     }
 }
@@ -119,7 +126,7 @@ inline void split_groups(size_t n, Emit emit)
 
 // Appends the launches over `list` and their tables to the plan.
 inline void add_groups(const std::vector<std::string> &adapters, const std::vector<Piece> &list, Route route,
-                       std::vector<Launch> &launches, Plan &out)
+                       std::vector<Launch> &launches, Plan &out, bool wildcards = false)
 {
     const size_t rows = route == Route::PlaneTotal ? 4 : 256;        // Eq rows per group: one per 2-bit code / per byte value
     split_groups(list.size(), [&](size_t first, size_t count, int P) {
@@ -132,10 +139,11 @@ inline void add_groups(const std::vector<std::string> &adapters, const std::vect
             const size_t g = i / P, slot = i % P;
             const uint32_t wild = pc.len >= 32 ? 0u : (0xFFFFFFFFu >> pc.len);     // the bits below the piece
             uint32_t eq[5];
-            eq_words(adapters[pc.adapter], pc, eq);
+            eq_words(adapters[pc.adapter], pc, eq, wildcards);
             if (route == Route::PlaneTotal) {
                 // the plane holds codes 0..3 only, a read's non-base among them as 0: an adapter letter that is not a
-                // base (Dna5 code 4) matches all four, so that no match of the byte route (N == N) is lost
+                // base (Dna5 code 4) matches all four, so that no match of the byte route (N == N) is lost.  (With wildcards
+                // eq[4] holds no row: a row matches exactly the bases of its set.)
                 for (size_t code = 0; code < 4; ++code) out.tables[L.table_off + (g * 4 + code) * P + slot] = eq[code] | (eq[4] & ~wild);
             } else {
                 for (int b = 0; b < 256; ++b) out.tables[L.table_off + (g * 256 + b) * P + slot] = eq[dna5((unsigned char)b)];
@@ -150,7 +158,7 @@ inline void add_groups(const std::vector<std::string> &adapters, const std::vect
 // The plan of adapters[ids[j]] with bound max_edits[j] (< 0: do not filter this adapter), j < n; bit j % 32 of mask word
 // j / 32 is adapter j's.  Returns 0, or -1 for an adapter index outside `adapters` (then `out` is unspecified).
 inline int build(const std::vector<std::string> &adapters, const int32_t *ids, const int32_t *max_edits, int n, Route route,
-                 const Options &opt, Plan &out)
+                 const Options &opt, Plan &out, bool wildcards = false)
 {
     out = Plan();
     const bool plane = route != Route::Bytes;
@@ -179,7 +187,7 @@ inline int build(const std::vector<std::string> &adapters, const int32_t *ids, c
             pos += len;
         }
     }
-    add_groups(adapters, pieces, route, out.launches, out);
+    add_groups(adapters, pieces, route, out.launches, out, wildcards);
 
     // ---- seed stage: which pieces it takes, and its tables ------------------------------------------------------
     // ONE seed length for all pieces -- the shortest any seedable piece needs: a longer part's seed is its first q bases, which
@@ -209,6 +217,9 @@ inline int build(const std::vector<std::string> &adapters, const int32_t *ids, c
         // of the adapter would match the read's 'N', which the plane holds as 'A')
         if (ok && plane)
             for (char ch : ad) if (dna5((unsigned char)ch) > 3) ok = false;
+        // wildcards: a piece that holds a degenerate letter has no seeds (a seed is one exact q-gram)
+        if (ok && wildcards)
+            for (int r = 0; r < pc.len; ++r) if (pcl::degenerate((uint8_t)ad[pc.begin + r])) ok = false;
         const size_t seeds_before = seeds.size();
         const int parts = pc.k + 1;
         int pos = 0;
@@ -267,11 +278,11 @@ inline int build(const std::vector<std::string> &adapters, const int32_t *ids, c
             const Piece &pc = seeded[i];
             int32_t *mt = &out.piece_meta[(size_t)i * 4];
             mt[0] = pc.len; mt[1] = pc.k; mt[2] = pc.word; mt[3] = (int32_t)pc.bit;
-            eq_words(adapters[pc.adapter], pc, &out.piece_eq[(size_t)i * 8]);
+            eq_words(adapters[pc.adapter], pc, &out.piece_eq[(size_t)i * 8], wildcards);
         }
         // the rest (long pieces with large bounds, tiny adapters, seeds with an N) keeps the exhaustive kernel:
         // its groups are appended to the same tables
-        add_groups(adapters, rest, route, out.rest_launches, out);
+        add_groups(adapters, rest, route, out.rest_launches, out, wildcards);
     }
     if (out.tables.empty()) { out.tables.assign(4, 0); out.meta.assign(4, 0); }
     return 0;

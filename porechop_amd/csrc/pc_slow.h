@@ -8,10 +8,15 @@
 // The cell, the scout and _correctTraceValue are pc_cell.h (the one copy, with the reference's lines cited there); the
 // trace is kept as the nibble pc_walk.h consumes and the traceback + digest ARE pc_walk.h (matches counted from the
 // bases: finish_counted).  No drift, no bounds, no pruning: O(n m) cells, one byte of trace per cell.
+//
+// Whether two bases match is pc_letters.h: the adapter side is a SET of read codes per row (align_pair_sets; with IUPAC
+// wildcards a letter's set of bases); align_pair takes Dna5 codes and is the same body over one-code sets -- the form the host
+// programs that hold this file to the oracle call.
 #pragma once
 #include <stdint.h>
 
 #include "pc_cell.h"
+#include "pc_letters.h"
 
 namespace pcs {
 
@@ -32,10 +37,11 @@ PC_HD bool fits(int n, int m, int match, int mismatch, int gap_open, int gap_ext
 
 // Mem:  int &M(int i), int &H(int i)   for adapter rows i = 1..m (the column state)
 //       uint8_t &T(int j, int i)       trace nibble of cell (column j = 1..n, row i = 1..m)
-// rd(k) / ad(k): Dna5 code of the k-th (0-based) read / adapter base.
+// rd(k): Dna5 code of the k-th (0-based) read base.  ad(k): the set of read codes the k-th adapter letter matches
+// (pcl::letter_set).
 // -> 0, or 1 if the walk reported an inconsistency (never expected).  n or m == 0: the reference's failure record.
 template <typename Mem, typename RdFn, typename AdFn>
-PC_HD int align_pair(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
+PC_HD int align_pair_sets(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
                      pcw::Digest &out)
 {
     if (n <= 0 || m <= 0) { pcc::failure_record(out); return 0; }
@@ -49,7 +55,7 @@ PC_HD int align_pair(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, in
         const bool last_col = j == n;
         for (int i = 1; i <= m; ++i) {
             const int Mi = mem.M(i);
-            const int sub = (h == ad(i - 1)) ? match : mismatch;
+            const int sub = pcl::matches(ad(i - 1), h) ? match : mismatch;
             const pcc::Cell c = pcc::cell(linear, diag, sub, upM, upV, Mi, mem.H(i), gap_open, gap_extend);
             diag = Mi;
             mem.M(i) = c.S;
@@ -62,9 +68,17 @@ PC_HD int align_pair(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, in
     w.start(best.I, best.J, m, 0, n, best.M, best.tie_fix(linear));
     while (!w.done) {
         const int c = w.col, r = w.row;
-        w.consume(mem.T(c, r), rd(c - 1) == ad(r - 1));
+        w.consume(mem.T(c, r), pcl::matches(ad(r - 1), rd(c - 1)));
     }
     return w.finish_counted(out);
+}
+
+// ad(k): Dna5 code of the k-th adapter base -- the reference's equality, N == N included.
+template <typename Mem, typename RdFn, typename AdFn>
+PC_HD int align_pair(int n, int m, RdFn rd, AdFn ad, int match, int mismatch, int gap_open, int gap_extend, Mem mem,
+                     pcw::Digest &out)
+{
+    return align_pair_sets(n, m, rd, [&](int k) { return pcl::code_set(ad(k)); }, match, mismatch, gap_open, gap_extend, mem, out);
 }
 
 }  // namespace pcs

@@ -1,8 +1,10 @@
 // pc_slow.hip -- the plain-int32 alignment kernel: one LANE per (window, adapter) pair, any scoring scheme, adapters up
 // to pcs::MAX_ADAPTER bases.  It exists so that the drop-in boundary is TOTAL: the reference takes any four integers
 // and any adapter (porechop/porechop.py:145,196-202, porechop/src/adapter_align.cpp:11-31), the packed 16-bit kernels
-// of pc_kernels.hip only the schemes pcb::scores_supported proves exact.  The arithmetic is pcs::align_pair
-// (pc_slow.h), the very function tests/host/test_slow.cpp checks against the oracle on unrestricted schemes.
+// of pc_kernels.hip only the schemes pcb::scores_supported proves exact.  The arithmetic is pcs::align_pair_sets
+// (pc_slow.h), the very function tests/host/test_slow.cpp checks against the oracle on unrestricted schemes and
+// tests/host/test_wildcards.cpp against the wildcard rule: the adapter arrives as one set of read codes per row (pc_letters.h,
+// in the context's mode), so a wildcard context's long adapters and unsupported schemes run here too.
 //
 // Layout: the column state (M, H per adapter row) sits in LDS as [row][lane] when the adapter has at most 128 rows
 // (64 KB per wave), otherwise in HBM as [row][pair]; the trace, one nibble-holding byte per cell, in HBM as
@@ -47,17 +49,17 @@ __global__ __launch_bounds__(64) void slow_kernel(SlowArgs a)
         return;
     }
     const uint8_t *rd = a.arena + a.win_off[w];
-    const uint8_t *ad = a.adapter;            // Dna5 codes already
+    const uint8_t *ad = a.adapter;            // per row the set of read codes it matches (pc_letters.h)
     pcw::Digest d;
     int err;
     auto rdf = [&](int k) { return pcc::dna5_code(rd[k]); };
-    auto adf = [&](int k) { return (int)ad[k]; };
+    auto adf = [&](int k) { return (unsigned)ad[k]; };
     if constexpr (LDS)
-        err = pcs::align_pair(n, a.m, rdf, adf, a.match, a.mismatch, a.gap_open, a.gap_extend,
-                              LdsMem{dyn, a.m, lane, a.trace, a.P, p}, d);
+        err = pcs::align_pair_sets(n, a.m, rdf, adf, a.match, a.mismatch, a.gap_open, a.gap_extend,
+                                   LdsMem{dyn, a.m, lane, a.trace, a.P, p}, d);
     else
-        err = pcs::align_pair(n, a.m, rdf, adf, a.match, a.mismatch, a.gap_open, a.gap_extend,
-                              HbmMem{a.state, a.m, a.trace, a.P, p}, d);
+        err = pcs::align_pair_sets(n, a.m, rdf, adf, a.match, a.mismatch, a.gap_open, a.gap_extend,
+                                   HbmMem{a.state, a.m, a.trace, a.P, p}, d);
     if (err) atomicAdd(a.err, 1u);
     ((int4 *)o)[0] = make_int4(d.read_start, d.read_end, d.adapter_start, d.adapter_end);
     ((int4 *)o)[1] = make_int4(d.score, d.matches, d.aligned_len, d.full_len);

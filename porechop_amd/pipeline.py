@@ -58,6 +58,8 @@ class ScanParams:
     # packed-only reads (DeviceReads.packed_only): the prefilter takes EVERY middle-adapter list over the plane
     # (pc_prefilter_packed_any) instead of unpacking all reads for a list the seed stage cannot cover
     packed_total: bool = False
+    # IUPAC wildcards in the adapters (Aligner.set_wildcards): off by default
+    wildcards: bool = False
 
 
 @dataclass
@@ -265,10 +267,12 @@ class Pipeline:
         if aligner is None:
             self.device = torch.device(device if device is not None else "cuda")
             dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.aligner = Aligner(self.seqs, self.p.scores, device=dev_index)
+            self.aligner = Aligner(self.seqs, self.p.scores, device=dev_index, wildcards=self.p.wildcards)
         else:
             self.device = torch.device(device if device is not None else "cpu")
             self.aligner = aligner
+            if self.p.wildcards or getattr(aligner, "wildcards", False):
+                self.aligner.set_wildcards(self.p.wildcards)      # (an aligner without the mode: an error, not a silent off)
             self.aligner.set_adapters(self.seqs)
         self.stats = {"pairs_end": 0, "pairs_middle": 0, "cells_end": 0, "cells_middle": 0}
         self._floor_seen = 0          # the aligner's total of pairs left untraced by a score floor, as of the last phase_c

@@ -339,13 +339,14 @@ def gz_out_hint(opts, output, barcode_dir, input_path):
         return False
 
 
-def _open_pipeline(opts, device, aligner, adapter_panel):
-    """-> (adapter panel, Pipeline) for a run's options."""
+def _open_pipeline(opts, device, aligner, adapter_panel, wildcards=False):
+    """-> (adapter panel, Pipeline) for a run's options.  wildcards: IUPAC letters in the panel's adapters stand for their sets of
+    bases (ScanParams.wildcards); not an Option -- the options are the reference's."""
     panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
     params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
                         end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
                         adapter_threshold=opts.adapter_threshold, check_reads=opts.check_reads,
-                        scores=tuple(int(x) for x in opts.scoring_scheme))
+                        scores=tuple(int(x) for x in opts.scoring_scheme), wildcards=bool(wildcards))
     pl = Pipeline(panel, params, device=device, aligner=aligner)
     if aligner is None:
         # a one-shot run should not wait for hiprtc: specialised kernels are compiled on a worker
@@ -647,7 +648,7 @@ def _stream_block_bytes():
 
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
-                 report_paths: bool = False, report_middle_paths: bool = False) -> Optional[RunResult]:
+                 report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -685,7 +686,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     res = RunResult(n_reads=0, read_type="FASTQ" if first.is_fastq else "FASTA")     # (plain FASTA streams too: cut at '>' lines)
     busy = {"load": time.perf_counter() - t_start, "scan": 0.0, "write": 0.0}
 
-    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards)
 
     fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
     res.out_format = fmt
@@ -857,7 +858,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
 
 
 def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
-                adapter_panel: List[AdapterSet] = None) -> Optional[RunResult]:
+                adapter_panel: List[AdapterSet] = None, wildcards: bool = False) -> Optional[RunResult]:
     """One plain FASTQ file -- or one gzip file of sized members, addressed by its inflated bytes -- over the ranks of a
     torch.distributed job WITHOUT any rank touching the whole file: rank r
     parses the records that start in its W-th of the file's bytes (pc_fastq_find_record / pc_readset_load_segment),
@@ -938,7 +939,7 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
     res.seconds["load"] = time.perf_counter() - t_start
     check_idx = np.arange(max(0, min(R, max(0, opts.check_reads) - first_read)), dtype=np.int64)
 
-    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards)
     coll_dev = pl.device if aligner is None else None
     try:
         t0 = time.perf_counter()
@@ -1027,9 +1028,13 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
         adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False,
-        report_middle_paths: bool = False) -> RunResult:
+        report_middle_paths: bool = False, wildcards: bool = False) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
+
+    wildcards=True reads the IUPAC letters of the panel's adapters as their sets of bases (Aligner.set_wildcards; DESIGN.md
+    section 15): for custom panels (adapter_panel, python -m porechop_amd.custom).  Off, every byte written is what it is
+    without the keyword.
 
     report=PATH writes the per-read explain report (REPORT_COLUMNS: the qualifying end alignments, the barcode scores and
     the middle hits behind every trim and call, one TSV row per read in input order) and fills RunResult.explain.  Phase B
@@ -1072,12 +1077,13 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
-                                report=report, report_paths=report_paths, report_middle_paths=report_middle_paths)
+                                report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards)
         if streamed is not None:
             return streamed
 
     if sharded:
-        shared = run_sharded(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel)
+        shared = run_sharded(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
+                             wildcards=wildcards)
         if shared is not None:
             return shared
 
@@ -1099,7 +1105,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     check_idx = check_idx[(check_idx >= lo_r) & (check_idx < hi_r)] - lo_r
     lap("load")
 
-    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel)
+    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards)
     try:
         reads = _upload(rs, pl.device, lo_r, hi_r)
         lap("upload", sync=True)
