@@ -179,6 +179,19 @@ int pc_scan_device_floored(pc_ctx *ctx, const void *d_arena, const int64_t *d_wi
                            int mode, int32_t *d_out, void *stream, const int32_t *job_floor,
                            const int32_t *job_floor_b);
 
+/* pc_scan_device_floored with per-call flags (0: pc_scan_device_floored itself; an unknown bit is PC_ERR_BAD_ARG).
+ * PC_SCAN_NO_SKIP_UNDERFILLED: the score pass of this call skips no adapter rows (see pc_set_row_skip_debug below) in a launch
+ * group that does not fill the device -- one whose windows the library cuts into column chunks.  Such a launch is made of few,
+ * short units, which pay the skip's entry and exit more often than they save rows: Pipeline.phase_c sets the flag for its
+ * mask-and-realign rounds.  A group that fills the device keeps the skip.  Records are the same either way.  The flag belongs
+ * to the call: it is no context state and the next call knows nothing of it. */
+#define PC_SCAN_NO_SKIP_UNDERFILLED 1
+int pc_scan_device_floored_flags(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off,
+                                 const int32_t *d_win_len, int64_t nwindows, const int32_t *job_adapter,
+                                 const int32_t *job_adapter_b, const int64_t *job_start, int njobs, int max_len,
+                                 int mode, int32_t *d_out, void *stream, const int32_t *job_floor,
+                                 const int32_t *job_floor_b, int flags);
+
 /* pc_scan_device over END WINDOWS with the trimming rule of their caller: phase B keeps, per read and side, the largest trim
  * among the alignments that qualify (identity above end_threshold, not flush with the window's inner edge, at least
  * min_trim_size columns), so a pair that cannot qualify need not be traced.  job_side (host, njobs entries) says what a
@@ -519,7 +532,15 @@ int pc_prefilter_packed_any(pc_ctx *ctx, const void *d_plane, const int64_t *d_w
  * pc_middle_hits: full-adapter identity (the %f-printed double) of whole-read records and whether it reaches the threshold.
  * pc_group_survivors: cand[g][w] = (mask row w AND gmask row g) != 0 over the prefilter's mask, counts[g] = how many.
  * pc_round_consume: per active masked read the first adapter >= its cursor whose record is a hit; stats int64[4] = alignments
- *   consumed, reads that hit, 2^40 - smallest hit adapter (0: none), bases to mask. */
+ *   consumed, reads that hit, 2^40 - smallest hit adapter (0: none), bases to mask.
+ * pc_round_select: behind pc_round_consume, with its d_anyh and d_a_hit: which adapter SETS the next round must scan for
+ *   which of the reads that hit.  d_set_of int32[nadapters]: the dense index (0 .. nsets - 1) of every middle adapter's set.
+ *   A read's hit interval is masked, and csrc/pc_mask_rule.h says which of its records the mask can have changed:
+ *   d_need[s * nact + k] = 1 when some adapter of set s at or above read k's hit adapter is the hit itself or has such a
+ *   record, else 0 (reads without a hit: 0); d_counts int64[nsets] = reads that need set s.  floored_positive: the rounds'
+ *   scans are floored with floors all > 0 (then a "no alignment" record is stable).  The caller decides whether the rule
+ *   may be used at all (pc_mask_rule_gate).  d_counts may lie behind pc_round_consume's d_stats in one buffer, so that one
+ *   copy brings both to the host. */
 int pc_trim_windows(pc_ctx *ctx, const int64_t *d_off, const int32_t *d_len, const int32_t *d_start_trim, const int32_t *d_end_trim,
                     int64_t n, int64_t *d_toff, int32_t *d_tlen, int64_t *d_stats, void *stream);
 int pc_middle_hits(pc_ctx *ctx, const int32_t *d_records, int64_t n, double threshold, double *d_full, uint8_t *d_hit, void *stream);
@@ -528,6 +549,15 @@ int pc_group_survivors(pc_ctx *ctx, const int32_t *d_mask, int64_t n, int words,
 int pc_round_consume(pc_ctx *ctx, const double *d_full_all, const int32_t *d_rec_all, const int64_t *d_cur, const int64_t *d_act,
                      int64_t nact, int nadapters, int64_t ndirty, double threshold, uint8_t *d_anyh, int32_t *d_a_hit, int64_t *d_cnt,
                      int64_t *d_stats, void *stream);
+
+int pc_round_select(pc_ctx *ctx, const int32_t *d_rec_all, const int64_t *d_act, const uint8_t *d_anyh, const int32_t *d_a_hit,
+                    const int32_t *d_set_of, int64_t nact, int nadapters, int64_t ndirty, int nsets, int floored_positive,
+                    uint8_t *d_need, int64_t *d_counts, void *stream);
+/* The rule's gate and the rule itself as the host compiles them (csrc/pc_mask_rule.h); no context, no device.
+ * pc_mask_rule_gate: 1 when every adapter (NUL-terminated) holds A/C/G/T/U only, wildcards are off and mismatch <= match. */
+int pc_mask_rule_gate(const char *const *adapters, int nadapters, int match, int mismatch, int gap_open, int gap_extend, int wildcards);
+int pc_mask_rule_must_realign(int adapter, int cur, int32_t read_start, int32_t read_end, int32_t mask_start, int32_t mask_end,
+                              int floored_positive);
 
 int pc_prefilter_defer_count(pc_ctx *ctx, int enabled);
 int pc_prefilter_overflowed(pc_ctx *ctx);

@@ -28,6 +28,7 @@ EXPORTS = [
     "pc_align_paths", "pc_path_cigar",
     "pc_middle_paths", "pc_middle_paths_cols",
     "pc_set_wildcards", "pc_letter_set",
+    "pc_scan_device_floored_flags", "pc_round_select", "pc_mask_rule_gate", "pc_mask_rule_must_realign",
 ]
 
 
@@ -87,6 +88,8 @@ def load_library():
     L.pc_scan_device.restype = c_int
     L.pc_scan_device_floored.argtypes = L.pc_scan_device.argtypes + [c_vp, c_vp]
     L.pc_scan_device_floored.restype = c_int
+    L.pc_scan_device_floored_flags.argtypes = L.pc_scan_device_floored.argtypes + [c_int]
+    L.pc_scan_device_floored_flags.restype = c_int
     L.pc_scan_device_end_rule.argtypes = L.pc_scan_device.argtypes + [ctypes.POINTER(EndRule), c_vp]
     L.pc_scan_device_end_rule.restype = c_int
     L.pc_floor_skipped.argtypes = [c_vp, c_vp, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]
@@ -223,6 +226,12 @@ def load_library():
     L.pc_group_survivors.restype = c_int
     L.pc_round_consume.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, ctypes.c_double, c_vp, c_vp, c_vp, c_vp, c_vp]
     L.pc_round_consume.restype = c_int
+    L.pc_round_select.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp]
+    L.pc_round_select.restype = c_int
+    L.pc_mask_rule_gate.argtypes = [ctypes.POINTER(ctypes.c_char_p), c_int, c_int, c_int, c_int, c_int, c_int]
+    L.pc_mask_rule_gate.restype = c_int
+    L.pc_mask_rule_must_realign.argtypes = [c_int] * 7
+    L.pc_mask_rule_must_realign.restype = c_int
     L.pc_kmer_count.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]
     L.pc_kmer_count.restype = c_int
     L.pc_kmer_select.argtypes = [c_vp, c_vp, c_int, ctypes.c_uint32, c_vp, c_vp, c_i64, c_vp, c_vp]

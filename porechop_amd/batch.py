@@ -11,6 +11,7 @@ from ._lib import check, load_library
 
 RESULT_INTS = 8      # readStart, readEnd, adapterStart, adapterEnd, rawScore, matches, alignedLen, fullLen
 MODE_AUTO, MODE_TRACE, MODE_TWO_PASS, MODE_SCORE, MODE_TRACE_AT = 0, 1, 2, 3, 4
+SCAN_NO_SKIP_UNDERFILLED = 1  # scan_device(no_skip_underfilled=True): PC_SCAN_NO_SKIP_UNDERFILLED of include/porechop_amd.h
 NO_FLOOR = -2 ** 31  # scan_device(floors=...): this job has no score floor (INT32_MIN)
 DEFAULT_SCORES = (3, -6, -5, -2)   # porechop/porechop.py:145
 INT_MIN = -2147483648
@@ -145,6 +146,23 @@ def letter_set(byte, wildcards):
 _LETTER_SETS = {}                # (byte, mode) -> set, as the library answered
 
 
+def mask_rule_gate(adapters, scores, wildcards):
+    """May the mask rule (csrc/pc_mask_rule.h) be applied to a middle scan of these adapters under this scheme?  The
+    library's answer (pc_mask_rule_gate; no device involved): every letter A/C/G/T/U, wildcards off, mismatch <= match."""
+    seqs = [a if isinstance(a, bytes) else a.encode() for a in adapters]
+    if any(b"\0" in a for a in seqs):
+        return False
+    arr = (ctypes.c_char_p * max(1, len(seqs)))(*seqs)
+    match, mismatch, gap_open, gap_extend = (int(x) for x in scores)
+    return bool(load_library().pc_mask_rule_gate(arr, len(seqs), match, mismatch, gap_open, gap_extend, 1 if wildcards else 0))
+
+
+def mask_rule_must_realign(adapter, cur, read_start, read_end, mask_start, mask_end, floored_positive):
+    """pcm::must_realign as the host compiles it (pc_mask_rule_must_realign): one record of one masked read."""
+    return bool(load_library().pc_mask_rule_must_realign(int(adapter), int(cur), int(read_start), int(read_end), int(mask_start),
+                                                         int(mask_end), 1 if floored_positive else 0))
+
+
 class Aligner:
     """One GPU context: a scoring scheme + an adapter panel + scratch buffers."""
     fast_prefilter = True      # prefilter_rows is the device's exact prefilter (callers may put it in front of the middle scan)
@@ -227,7 +245,8 @@ class Aligner:
 
     # ---- device buffers (torch tensors on the GPU) --------------------------------------
     def scan_device(self, arena, win_off, win_len, job_adapter, job_start, max_len, out,
-                    mode=MODE_AUTO, stream=None, job_adapter_b=None, floors=None, floors_b=None, end_rule=None, job_side=None):
+                    mode=MODE_AUTO, stream=None, job_adapter_b=None, floors=None, floors_b=None, end_rule=None, job_side=None,
+                    no_skip_underfilled=False):
         """arena uint8[*], win_off int64[n], win_len int32[n]: CUDA(HIP) tensors describing n windows.
         job_adapter int32[k], job_start int64[k+1] (window ranges), optional job_adapter_b int32[k]
         (-1 = none): host numpy.  out int32[total,8] with total = sum n_k * (1 or 2), job order,
@@ -236,7 +255,10 @@ class Aligner:
         not traced and gets the record (-1, 0, ..., 0) (pc_scan_device_floored); every other record is unchanged.
         end_rule = (end_size, min_trim_size, extra_end_trim, end_threshold) with job_side int32[k] (0 = start windows, 1 = end
         windows; MODE_AUTO or MODE_TWO_PASS): a pair that cannot trim its read by phase B's rule is not traced and gets that
-        same record (pc_scan_device_end_rule); every other record is unchanged."""
+        same record (pc_scan_device_end_rule); every other record is unchanged.
+        no_skip_underfilled (this call only): launches the library cuts into column chunks, because they do not fill the
+        device, skip no adapter rows (pc_scan_device_floored_flags; the records are the same either way).  Only a call with
+        floors skips rows at all, so with an end rule the option is an error and without floors it changes nothing."""
         import torch
         assert arena.is_cuda and win_off.is_cuda and win_len.is_cuda and out.is_cuda
         assert win_off.dtype == torch.int64 and win_len.dtype == torch.int32 and out.dtype == torch.int32
@@ -248,7 +270,7 @@ class Aligner:
         n = win_off.shape[0]
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         if end_rule is not None:
-            assert floors is None and floors_b is None and job_side is not None
+            assert floors is None and floors_b is None and job_side is not None and not no_skip_underfilled
             from ._lib import EndRule
             rule = EndRule(int(end_rule[0]), int(end_rule[1]), int(end_rule[2]), float(end_rule[3]))
             side = np.ascontiguousarray(job_side, dtype=np.int32)
@@ -265,12 +287,13 @@ class Aligner:
             fb = None if jb is None else np.ascontiguousarray(floors_b if floors_b is not None else np.full(len(job_adapter), NO_FLOOR),
                                                               dtype=np.int32)
             assert fa.shape[0] == len(job_adapter) and (fb is None or fb.shape[0] == len(job_adapter))
-            check(self.lib.pc_scan_device_floored(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
-                                                  job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None,
-                                                  job_start.ctypes.data, len(job_adapter),
-                                                  int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s),
-                                                  fa.ctypes.data, fb.ctypes.data if fb is not None else None),
-                  "pc_scan_device_floored")
+            args = (self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
+                    job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None, job_start.ctypes.data, len(job_adapter),
+                    int(max_len), mode, out.data_ptr(), ctypes.c_void_p(s), fa.ctypes.data, fb.ctypes.data if fb is not None else None)
+            if no_skip_underfilled:
+                check(self.lib.pc_scan_device_floored_flags(*(args + (SCAN_NO_SKIP_UNDERFILLED,))), "pc_scan_device_floored_flags")
+            else:
+                check(self.lib.pc_scan_device_floored(*args), "pc_scan_device_floored")
             return
         check(self.lib.pc_scan_device(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n,
                                       job_adapter.ctypes.data, jb.ctypes.data if jb is not None else None,
@@ -711,6 +734,30 @@ class Aligner:
         check(self.lib.pc_round_consume(self._ctx, full_all.data_ptr(), rec_all.data_ptr(), cur.data_ptr(), act.data_ptr(), n, A, Dn, float(threshold),
                                         anyh.data_ptr(), a_hit.data_ptr(), cnt.data_ptr(), stats.data_ptr(), ctypes.c_void_p(s)), "pc_round_consume")
         return anyh.view(torch.bool), a_hit, cnt, stats
+
+    def round_consume_select(self, full_all, rec_all, cur, act, threshold, set_of, nsets, floored_positive):
+        """round_consume and, behind it, which adapter sets the next round must scan for which of the reads that hit
+        (pc_round_select, csrc/pc_mask_rule.h) -> (anyh, a_hit, cnt, stats int64[4 + nsets], need uint8[nsets, n]): the
+        four statistics and the per-set counts in ONE buffer, for one copy to the host.  set_of int32[A] on the device."""
+        import torch
+        A, Dn = int(full_all.shape[0]), int(full_all.shape[1])
+        n = int(act.shape[0])
+        assert full_all.dtype == torch.float64 and full_all.is_contiguous() and rec_all.dtype == torch.int32 and rec_all.is_contiguous()
+        assert cur.dtype == torch.int64 and cur.is_contiguous() and act.dtype == torch.int64
+        assert set_of.dtype == torch.int32 and set_of.is_contiguous() and int(set_of.shape[0]) == A and nsets >= 1
+        act = act.contiguous()
+        dev = act.device
+        anyh = torch.empty(n, dtype=torch.uint8, device=dev)
+        a_hit = torch.empty(n, dtype=torch.int32, device=dev)
+        cnt = torch.empty(n, dtype=torch.int64, device=dev)
+        stats = torch.empty(4 + nsets, dtype=torch.int64, device=dev)
+        need = torch.empty((nsets, n), dtype=torch.uint8, device=dev)
+        s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(self.lib.pc_round_consume(self._ctx, full_all.data_ptr(), rec_all.data_ptr(), cur.data_ptr(), act.data_ptr(), n, A, Dn, float(threshold),
+                                        anyh.data_ptr(), a_hit.data_ptr(), cnt.data_ptr(), stats.data_ptr(), s), "pc_round_consume")
+        check(self.lib.pc_round_select(self._ctx, rec_all.data_ptr(), act.data_ptr(), anyh.data_ptr(), a_hit.data_ptr(), set_of.data_ptr(), n, A, Dn,
+                                       int(nsets), 1 if floored_positive else 0, need.data_ptr(), stats.data_ptr() + 32, s), "pc_round_select")
+        return anyh.view(torch.bool), a_hit, cnt, stats, need
 
     def prefilter_defer_count(self, enabled=True):
         """No host round trip inside prefilter_mask (pc_prefilter_defer_count): after the caller's next synchronisation,

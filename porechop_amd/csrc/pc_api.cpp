@@ -27,6 +27,7 @@
 #include "pc_middle_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
+#include "pc_mask_rule.h"
 #include "pc_prefilter_plan.h"
 #include "pc_scan_plan.h"
 
@@ -417,6 +418,7 @@ struct ScanCall {
     pcr::EndRule rule;                   // of a call with an end rule (floors.rule_side says for which jobs)
     int64_t npairs;
     bool linear;
+    bool no_skip_underfilled = false;    // PC_SCAN_NO_SKIP_UNDERFILLED of this call (pcn::row_skip_allowed)
     // the plan (plan_scan)
     pcn::Params p;
     pcn::Scratch scratch;
@@ -460,9 +462,10 @@ void plan_scan(pc_ctx *c, ScanCall &s)
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const pcn::Group &g = groups[gi];
         if (!g.two_pass || s.mode == PC_MODE_TRACE_AT) continue;           // (TRACE_AT: the end cells are the caller's)
-        skip_ok = pcn::row_skip_allowed(s.p, g, s.mode, s.floors);
+        const int group_chunks = pcn::group_chunks_for(s.p, g, s.max_len);
+        skip_ok = pcn::row_skip_allowed(s.p, g, s.mode, s.floors, s.no_skip_underfilled, group_chunks);
         size_t need = 0;
-        s.score_plan[gi] = pcn::plan_score_launches(s.p, g, s.max_len, s.npairs, pcn::group_chunks_for(s.p, g, s.max_len), lookup, &need);
+        s.score_plan[gi] = pcn::plan_score_launches(s.p, g, s.max_len, s.npairs, group_chunks, lookup, &need);
         s.k1_ints = std::max(s.k1_ints, need);
         s.n_score_launches += s.score_plan[gi].size();
         for (const pcn::ScoreLaunch &L : s.score_plan[gi]) if (L.chunks > pcn::kMaxChunks) s.unit_ints += 2 * (L.count + 1);
@@ -786,7 +789,8 @@ int run_slow_jobs(pc_ctx *c, const ScanCall &s)
 int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
                 int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
                 const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
-                const int32_t *job_floor, const int32_t *job_floor_b, const pc_end_rule *rule = nullptr, const int32_t *job_side = nullptr)
+                const int32_t *job_floor, const int32_t *job_floor_b, const pc_end_rule *rule = nullptr, const int32_t *job_side = nullptr,
+                int flags = 0)
 {
     // 1: the arguments, the panel, the table of the job list
     if (!c || nwindows < 0 || njobs < 0 || max_len < 0) return PC_ERR_BAD_ARG;
@@ -802,6 +806,7 @@ int scan_device(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const 
     s.floors.a = job_floor; s.floors.b = job_floor_b;
     s.job_adapter = job_adapter; s.job_adapter_b = job_adapter_b; s.njobs = njobs;
     s.linear = pcb::is_linear(c->gap_open, c->gap_extend);
+    s.no_skip_underfilled = (flags & PC_SCAN_NO_SKIP_UNDERFILLED) != 0;
     s.p = plan_params(c);
     if (rule && job_side && !s.p.opt.no_end_floor) {
         s.p.end_rule = true;
@@ -992,6 +997,18 @@ int pc_scan_device_floored(pc_ctx *c, const void *d_arena, const int64_t *d_win_
     if (job_floor_b && !job_adapter_b) return PC_ERR_BAD_ARG;
     return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
                        stream_v, job_floor, job_floor_b);
+}
+
+int pc_scan_device_floored_flags(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
+                                 int64_t nwindows, const int32_t *job_adapter, const int32_t *job_adapter_b,
+                                 const int64_t *job_start, int njobs, int max_len, int mode, int32_t *d_out, void *stream_v,
+                                 const int32_t *job_floor, const int32_t *job_floor_b, int flags)
+{
+    if ((job_floor || job_floor_b) && mode != PC_MODE_TWO_PASS) return PC_ERR_BAD_ARG;
+    if (job_floor_b && !job_adapter_b) return PC_ERR_BAD_ARG;
+    if (flags & ~PC_SCAN_NO_SKIP_UNDERFILLED) return PC_ERR_BAD_ARG;
+    return scan_device(c, d_arena, d_win_off, d_win_len, nwindows, job_adapter, job_adapter_b, job_start, njobs, max_len, mode, d_out,
+                       stream_v, job_floor, job_floor_b, nullptr, nullptr, flags);
 }
 
 int pc_scan_device_end_rule(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len,
@@ -1475,6 +1492,38 @@ int pc_round_consume(pc_ctx *c, const double *d_full_all, const int32_t *d_rec_a
     HIP_TRY(hipMemsetAsync(d_stats, 0, 32, stream));
     return pck::launch_round_consume(d_full_all, d_rec_all, d_cur, d_act, nact, nadapters, ndirty, threshold, d_anyh, d_a_hit, d_cnt, d_stats, stream)
                ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
+int pc_round_select(pc_ctx *c, const int32_t *d_rec_all, const int64_t *d_act, const uint8_t *d_anyh, const int32_t *d_a_hit,
+                    const int32_t *d_set_of, int64_t nact, int nadapters, int64_t ndirty, int nsets, int floored_positive,
+                    uint8_t *d_need, int64_t *d_counts, void *stream_v)
+{
+    if (!c || nact < 0 || nadapters < 1 || ndirty < 0 || nsets < 1 || !d_counts || !d_set_of) return PC_ERR_BAD_ARG;
+    if (nact > 0 && (!d_rec_all || !d_act || !d_anyh || !d_a_hit || !d_need)) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipMemsetAsync(d_counts, 0, (size_t)nsets * 8, stream));
+    if (nact > 0) HIP_TRY(hipMemsetAsync(d_need, 0, (size_t)nsets * (size_t)nact, stream));
+    return pck::launch_round_select(d_rec_all, d_act, d_anyh, d_a_hit, d_set_of, nact, nadapters, ndirty, nsets, floored_positive, d_need,
+                                    d_counts, stream)
+               ? PC_ERR_NO_DEVICE : PC_OK;
+}
+
+int pc_mask_rule_gate(const char *const *adapters, int nadapters, int match, int mismatch, int gap_open, int gap_extend, int wildcards)
+{
+    if (nadapters < 0 || (nadapters > 0 && !adapters)) return 0;
+    std::vector<int> lens;
+    for (int i = 0; i < nadapters; ++i) {
+        if (!adapters[i]) return 0;
+        lens.push_back((int)strlen(adapters[i]));
+    }
+    return pcm::gate(adapters, lens.data(), nadapters, match, mismatch, gap_open, gap_extend, wildcards != 0) ? 1 : 0;
+}
+
+int pc_mask_rule_must_realign(int adapter, int cur, int32_t read_start, int32_t read_end, int32_t mask_start, int32_t mask_end,
+                              int floored_positive)
+{
+    return pcm::must_realign(adapter, cur, read_start, read_end, mask_start, mask_end, floored_positive != 0) ? 1 : 0;
 }
 
 int pc_unpack_device(pc_ctx *c, const void *d_packed, int64_t nbases, const int64_t *d_exc_pos, int64_t nexc, void *d_arena,

@@ -238,6 +238,34 @@ inline int row_skip_r0(int match, int mismatch, int gap_open, int gap_extend, in
     return R;
 }
 
+// PC_JIT_R0 (measurements): the row the environment asks for in place of row_skip_r0's, for the pair of adapters of m_a and m_b
+// bases.  "20": that row for every pair.  "28|22:20,33|30:22": a row per pair, named by both of its lengths in either order; a
+// pair that is not listed keeps rule_r0.  Anything else -- an empty entry, a missing part, a stray character -- sets *malformed
+// and the whole text is ignored (rule_r0): a typo must not pass for a measurement.  The caller still checks that the row is usable.
+inline int row_skip_r0_override(const char *spec, int m_a, int m_b, int rule_r0, bool *malformed)
+{
+    *malformed = false;
+    auto number = [](const char *&q, int &v) {
+        if (*q < '0' || *q > '9') return false;
+        v = 0;
+        while (*q >= '0' && *q <= '9' && v < 100000) v = v * 10 + (*q++ - '0');
+        return true;
+    };
+    const char *q = spec;
+    int first = 0;
+    if (!q || !number(q, first)) { *malformed = true; return rule_r0; }
+    if (!*q) return first;                                   // one row for every pair
+    int found = rule_r0;
+    q = spec;
+    for (;;) {
+        int a = 0, b = 0, row = 0;
+        if (!number(q, a) || *q++ != '|' || !number(q, b) || *q++ != ':' || !number(q, row)) { *malformed = true; return rule_r0; }
+        if ((a == m_a && b == m_b) || (a == m_b && b == m_a)) found = row;
+        if (!*q) return found;
+        if (*q++ != ',') { *malformed = true; return rule_r0; }
+    }
+}
+
 inline bool compute_bounds(int match, int mismatch, int gap_open, int gap_extend, int m, Bounds &b)
 {
     if (!scores_supported(match, mismatch, gap_open, gap_extend, m > 0 ? m : 1)) return false;

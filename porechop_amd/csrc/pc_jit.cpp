@@ -172,12 +172,21 @@ Derived derive(const Recipe &rc)
     // the row its row-skipping fast path tests (pc_bounds.h): packed fp16 only, and not in the range-recording build, which
     // takes the one-column path throughout.  Three-wave kernels only: the longer pairs' kernels (two waves, or one with rows
     // parked in AGPRs) have no room for the lower part beside their rows, and their few workgroups per CU would pay for the
-    // lower rows' LDS with occupancy.  PC_JIT_R0 overrides the rule (measurements; an unusable value means none)
+    // lower rows' LDS with occupancy.  PC_JIT_R0 overrides the rule (measurements; an unusable row means none)
     const bool may_skip = rc.row_skip && rc.f16 && !check_range && waves == 3;
     d.r0 = may_skip ? pcb::row_skip_r0(rc.match, rc.mismatch, rc.gap_open, rc.gap_extend, R, rc.m_lo, rc.m_hi) : R;
     if (const char *e = getenv("PC_JIT_R0")) {
-        const int v = atoi(e), pad = R - std::min(rc.m_lo, rc.m_hi);
-        if (may_skip) d.r0 = (v >= 2 && !(v & 1) && v < R && v > pad) ? v : R;
+        // one row for every pair ("20") or a row per pair ("28|22:20,33|30:22"): pcb::row_skip_r0_override
+        bool malformed = false;
+        const int rule_r0 = d.r0;
+        const int v = pcb::row_skip_r0_override(e, rc.m_lo, rc.m_hi, rule_r0, &malformed);
+        const int pad = R - std::min(rc.m_lo, rc.m_hi);
+        if (malformed) {
+            static std::atomic<bool> said{false};
+            if (!said.exchange(true)) fprintf(stderr, "porechop_amd: PC_JIT_R0=%s is not a row or a list of LEN|LEN:ROW entries; ignored\n", e);
+        } else if (may_skip && v != rule_r0) {
+            d.r0 = (v >= 2 && !(v & 1) && v < R && v > pad) ? v : R;
+        }
     }
     // the kernel's LDS (tables, three look-up tables, 512 bytes per lower row) times the twelve workgroups of a CU at three
     // waves per SIMD must fit its 160 KiB, or the variant would run at a lower occupancy than the plain kernel: then none

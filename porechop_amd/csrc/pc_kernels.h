@@ -366,6 +366,9 @@ int launch_middle_hits(const int32_t *rec, int64_t n, double threshold, double *
 int launch_group_survivors(const int32_t *mask, int64_t n, int words, const int32_t *gmask, int ngroups, uint8_t *cand, int64_t *counts, void *stream);
 int launch_round_consume(const double *full_all, const int32_t *rec_all, const int64_t *cur, const int64_t *act, int64_t nact, int A, int64_t Dn,
                          double threshold, uint8_t *anyh, int32_t *a_hit, int64_t *cnt, int64_t *stats, void *stream);
+// which adapter sets the next round must scan for which of the reads that just hit (pc_mask_rule.h); need and counts zeroed by the caller
+int launch_round_select(const int32_t *rec_all, const int64_t *act, const uint8_t *anyh, const int32_t *a_hit, const int32_t *set_of, int64_t nact,
+                        int A, int64_t Dn, int S, int floored_positive, uint8_t *need, int64_t *counts, void *stream);
 int launch_plan(const PlanArgs &a, void *stream);
 
 // the k-mer census of adapter discovery (pc_discover.hip): counts[code] += 1 for every k-mer of every window that holds

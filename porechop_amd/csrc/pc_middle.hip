@@ -1,4 +1,4 @@
-// pc_middle.hip -- the glue of the middle scan (Pipeline.phase_c) as four small kernels.
+// pc_middle.hip -- the glue of the middle scan (Pipeline.phase_c) as five small kernels.
 //
 // Between the scans of a step, porechop_amd/pipeline.py decides -- per read -- what nanopore_read.py:56-62,210-243 decide:
 // the trimmed interval the middle scan looks at, which alignments are hits (full identity >= --middle_threshold), which
@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "pc_kernels.h"
+#include "pc_mask_rule.h"
 
 namespace pck {
 
@@ -141,6 +142,57 @@ __global__ __launch_bounds__(256) void round_consume_kernel(const double *full_a
         atomicMax(stats + 2, mn);
         if (ms) atomicAdd((unsigned long long *)stats + 3, (unsigned long long)ms);
     }
+}
+
+// ---- one round of mask-and-realign, the selecting part: which adapter SETS the next round must scan for which reads --------
+// Active read k that round_consume_kernel found a hit for (anyh[k], a_hit[k]) is masked over its hit's interval and stands at
+// a_hit[k] next; pc_mask_rule.h says which of its records the mask can have changed.  need[s][k] = 1 when some adapter of set s
+// (set_of[a] == s) at or above a_hit[k] is the hit itself or has such a record; counts[s] = reads that need set s.  Reads
+// without a hit are not active in the next round and need nothing.  need and counts come zero-initialised.  Every thread runs
+// the adapters in the same order, so a wave adds its reads' first marks of a set with one atomic.
+__global__ __launch_bounds__(256) void round_select_kernel(const int32_t *rec_all, const int64_t *act, const uint8_t *anyh, const int32_t *a_hit,
+                                                           const int32_t *set_of, int64_t nact, int A, int64_t Dn, int S, int floored_positive,
+                                                           uint8_t *need, unsigned long long *counts)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = k < nact && anyh[k] != 0;
+    int64_t d = 0;
+    int cur = A;
+    int32_t rs = 0, re = 0;
+    if (live) {
+        d = act[k];
+        cur = a_hit[k];
+        if (cur < 0 || cur >= A) {
+            cur = A;                                     // (not an adapter: nothing of this read is looked at)
+        } else {
+            const int32_t *h = rec_all + ((int64_t)cur * Dn + d) * TRACE_OUT_INTS;
+            rs = h[0]; re = h[1] + 1;
+        }
+    }
+    for (int a = 0; a < A; ++a) {
+        const int s = set_of[a];
+        bool first = false;
+        if (a >= cur && s >= 0 && s < S) {
+            bool must = a == cur;
+            if (!must) {
+                const int32_t *r = rec_all + ((int64_t)a * Dn + d) * TRACE_OUT_INTS;
+                must = pcm::must_realign(a, cur, r[0], r[1], rs, re, floored_positive != 0);
+            }
+            uint8_t *mark = need + (int64_t)s * nact + k;
+            if (must && !*mark) { *mark = 1; first = true; }
+        }
+        const unsigned long long votes = __ballot(first);
+        if (votes && (threadIdx.x & 63) == 0) atomicAdd(counts + s, (unsigned long long)__popcll(votes));
+    }
+}
+
+int launch_round_select(const int32_t *rec_all, const int64_t *act, const uint8_t *anyh, const int32_t *a_hit, const int32_t *set_of, int64_t nact,
+                        int A, int64_t Dn, int S, int floored_positive, uint8_t *need, int64_t *counts, void *stream)
+{
+    if (nact <= 0 || S <= 0) return 0;
+    hipLaunchKernelGGL(round_select_kernel, dim3((unsigned)((nact + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rec_all, act, anyh, a_hit, set_of,
+                       nact, A, Dn, S, floored_positive, need, (unsigned long long *)counts);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 int launch_trim_windows(const int64_t *off, const int32_t *len, const int32_t *st, const int32_t *et, int64_t n, int64_t *toff, int32_t *tlen,

@@ -576,8 +576,14 @@ inline int32_t launch_floor(const int32_t *job_adapter, const int32_t *job_adapt
     }
     return lowest == INT64_MAX ? INT32_MIN : (int32_t)lowest;
 }
-inline bool row_skip_allowed(const Params &p, const Group &g, int mode, const Floors &f)
+// Not where the caller asked for none in under-filled launches (PC_SCAN_NO_SKIP_UNDERFILLED, per call) and the fill rule cut
+// the group's windows into column chunks (group_chunks: what group_chunks_for returned): a launch of few, short units pays a
+// stretch's first window and the LDS round trip of the lower rows at every unit's entry and exit, which on the mask rounds of
+// the middle scan cost twice what the skipped rows saved (profiles/mask_rule_before_after.txt).  A launch that fills the chip
+// (one chunk) keeps the skip whatever the caller asked.
+inline bool row_skip_allowed(const Params &p, const Group &g, int mode, const Floors &f, bool no_skip_underfilled = false, int group_chunks = 1)
 {
+    if (no_skip_underfilled && group_chunks > 1) return false;
     return !p.opt.no_row_skip && !f.rule_side && floored(g, mode, f);
 }
 

@@ -21,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from .batch import MODE_AUTO, MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS
+from .batch import MODE_AUTO, MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS, mask_rule_gate
 
 # phase B is pruned (exactly: see "Exact pruning of phase B" below) from this many (sequence, side) jobs on; measured on
 # MI355X, 1 M reads: 198 jobs 192 -> 122 ms; with the 4-6 jobs of a run without barcodes tracing everything is faster
@@ -144,6 +144,14 @@ class EndExplain:
     # phase_b_explain(paths=True): the path of every hit, row for row with `hits` (Aligner.align_paths' heads and operations)
     path_heads: Optional[torch.Tensor] = None                     # int32 [H, 4]  path_len, read_first, adapter_first, opens
     path_ops: Optional[torch.Tensor] = None                       # int32 [H, pitch]
+
+
+def must_realign_torch(a, cur, read_start, read_end, rs, re, floored_positive):
+    """pcm::must_realign (csrc/pc_mask_rule.h) over tensors that broadcast against one another, for aligners without the native
+    selection step; tests/test_mask_rule_pipeline_cpu.py holds it against the header's function record by record."""
+    changed = torch.where(read_start == -1, torch.full_like(read_start, 0 if floored_positive else 1, dtype=torch.bool),
+                          (re > rs) & ((read_start < 0) | (read_end < read_start) | ((read_start < re) & (read_end >= rs))))
+    return (changed & (a > cur)) | (a == cur)
 
 
 def _round6(x):
@@ -341,7 +349,7 @@ class Pipeline:
         return reads.arena if reads.arena is not None else reads.ends[0]
 
     def _scan_jobs(self, arena, jobs, mode, max_len, with_layout=False, sort_lengths=False, typ_len=0, fuse=True, floors=None,
-                   end_sides=None):
+                   end_sides=None, presorted=False, no_skip_underfilled=False):
         """jobs: list of (adapter_index, win_off int64[n], win_len int32[n]) -> list of [n,8] views.
 
         floors (MODE_TWO_PASS): one score per job -- a pair whose best score is below it is not traced and gets the
@@ -358,7 +366,10 @@ class Pipeline:
         over longest first -- a tile then holds windows of nearly one length, and the specialised score
         kernel stays on its block-resolved path -- and the records are put back in the caller's order.
         typ_len: their typical (mean) length, which lets the library cut the longest reads into chunks of
-        about that many columns (pc_set_length_hint) so that a launch does not last as long as its longest read."""
+        about that many columns (pc_set_length_hint) so that a launch does not last as long as its longest read.
+        presorted: such windows, which the caller already hands over longest first (typ_len as above; nothing is reordered).
+        no_skip_underfilled: Aligner.scan_device's option of that name, for this call.  It means something with floors only
+        (an unfloored call skips no rows anyway) and is dropped without them."""
         order_of = {}
         if sort_lengths:
             sorted_jobs = []
@@ -411,11 +422,13 @@ class Pipeline:
             ostarts[k + 1] = ostarts[k] + n * (2 if b is not None else 1)
         out = torch.empty((int(ostarts[-1]), RESULT_INTS), dtype=torch.int32, device=self.device)
         if starts[-1] > 0:
-            self.aligner.set_length_hint(typ_len if sort_lengths else 0)
+            self.aligner.set_length_hint(typ_len if sort_lengths or presorted else 0)
             fl = {}
             if floors is not None:
                 fl = dict(floors=np.array([floors[a] for a, _ in fused], dtype=np.int32),
                           floors_b=np.array([floors[b] if b is not None else NO_FLOOR for _, b in fused], dtype=np.int32))
+                if no_skip_underfilled:
+                    fl["no_skip_underfilled"] = True
             if end_sides is not None:
                 p = self.p
                 fl = dict(end_rule=(p.end_size, p.min_trim_size, p.extra_end_trim, p.end_threshold),
@@ -1287,6 +1300,7 @@ class Pipeline:
             d_sel = torch.nonzero_static(dmask, size=Dn).flatten() if hasattr(torch, "nonzero_static") else torch.nonzero(dmask).flatten()
         n_align = A * int(live.numel())                              # alignments the reference performs
         n_spec = 0                                                   # speculative ones, discarded
+        n_kept = 0                                                   # of the rounds' (A - a0) x active pairs, those the mask rule kept
         rounds = 0
         H_read, H_ad, H_s, H_e, H_id = [], [], [], [], []
         if Dn > 0:
@@ -1331,10 +1345,34 @@ class Pipeline:
             act = torch.arange(Dn, device=dev)
             n_align -= A * Dn                                        # re-counted below as consumed
             scheduled = A * Dn
+            # The mask rule (csrc/pc_mask_rule.h): a mask only lowers substitution scores, so the record of a pair whose read
+            # interval the mask does not touch -- and, under positive floors, every "no alignment" record -- is provably the one
+            # already held.  A round then scans, per adapter SET (its sequences share one window list and fuse into the dual
+            # kernel), only the reads that have a record of the set the mask can have changed.  Behind the rule's gate (letters
+            # A/C/G/T/U, no wildcards, mismatch <= match); PC_NO_MASK_RULE=1, read per call: every round as before.  The proving
+            # routes keep their rounds (their tables hold all-zero "not computed" records, of which the rule says nothing).
+            use_rule = not prefilter and not prove and os.environ.get("PC_NO_MASK_RULE", "0") in ("", "0") \
+                and mask_rule_gate([self.seqs[ai] for ai in aidx], p.scores, p.wildcards)
+            if use_rule:
+                set_ids = sorted(set(si for _, si in ads_sets))
+                S_ = len(set_ids)
+                set_of = [set_ids.index(si) for _, si in ads_sets]                 # the dense set index of every middle adapter
+                set_adapters = [[a for a in range(A) if set_of[a] == s_] for s_ in range(S_)]
+                set_of_t = self._const(set_of, dtype=torch.int32 if fused else torch.int64)
+                floored_pos = floors is not None and all(f > 0 for f in floors)
             while True:
                 # consume, per active read: adapters cur.. in order, up to and including the first hit
-                # (one round trip per round: alignments consumed, reads that hit, the first adapter among them, bases to mask)
-                if fused:
+                # (one round trip per round: alignments consumed, reads that hit, the first adapter among them, bases to mask --
+                # and, with the rule, how many of the reads that hit need each set: the same buffer)
+                need = None
+                if fused and use_rule:
+                    anyh, a_hit, cnt_all, st4, need = al.round_consume_select(full_all, rec_all, cur, act, p.middle_threshold, set_of_t, S_,
+                                                                              floored_pos)
+                    st_ = st4.cpu()
+                    n_used, n_hit, n_mask = int(st_[0]), int(st_[1]), int(st_[3])
+                    a0 = (al.STAT_BIG - int(st_[2])) if int(st_[2]) else A
+                    r_all = None
+                elif fused:
                     anyh, a_hit, cnt_all, st4 = al.round_consume(full_all, rec_all, cur, act, p.middle_threshold)
                     st_ = st4.cpu()
                     n_used, n_hit, n_mask = int(st_[0]), int(st_[1]), int(st_[3])
@@ -1349,7 +1387,13 @@ class Pipeline:
                     r_all = rec_all[a_hit, act]
                     cnt_all = torch.where(anyh, torch.clamp(r_all[:, 1] + 1 - r_all[:, 0], min=0), torch.zeros_like(r_all[:, 0])).to(torch.int64)
                     st_ = torch.stack([used.sum(), anyh.sum(), torch.where(anyh, a_hit, torch.full_like(a_hit, A)).min().to(torch.int64),
-                                       cnt_all.sum()]).cpu()
+                                       cnt_all.sum()])
+                    if use_rule:
+                        must = must_realign_torch(arow, a_hit[None, :], rec_all[:, act, 0], rec_all[:, act, 1], r_all[:, 0][None, :],
+                                                  (r_all[:, 1] + 1)[None, :], floored_pos) & anyh[None, :]
+                        need = torch.zeros((S_, int(act.numel())), dtype=torch.int32, device=dev).index_add_(0, set_of_t, must.to(torch.int32)) > 0
+                        st_ = torch.cat([st_, need.sum(dim=1)])
+                    st_ = st_.cpu()
                     n_used, n_hit, a0, n_mask = int(st_[0]), int(st_[1]), int(st_[2]), int(st_[3])
                 n_align += n_used
                 n_spec += scheduled - n_used
@@ -1371,14 +1415,48 @@ class Pipeline:
                 act = hsel
                 rounds += 1
                 o_act, l_act = d_off[act], dlen[act]
+                scheduled = (A - a0) * int(act.numel())
+                if use_rule:
+                    # per set with a non-zero count, one job per sequence of the set over the reads that need the set.  The
+                    # windows go longest first (one argsort a round, as _scan_jobs would per window list); one nonzero lists the
+                    # (set, read) pairs set by set, and the host cuts that list at the counts it already holds.
+                    counts = [int(x) for x in st_[4:4 + S_]]
+                    act_s, o_s, l_s, need_h = act, o_act, l_act, need[:, hidx]
+                    if ragged:
+                        perm = torch.argsort(l_act, descending=True, stable=True)
+                        act_s, o_s, l_s, need_h = act[perm], o_act[perm], l_act[perm], need_h[:, perm]
+                    need_flat = need_h.reshape(-1)
+                    flat = torch.nonzero_static(need_flat, size=sum(counts)).flatten() if hasattr(torch, "nonzero_static") \
+                        else torch.nonzero(need_flat).flatten()
+                    which = flat % n_hit
+                    o_f, l_f, act_f = o_s[which], l_s[which], act_s[which]
+                    rjobs, rmeta, at = [], [], 0
+                    for s_ in range(S_):
+                        if counts[s_]:
+                            o_c, l_c, a_c = o_f[at:at + counts[s_]], l_f[at:at + counts[s_]], act_f[at:at + counts[s_]]
+                            at += counts[s_]
+                            for a in set_adapters[s_]:
+                                if a >= a0:
+                                    rjobs.append((aidx[a], o_c, l_c, hint[a])); rmeta.append((a, a_c))
+                    n_kept += scheduled - sum(int(a_c.shape[0]) for _, a_c in rmeta)
+                    if rjobs:
+                        res, out_r, rec_off = self._scan_jobs(dirty, rjobs, MODE_TWO_PASS, dmax, with_layout=True, presorted=ragged, typ_len=dtyp,
+                                                              floors=[floors[a] for a, _ in rmeta] if floors is not None else None,
+                                                              no_skip_underfilled=True)
+                        full_r = al.middle_hits(out_r, p.middle_threshold)[0] if fused else torch.nan_to_num(identity_of(out_r), nan=0.0)
+                        for (a, a_c), r_, ro in zip(rmeta, res, rec_off):
+                            rec_all[a, a_c] = r_
+                            full_all[a, a_c] = full_r[ro:ro + int(a_c.shape[0])]
+                    continue
                 if prefilter:                                        # the masked reads go through the same proof first
                     rb, rw, rr = self._prefiltered_scan(dirty, o_act, l_act, dmax, list(range(a0, A)), aidx, hint, ks, ragged, dtyp)
                     outs_r = torch.zeros((A - a0, int(act.numel()), RESULT_INTS), dtype=torch.int32, device=dev)
                     outs_r[rb, rw] = rr
                 else:
+                    # (a mask round is a launch of few, short units: no row skipping where the library chunks it -- DESIGN.md 4)
                     outs_r = self._scan_jobs(dirty, [(aidx[a], o_act, l_act, hint[a]) for a in range(a0, A)], MODE_TWO_PASS, dmax,
-                                             sort_lengths=ragged, typ_len=dtyp, floors=floors[a0:] if floors is not None else None)
-                scheduled = (A - a0) * int(act.numel())
+                                             sort_lengths=ragged, typ_len=dtyp, floors=floors[a0:] if floors is not None else None,
+                                             no_skip_underfilled=True)
                 if not torch.is_tensor(outs_r):
                     outs_r = torch.stack(outs_r)                     # [A - a0, active, 8]
                 # (all adapters at once: a loop over the 196 sequences of a barcode panel is ~2 000 tiny launches a round)
@@ -1386,6 +1464,7 @@ class Pipeline:
                 full_all[a0:, act] = al.middle_hits(outs_r.contiguous(), p.middle_threshold)[0] if fused else torch.nan_to_num(identity_of(outs_r), nan=0.0)
         self.stats["pairs_middle"] += n_align
         self.stats["pairs_middle_speculative"] = self.stats.get("pairs_middle_speculative", 0) + n_spec
+        self.stats["pairs_middle_kept_by_mask_rule"] = self.stats.get("pairs_middle_kept_by_mask_rule", 0) + n_kept
         if floors is not None:
             # (the context's running total, read once per call where the device has just been waited for -- the last round's
             # statistics above, or the dirty-read count -- so the 16-byte copy waits for nothing)
