@@ -290,6 +290,38 @@ int pc_middle_paths(pc_ctx *ctx, const void *d_arena, const int64_t *d_read_off,
  * table and scheme; < 0: an error code. */
 int pc_middle_paths_cols(pc_ctx *ctx, int max_len);
 
+/* UMI extraction: the read bases that lie under an adapter's degenerate letters (csrc/pc_umi.h).  Window p = [d_win_off[p],
+ * + d_win_len[p]) of the arena is aligned with adapter `adapter` of the context's table -- ONE adapter per call, a host
+ * value -- exactly as pc_align_paths aligns it, and the path is walked on the device: no operation leaves it.  All
+ * pointers but `ctx` and `rule` are device memory; d_records and d_umi are 16-byte aligned.
+ *   * The adapter's UMI span is rows u0 .. u1 (pc_umi_span): its first and last row whose letter set holds two or more
+ *     bases.  Walking the path forward, a window column belongs to the UMI when a diagonal step consumes it with a span
+ *     row, or an insertion consumes it with a span row behind it and one still ahead (u0 < next row <= u1).  These columns
+ *     are one run [first, first + len); covered = the diagonal steps among them.
+ *   * d_records[p][8] is the record pc_scan_device writes for the pair.  d_umi[p] = {status, first, len, covered}:
+ *       0  complete: the path starts at or before row u0 and consumes row u1 or one behind it
+ *       1  no alignment (the record's field 0 < 0; an empty window included)
+ *       2  the alignment does not qualify under `rule` for a window of side `side` (0: start windows, 1: end windows):
+ *          phase B's condition for a trim -- identity above end_threshold, read_end - read_start >= min_trim_size, not
+ *          flush with the window's inner edge (side 0: read_end != end_size; side 1: read_start != 0).  rule == NULL:
+ *          every alignment qualifies.  extra_end_trim is not read.
+ *       3  the window's edge clipped the span: first, len and covered describe the part that is there
+ *     Statuses 1 and 2 have first = -1, len = covered = 0; so has a span with no column under it (len == 0).
+ *   * LDS and scratch are sized from THIS adapter's rows, not from the table's longest.  Trace and operations live in
+ *     scratch buffers of the context; slicing into launches follows pc_align_paths' rule (PC_PATHS_SCRATCH_MB, read per
+ *     call, never fewer than 64 pairs).
+ *   * PC_ERR_BAD_ARG before anything is launched: an adapter index outside the table, an adapter above 128 rows, an
+ *     adapter without a span, wildcards off (pc_set_wildcards), a side outside 0..1, n < 0.  n == 0 is a no-op.
+ *   * No host round trip; asynchronous on `stream`.  A window above max_len and a walk that leaves its operations are
+ *     caught by the kernel, which writes nothing for that pair, and surface as PC_ERR_INTERNAL at pc_sync. */
+int pc_umi_extract(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len, int64_t n,
+                   int max_len, int adapter, int side, const pc_end_rule *rule, int32_t *d_records, int32_t *d_umi,
+                   void *stream);
+/* Host: the UMI span of adapter `adapter` under the context's letter rule.  -> 1 and *first, *last (0-based rows,
+ * inclusive; either pointer may be NULL), 0 if the adapter has no span (wildcards off included; *first = *last = -1),
+ * PC_ERR_BAD_ARG for an index outside the table. */
+int pc_umi_span(pc_ctx *ctx, int adapter, int *first, int *last);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,
@@ -685,6 +717,13 @@ const char *pc_readset_arena(const pc_readset *rs, int64_t *bytes);
 const int64_t *pc_readset_offsets(const pc_readset *rs);
 const int32_t *pc_readset_lengths(const pc_readset *rs);
 const char *pc_readset_name(const pc_readset *rs, int64_t i);     /* full header, no leading marker */
+/* Appends " " + text[k] to the END of the stored header of read read[k], k = 0 .. n - 1 (host; the name arena is rebuilt
+ * once).  Every writer (pc_readset_write, _write_at, _write_sizes, _write_shared, pc_readset_compress) and
+ * pc_readset_name then give the longer header; a piece number ("_3") still goes before the header's first space, the
+ * text stays at the end.  A read named twice gets both texts, in the order given.  A read index out of range, a NULL or
+ * empty text and a text holding '\n' or '\r' (a NUL ends a C string: it cannot be passed) are PC_ERR_BAD_ARG, and then
+ * nothing has changed.  Pointers pc_readset_name returned before the call are stale after it. */
+int pc_readset_annotate(pc_readset *rs, int64_t n, const int64_t *read, const char *const *text);
 const char *pc_readset_quals(const pc_readset *rs, int64_t i);    /* FASTQ only */
 int pc_readset_is_rna(const pc_readset *rs, int64_t i);
 /* Several FASTQ (or several FASTA) files into ONE read set, in the order given -- the Albacore

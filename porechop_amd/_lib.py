@@ -29,6 +29,7 @@ EXPORTS = [
     "pc_middle_paths", "pc_middle_paths_cols",
     "pc_set_wildcards", "pc_letter_set",
     "pc_scan_device_floored_flags", "pc_round_select", "pc_mask_rule_gate", "pc_mask_rule_must_realign",
+    "pc_umi_extract", "pc_umi_span", "pc_readset_annotate",
 ]
 
 
@@ -106,6 +107,10 @@ def load_library():
     L.pc_middle_paths.restype = c_int
     L.pc_middle_paths_cols.argtypes = [c_vp, c_int]
     L.pc_middle_paths_cols.restype = c_int
+    L.pc_umi_extract.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, ctypes.POINTER(EndRule), c_vp, c_vp, c_vp]
+    L.pc_umi_extract.restype = c_int
+    L.pc_umi_span.argtypes = [c_vp, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    L.pc_umi_span.restype = c_int
     L.pc_sync.argtypes = [c_vp, c_vp]
     L.pc_sync.restype = c_int
     L.pc_copy_windows.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_int, c_vp]
@@ -185,6 +190,8 @@ def load_library():
     L.pc_readset_lengths.restype = c_vp
     L.pc_readset_name.argtypes = [c_vp, c_i64]
     L.pc_readset_name.restype = c_cp
+    L.pc_readset_annotate.argtypes = [c_vp, c_i64, c_vp, ctypes.POINTER(c_cp)]
+    L.pc_readset_annotate.restype = c_int
     L.pc_readset_quals.argtypes = [c_vp, c_i64]
     L.pc_readset_quals.restype = c_cp
     L.pc_readset_is_rna.argtypes = [c_vp, c_i64]

@@ -359,6 +359,45 @@ class Aligner:
         heads = heads.cpu().numpy()
         return recs.cpu().numpy(), heads, decode_paths(heads, ops.cpu().numpy())
 
+    # ---- UMI extraction (pc_paths.hip umi_kernel, pc_umi.h) --------------------------------------------------------------
+    umi = True                 # umi_span / umis: the read bases under an adapter's degenerate letters (pc_umi_extract)
+
+    def umi_span(self, adapter_index):
+        """(first, last) -- the 0-based, inclusive rows of the adapter's UMI span under the context's letter rule: its first
+        and last row whose letter set holds two or more bases -- or None (wildcards off included).  Host (pc_umi_span)."""
+        first, last = ctypes.c_int(-1), ctypes.c_int(-1)
+        rc = self.lib.pc_umi_span(self._ctx, int(adapter_index), ctypes.byref(first), ctypes.byref(last))
+        if rc < 0:
+            check(rc, "pc_umi_span")
+        return (int(first.value), int(last.value)) if rc == 1 else None
+
+    def umis(self, arena, win_off, win_len, adapter_index, side, rule=None, max_len=None, stream=None):
+        """The UMI of n end windows under ONE adapter (pc_umi_extract).  arena uint8[*], win_off int64[n], win_len int32[n]:
+        CUDA tensors; side 0 = start windows, 1 = end windows; rule = (end_size, min_trim_size, extra_end_trim,
+        end_threshold) or None (every alignment qualifies); max_len bounds win_len (None: its maximum, one host round
+        trip).  -> (records int32[n, 8], umi int32[n, 4]) CUDA tensors: the scans' records and {status, first, len,
+        covered} in window columns; status 0 complete, 1 no alignment, 2 does not qualify, 3 span clipped by the window.
+        Asynchronous; call sync()."""
+        import torch
+        assert arena.is_cuda and win_off.is_cuda and win_len.is_cuda
+        assert arena.dtype == torch.uint8 and win_off.dtype == torch.int64 and win_len.dtype == torch.int32
+        assert win_off.is_contiguous() and win_len.is_contiguous()
+        n = int(win_off.shape[0])
+        assert int(win_len.shape[0]) == n
+        if max_len is None:
+            max_len = int(win_len.max().item()) if n else 0
+        records = torch.zeros((n, RESULT_INTS), dtype=torch.int32, device=arena.device)
+        umi = torch.zeros((n, 4), dtype=torch.int32, device=arena.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        r = None
+        if rule is not None:
+            from ._lib import EndRule
+            r = ctypes.byref(EndRule(int(rule[0]), int(rule[1]), int(rule[2]), float(rule[3])))
+        check(self.lib.pc_umi_extract(self._ctx, arena.data_ptr(), win_off.data_ptr(), win_len.data_ptr(), n, int(max_len),
+                                      int(adapter_index), int(side), r, records.data_ptr(), umi.data_ptr(), ctypes.c_void_p(s)),
+              "pc_umi_extract")
+        return records, umi
+
     # ---- paths of middle hits (pc_paths.hip) ----------------------------------------------------------------------------
     def middle_paths_cols(self, max_len):
         """The widest window (columns) a hit of middle_paths can have over reads of up to max_len bases

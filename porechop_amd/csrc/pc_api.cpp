@@ -24,6 +24,7 @@
 #include "pc_bounds.h"
 #include "pc_slow.h"
 #include "pc_paths.h"
+#include "pc_umi.h"
 #include "pc_middle_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
@@ -135,6 +136,7 @@ struct pc_ctx {
     DevBuf d_slow_ad, d_slow_state, d_slow_trace;
     DevBuf d_paths_trace;                    // pc_align_paths: the packed trace of one launch (pc_paths.hip)
     DevBuf d_middle_paths_trace;             // pc_middle_paths: the same for its windows, a buffer of its own
+    DevBuf d_umi_ops;                        // pc_umi_extract: the operations of one launch (its trace is d_paths_trace)
     std::vector<int32_t> last_job_adapter, last_job_adapter_b;
     std::vector<int64_t> last_job_start;
     int last_max_len = -1, last_mode = -1;
@@ -912,7 +914,7 @@ void pc_destroy(pc_ctx *c)
                       &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
                       &c->d_sd_entries, &c->d_sd_meta, &c->d_sd_eq, &c->d_sd_cand, &c->d_sd_count, &c->d_slow_ad, &c->d_slow_state,
-                      &c->d_slow_trace, &c->d_paths_trace, &c->d_middle_paths_trace};
+                      &c->d_slow_trace, &c->d_paths_trace, &c->d_middle_paths_trace, &c->d_umi_ops};
     if (c->h_sd_count) (void)hipHostFree(c->h_sd_count);
     c->h_table_slot[0].release(); c->h_table_slot[1].release();
     for (DevBuf *b : bufs) b->release();
@@ -1177,6 +1179,65 @@ int pc_middle_paths(pc_ctx *c, const void *d_arena, const int64_t *d_read_off, c
     for (int64_t first = 0; first < n; first += a.P) {
         a.first = first; a.count = std::min<int64_t>(a.P, n - first);
         if (pck::launch_middle_paths(a, stream)) return PC_ERR_NO_DEVICE;
+    }
+    return PC_OK;
+}
+
+int pc_umi_span(pc_ctx *c, int adapter, int *first, int *last)
+{
+    if (!c || adapter < 0 || adapter >= (int)c->adapters.size()) return PC_ERR_BAD_ARG;
+    const std::string &s = c->adapters[adapter];
+    const bool wild = c->wildcards;
+    int u0, u1;
+    const bool has = pcu::span([&](int k) { return pcl::letter_set((uint8_t)s[k], wild); }, (int)s.size(), &u0, &u1);
+    if (first) *first = u0;
+    if (last) *last = u1;
+    return has ? 1 : 0;
+}
+
+int pc_umi_extract(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, const int32_t *d_win_len, int64_t n,
+                   int max_len, int adapter, int side, const pc_end_rule *rule, int32_t *d_records, int32_t *d_umi,
+                   void *stream_v)
+{
+    if (!c || n < 0 || max_len < 0 || side < 0 || side > 1) return PC_ERR_BAD_ARG;
+    if (adapter < 0 || adapter >= (int)c->adapters.size() || !c->wildcards) return PC_ERR_BAD_ARG;
+    const int m = (int)c->adapters[adapter].size();
+    if (m > pcb::MAX_ADAPTER) return PC_ERR_BAD_ARG;                 // the code table holds 128 rows per adapter
+    int u0, u1;
+    if (pc_umi_span(c, adapter, &u0, &u1) != 1) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    int rc = upload_panel(c);
+    if (rc) return rc;
+    if (n == 0) return PC_OK;
+    if (!d_arena || !d_win_off || !d_win_len || !d_records || !d_umi) return PC_ERR_BAD_ARG;
+    if (!pcs::fits(max_len, m, c->match, c->mismatch, c->gap_open, c->gap_extend)) {
+        fprintf(stderr, "porechop_amd: scores %d,%d,%d,%d over windows of up to %d bases and an adapter of %d leave the 32-bit range\n",
+                c->match, c->mismatch, c->gap_open, c->gap_extend, max_len, m);
+        return PC_ERR_UNSUPPORTED_SCORES;
+    }
+    // pc_align_paths' slicing rule over THIS adapter's rows: a lane's trace and, behind it, its operations
+    size_t budget = kPathsScratchMB << 20;
+    if (const char *e = getenv("PC_PATHS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
+    const int groups = pcpath::row_groups(m);
+    const int64_t words = std::max<int64_t>(1, pcpath::ops_words(max_len, m));
+    const size_t trace_lane = (size_t)std::max(1, max_len) * (size_t)groups * 4;
+    const int64_t P = pcn::slice_pairs(budget, trace_lane + (size_t)words * 4, n);
+    if ((rc = c->d_paths_trace.ensure((size_t)P * trace_lane + 256))) return rc;
+    if ((rc = c->d_umi_ops.ensure((size_t)P * (size_t)words * 4 + 256))) return rc;
+    pck::UmiArgs a{};
+    a.arena = (const uint8_t *)d_arena; a.win_off = d_win_off; a.win_len = d_win_len;
+    a.ad_sets = c->d_ad_sets.as<uint32_t>() + (size_t)adapter * pcb::MAX_ADAPTER;
+    a.m = m; a.groups = groups; a.max_len = max_len;
+    a.match = c->match; a.mismatch = c->mismatch; a.gap_open = c->gap_open; a.gap_extend = c->gap_extend;
+    a.u0 = u0; a.u1 = u1; a.side = side; a.ruled = rule ? 1 : 0;
+    if (rule) { a.end_size = rule->end_size; a.min_trim_size = rule->min_trim_size; a.end_threshold = rule->end_threshold; }
+    a.records = d_records; a.umi = d_umi;
+    a.trace = c->d_paths_trace.as<uint32_t>(); a.ops = c->d_umi_ops.as<uint32_t>(); a.ops_words = words; a.P = P;
+    a.err = c->d_err.as<uint32_t>();
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    for (int64_t first = 0; first < n; first += P) {
+        a.first = first; a.count = std::min<int64_t>(P, n - first);
+        if (pck::launch_umi(a, stream)) return PC_ERR_NO_DEVICE;
     }
     return PC_OK;
 }

@@ -1677,6 +1677,46 @@ const char *pc_readset_name(const pc_readset *rs, int64_t i)
 {
     return (rs && i >= 0 && i < (int64_t)rs->name_off.size()) ? rs->name_of((size_t)i) : nullptr;
 }
+// " " + text[k] behind the stored header of read read[k]: every writer and pc_readset_name read the header from the name
+// arena, which is rebuilt once, in read order.  Everything is checked before anything changes.
+int pc_readset_annotate(pc_readset *rs, int64_t n, const int64_t *read, const char *const *text)
+{
+    if (!rs || n < 0 || (n > 0 && (!read || !text))) return PC_ERR_BAD_ARG;
+    const int64_t R = (int64_t)rs->name_off.size();
+    size_t extra = 0;
+    for (int64_t k = 0; k < n; ++k) {
+        if (read[k] < 0 || read[k] >= R || !text[k] || !text[k][0]) return PC_ERR_BAD_ARG;
+        if (strpbrk(text[k], "\n\r")) return PC_ERR_BAD_ARG;
+        extra += 1 + strlen(text[k]);
+    }
+    if (n == 0) return PC_OK;
+    // the texts of a read, in the order given (a stable counting sort by read)
+    std::vector<int64_t> first((size_t)R + 1, 0), order((size_t)n);
+    for (int64_t k = 0; k < n; ++k) ++first[(size_t)read[k] + 1];
+    for (int64_t r = 0; r < R; ++r) first[(size_t)r + 1] += first[(size_t)r];
+    {
+        std::vector<int64_t> next(first.begin(), first.end() - 1);
+        for (int64_t k = 0; k < n; ++k) order[(size_t)next[(size_t)read[k]]++] = k;
+    }
+    std::vector<char> fresh;
+    fresh.reserve(rs->name_arena.size() + extra);
+    std::vector<int64_t> fresh_off((size_t)R);
+    for (int64_t r = 0; r < R; ++r) {
+        fresh_off[(size_t)r] = (int64_t)fresh.size();
+        const char *name = rs->name_of((size_t)r);
+        fresh.insert(fresh.end(), name, name + strlen(name));
+        for (int64_t t = first[(size_t)r]; t < first[(size_t)r + 1]; ++t) {
+            const char *s = text[(size_t)order[(size_t)t]];
+            fresh.push_back(' ');
+            fresh.insert(fresh.end(), s, s + strlen(s));
+        }
+        fresh.push_back('\0');
+    }
+    rs->name_arena.resize(fresh.size());
+    memcpy(rs->name_arena.data(), fresh.data(), fresh.size());
+    rs->name_off.swap(fresh_off);
+    return PC_OK;
+}
 const char *pc_readset_quals(const pc_readset *rs, int64_t i)
 {
     return (rs && rs->fastq && i >= 0 && i < (int64_t)rs->qual_off.size()) ? rs->qual_of((size_t)i) : nullptr;

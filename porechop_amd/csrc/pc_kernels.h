@@ -442,4 +442,29 @@ struct MiddlePathArgs : PathArgs {
 };
 int launch_middle_paths(const MiddlePathArgs &a, void *stream);
 
+// umi_kernel: windows first .. first + count of the caller's table against ONE adapter of m rows, whose span of degenerate
+// rows is u0 .. u1 (pc_umi.h).  The LDS rows and the trace's row groups are this adapter's, not the table's.  The path's
+// operations go to a scratch of the launch, [ops_words][P] dwords, and are read back by the lane that wrote them.
+struct UmiArgs {
+    const uint8_t *arena;
+    const int64_t *win_off;      // [n]
+    const int32_t *win_len;      // [n]
+    int64_t first, count;
+    const uint32_t *ad_sets;     // [m] the adapter's rows: sets of read codes (pc_letters.h)
+    int32_t m, groups, max_len;
+    int32_t match, mismatch, gap_open, gap_extend;
+    int32_t u0, u1, side;
+    int32_t ruled;               // 0: every alignment qualifies
+    int32_t end_size, min_trim_size;
+    double end_threshold;
+    int32_t *records;            // [n][8]
+    int32_t *umi;                // [n][4] {status, first, len, covered}
+    uint32_t *trace;             // [max_len][groups][P] dwords
+    uint32_t *ops;               // [ops_words][P] dwords
+    int64_t ops_words;
+    int64_t P;                   // windows of a launch (stride of both scratches)
+    uint32_t *err;
+};
+int launch_umi(const UmiArgs &a, void *stream);
+
 }  // namespace pck

@@ -1,5 +1,5 @@
 // pc_paths.hip -- alignment PATHS, one LANE per alignment, 64 to a one-wave block, any scoring scheme pcs::fits accepts,
-// adapters of the context's table of letter sets (up to 128 bases; pc_letters.h), each lane its own.  Two kernels over one routine:
+// adapters of the context's table of letter sets (up to 128 bases; pc_letters.h), each lane its own.  Three kernels over one routine:
 //   path_kernel         a (window, adapter) pair against the whole window: pcpath::align_path (pc_paths.h), the very
 //                       function tests/host/test_paths.cpp replays base by base against the oracle;
 //   middle_path_kernel  a middle hit: pcpath::align_path_window over a window of a few hundred columns of the hit's
@@ -7,6 +7,9 @@
 //                       can touch), with the read masked as the hit's round of mask-and-realign saw it: the intervals
 //                       of the read's earlier hits read as code 4.  tests/host/test_middle_paths.cpp compares that very function with
 //                       align_path over the whole masked read.
+//   umi_kernel          an end window against ONE adapter with a span of degenerate rows: align_path_sets as in
+//                       path_kernel, then pcu::extract (pc_umi.h) over the lane's own operations -- the read columns under
+//                       the span.  No operation leaves the device.
 // Nothing of the packed kernels is touched: paths are wanted for the few alignments somebody looks at, not for a scan.
 //
 // Layout: the column state (M, H per adapter row) sits in LDS as [row][lane] -- consecutive lanes in consecutive banks,
@@ -22,6 +25,8 @@
 #include "pc_kernels.h"
 #include "pc_middle_paths.h"
 #include "pc_paths.h"
+#include "pc_record.h"
+#include "pc_umi.h"
 
 namespace pck {
 
@@ -131,6 +136,53 @@ __global__ __launch_bounds__(64) void middle_path_kernel(MiddlePathArgs a)
     store_path(a.records, a.heads, a.err, q, d, head, err);
 }
 
+// The UMI of one end window per lane (pc_umi.h): path_kernel's alignment against ONE adapter, uniform over the launch --
+// its rows, its span and the rule are scalars, and the LDS holds this adapter's rows, not the table's longest.  The
+// operations go to the launch's scratch as [word][lane of the launch] (a wave's store of one word is 256 contiguous
+// bytes); the lane that wrote them reads them back, last word first, and keeps only {status, first, len, covered}.
+__global__ __launch_bounds__(64) void umi_kernel(UmiArgs a)
+{
+    extern __shared__ int dyn[];
+    const int lane = threadIdx.x;
+    const int64_t p = (int64_t)blockIdx.x * 64 + lane;       // window of the launch
+    if (p >= a.count) return;
+    const int64_t q = a.first + p;                           // window of the call
+    const int n = a.win_len[q];
+    // the host sized the trace and the operations from max_len: a window outside writes nothing
+    if (n < 0 || n > a.max_len) {
+        atomicAdd(a.err, 1u);
+        return;
+    }
+    const uint8_t *rd = a.arena + a.win_off[q];
+    const uint32_t *ad = a.ad_sets;
+    uint32_t *ops = a.ops + p;
+    const int64_t P = a.P, words = a.ops_words;
+    pcw::Digest d;
+    int32_t head[4];
+    const int err = pcpath::align_path_sets(
+        n, a.m, [&](int k) { return pcc::dna5_code(rd[k]); }, [&](int k) { return ad[k]; }, a.match, a.mismatch, a.gap_open,
+        a.gap_extend, PathMem{dyn, a.m, lane, a.trace, (int64_t)a.groups, P, p}, d, head,
+        [&](int k, uint32_t w) { if (k < words) ops[(int64_t)k * P] = w; });
+    // a walk that left its operations: nothing of it is read back, nothing is written
+    if (err || head[0] < 0 || (int64_t)head[0] > words * pcpath::OPS_PER_WORD) {
+        atomicAdd(a.err, 1u);
+        return;
+    }
+    const Rec rec = {d.read_start, d.read_end, d.adapter_start, d.adapter_end, d.score, d.matches, d.aligned_len, d.full_len};
+    struct { int32_t end_size, min_trim_size; double end_threshold; } rule = {a.end_size, a.min_trim_size, a.end_threshold};
+    int4 u = make_int4(0, -1, 0, 0);
+    if (rec.rs < 0) u.x = 1;
+    else if (a.ruled && !pcu::qualifies(rec, a.side, rule, [](int matches, int len) { return identity(matches, len); })) u.x = 2;
+    else {
+        const pcu::Umi e = pcu::extract(head, [&](int k) { return ops[(int64_t)k * P]; }, a.u0, a.u1);
+        u = make_int4(e.complete ? 0 : 3, e.first, e.len, e.covered);
+    }
+    int32_t *o = a.records + q * TRACE_OUT_INTS;
+    ((int4 *)o)[0] = make_int4(rec.rs, rec.re, rec.as, rec.ae);
+    ((int4 *)o)[1] = make_int4(rec.score, rec.matches, rec.aligned_len, rec.full_len);
+    ((int4 *)(a.umi + q * 4))[0] = u;
+}
+
 template <typename Args>
 int launch(void (*kernel)(Args), const Args &a, void *stream)
 {
@@ -146,5 +198,15 @@ int launch(void (*kernel)(Args), const Args &a, void *stream)
 
 int launch_paths(const PathArgs &a, void *stream) { return launch(path_kernel, a, stream); }
 int launch_middle_paths(const MiddlePathArgs &a, void *stream) { return launch(middle_path_kernel, a, stream); }
+
+int launch_umi(const UmiArgs &a, void *stream)
+{
+    if (a.count <= 0) return 0;
+    const unsigned grid = (unsigned)((a.count + 63) / 64);
+    const size_t lds = (size_t)a.m * 2 * 64 * sizeof(int);          // the CALL's adapter: at most 128 rows, 64 KB
+    (void)hipFuncSetAttribute((const void *)umi_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    hipLaunchKernelGGL(umi_kernel, dim3(grid), dim3(64), lds, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
 
 }  // namespace pck

@@ -1,11 +1,15 @@
-"""`python -m porechop_amd.custom -i reads.fastq -o trimmed.fastq --adapters mine.fasta [--only_custom] [--wildcards]` -- the
+"""`python -m porechop_amd.custom -i reads.fastq -o trimmed.fastq --adapters mine.fasta [--only_custom] [--wildcards] [--umi]` -- the
 command line of `python -m porechop_amd` (the reference's option set, unchanged there) with a custom adapter panel:
   --adapters FASTA   adapter sets as discover.read_adapters reads them (records named <set>_start / <set>_end), added to
                      the built-in panel;
   --only_custom      the FASTA's sets alone;
   --wildcards        IUPAC letters in the panel's adapters stand for their sets of bases (R = AG ... N = ACGT; a read base
                      that is not A/C/G/T/U matches nothing): UMI adapters, degenerate primers, NNNN spacers (DESIGN.md
-                     section 15).
+                     section 15);
+  --umi              (with --wildcards) the read bases under an adapter's degenerate letters are kept: reads whose start or
+                     end adapter has such letters get UMI_start=<bases> and / or UMI_end=<bases> at the end of their header
+                     (DESIGN.md section 16);
+  --umi_report PATH  (with --umi) one TSV row per extracted UMI, in input order.
 It composes with the explain report: --report PATH, --report_paths, --report_middle_paths (porechop_amd.explain)."""
 import sys
 
@@ -17,6 +21,8 @@ def build_custom_parser(prog="porechop_amd.custom"):
     p.add_argument("--adapters", metavar="FASTA", help="custom adapter sets: FASTA records named <set>_start / <set>_end")
     p.add_argument("--only_custom", action="store_true", help="search for the sets of --adapters only, not the built-in panel")
     p.add_argument("--wildcards", action="store_true", help="IUPAC letters in adapters stand for their sets of bases")
+    p.add_argument("--umi", action="store_true", help="tag every read with the bases under its adapters' degenerate letters (needs --wildcards)")
+    p.add_argument("--umi_report", metavar="PATH", help="one TSV row per extracted UMI (needs --umi)")
     p.add_argument("--report", help="per-read explain report (TSV), written in input order")
     p.add_argument("--report_paths", action="store_true", help="append start_cigars / end_cigars to the report")
     p.add_argument("--report_middle_paths", action="store_true", help="append middle_cigars to the report")
@@ -56,6 +62,8 @@ def main(argv=None):
     kw = {}
     if a.report is not None or a.report_paths or a.report_middle_paths:
         kw = dict(report=a.report, report_paths=a.report_paths, report_middle_paths=a.report_middle_paths)
+    if a.umi or a.umi_report is not None:
+        kw.update(umi=a.umi, umi_report=a.umi_report)
     run_cli(a, adapter_panel=panel, wildcards=a.wildcards, **kw)
 
 

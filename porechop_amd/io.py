@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from ._lib import load_library
+from ._lib import check, load_library
 
 
 def pack_reads(arena, nbases=None, out=None):
@@ -231,6 +231,23 @@ class ReadSet:
 
     def name(self, i):
         return self.lib.pc_readset_name(self._h, i).decode()
+
+    def annotate(self, reads, texts):
+        """Append " " + texts[k] to the END of the stored header of read reads[k] (pc_readset_annotate): every writer and name()
+        give the longer header afterwards, a piece number still goes before the header's first space.  A read named twice
+        gets both texts in order.  A read outside the set, an empty text or one holding a line break or a NUL raises
+        ValueError, and nothing has changed."""
+        reads = np.ascontiguousarray(reads, dtype=np.int64)
+        raw = [t if isinstance(t, bytes) else t.encode() for t in texts]
+        if reads.shape[0] != len(raw):
+            raise ValueError("annotate: %d reads and %d texts" % (reads.shape[0], len(raw)))
+        if any(b"\0" in t for t in raw):                        # (a NUL would end the C string: caught here)
+            raise ValueError("annotate: a text holds a NUL")
+        arr = (ctypes.c_char_p * max(1, len(raw)))(*raw)
+        rc = self.lib.pc_readset_annotate(self._h, len(raw), reads.ctypes.data, arr)
+        if rc == -3:
+            raise ValueError("annotate: a read outside the set, or a text that is empty or holds a line break")
+        check(rc, "pc_readset_annotate")
 
     def seq(self, i):
         o, n = int(self.offsets[i]), int(self.lengths[i])

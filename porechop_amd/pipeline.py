@@ -566,6 +566,59 @@ class Pipeline:
                 jobs.append((self.seq_index[s.end[1]], eo, el)); where.append((1, si))
         return jobs, where
 
+    def umi_adapters(self, matching):
+        """[(side, set index, adapter index, (u0, u1))] for the start (side 0) and end (side 1) sequences of the `matching`
+        sets that have a UMI span (Aligner.umi_span: a row whose letter stands for two or more bases), in matching order."""
+        if not getattr(self.aligner, "umi", False):
+            raise RuntimeError("this aligner extracts no UMIs (Aligner.umis)")
+        out = []
+        for si in matching:
+            s = self.sets[si]
+            for side, ad in ((0, s.start), (1, s.end)):
+                if ad is not None:
+                    ai = self.seq_index[ad[1]]
+                    span = self.aligner.umi_span(ai)
+                    if span is not None:
+                        out.append((side, si, ai, span))
+        return out
+
+    def end_umis(self, reads: DeviceReads, matching: List[int]):
+        """The UMI of every read's start and end: the read bases under the degenerate rows of the matching sets' adapters
+        (DESIGN.md section 16).  One Aligner.umis call per UMI adapter over the end windows of its side, under phase B's
+        rule (this pipeline's end_size, min_trim_size, extra_end_trim, end_threshold); per read and side the complete
+        extraction (status 0) with the highest alignment score is kept, ties going to the adapter that comes first in
+        `matching`.  -> [(set, first, length, covered) for the start side, the same for the end side], int32[R] device
+        tensors each: set = index into self.sets, -1 where the read has no UMI on that side; first = the UMI's first base in
+        WHOLE-READ coordinates (-1 without one); covered = span rows aligned to a read base."""
+        R = reads.n
+        p = self.p
+        dev = self.device
+        rule = (p.end_size, p.min_trim_size, p.extra_end_trim, p.end_threshold)
+        adapters = self.umi_adapters(matching)
+        self.stats.setdefault("umi_pairs", 0)
+        out = []
+        for side, name in ((0, "start"), (1, "end")):
+            best_set = torch.full((R,), -1, dtype=torch.int32, device=dev)
+            best_score = torch.zeros(R, dtype=torch.int32, device=dev)
+            best = torch.zeros((R, 3), dtype=torch.int32, device=dev)
+            best[:, 0] = -1
+            mine = [a for a in adapters if a[0] == side]
+            if R and mine:
+                off, wl = self._end_windows(reads, None, name)
+                off, wl = off.to(torch.int64).contiguous(), wl.to(torch.int32).contiguous()
+                for _, si, ai, _span in mine:
+                    recs, umi = self.aligner.umis(self._ends_arena(reads), off, wl, ai, side, rule=rule, max_len=p.end_size)
+                    self.stats["umi_pairs"] = self.stats.get("umi_pairs", 0) + R
+                    better = (umi[:, 0] == 0) & ((best_set < 0) | (recs[:, 4] > best_score))      # strict: the earlier adapter keeps a tie
+                    best_set = torch.where(better, torch.full_like(best_set, si), best_set)
+                    best_score = torch.where(better, recs[:, 4], best_score)
+                    best = torch.where(better[:, None], umi[:, 1:4], best)
+                if side == 1:                          # window columns -> read coordinates
+                    shift = (reads.length.to(torch.int32) - wl)
+                    best[:, 0] = torch.where(best[:, 0] >= 0, best[:, 0] + shift, best[:, 0])
+            out.append((best_set, best[:, 0].contiguous(), best[:, 1].contiguous(), best[:, 2].contiguous()))
+        return out
+
     @property
     def native_reduce(self):
         """The per-read reduction of phase B runs as a library kernel (pc_phase_b_reduce) on the GPU;

@@ -75,6 +75,8 @@ class RunResult:
     first_read: int = 0
     local_reads: Optional[int] = None
     explain: Optional["RunExplain"] = None                       # run(..., report=PATH): why every read was trimmed and called
+    # run(..., umi=True): per read (start, end), each None or (set name, first base in the read, length, covered, bases)
+    umis: Optional[List[tuple]] = None
 
 
 @dataclass
@@ -339,9 +341,10 @@ def gz_out_hint(opts, output, barcode_dir, input_path):
         return False
 
 
-def _open_pipeline(opts, device, aligner, adapter_panel, wildcards=False):
+def _open_pipeline(opts, device, aligner, adapter_panel, wildcards=False, umi=False):
     """-> (adapter panel, Pipeline) for a run's options.  wildcards: IUPAC letters in the panel's adapters stand for their sets of
-    bases (ScanParams.wildcards); not an Option -- the options are the reference's."""
+    bases (ScanParams.wildcards); not an Option -- the options are the reference's.  umi: the run keeps the read bases under the
+    adapters' degenerate letters -- a panel none of whose sets has such a letter is a UsageError."""
     panel = list(adapter_panel) if adapter_panel is not None else panel_rules.load_panel()
     params = ScanParams(end_size=opts.end_size, min_trim_size=opts.min_trim_size, extra_end_trim=opts.extra_end_trim,
                         end_threshold=opts.end_threshold, middle_threshold=opts.middle_threshold,
@@ -352,7 +355,48 @@ def _open_pipeline(opts, device, aligner, adapter_panel, wildcards=False):
         # a one-shot run should not wait for hiprtc: specialised kernels are compiled on a worker
         # thread and picked up by later launches (pc_jit_async, include/porechop_amd.h)
         pl.aligner.lib.pc_jit_async(1)
+    if umi and not pl.umi_adapters(range(len(pl.sets))):
+        if aligner is None:
+            pl.close()
+        raise UsageError("Error: --umi needs an adapter with degenerate letters (IUPAC codes such as N, V or R): none of the panel's sets has one")
     return panel, pl
+
+
+UMI_REPORT_COLUMNS = ["name", "side", "set", "read_first", "length", "covered", "span_length", "umi"]
+
+
+def umi_report_header():
+    return "#" + "\t".join(UMI_REPORT_COLUMNS) + "\n"
+
+
+def _tag_umis(rs, sc, pl):
+    """What run(umi=True) does with the UMIs of a scanned ReadSet before any piece of it is written: the bases are taken from
+    the host reads at the coordinates Pipeline.end_umis returned -- the bytes as they stand in the input, in read orientation
+    on either side --, every read with one gets UMI_start=<bases> and / or UMI_end=<bases> at the end of its stored header
+    (ReadSet.annotate: all pieces of a split read carry them), -> (RunResult.umis for these reads, the rows of the UMI report:
+    one per extracted UMI, in read order, start before end).  A side whose span has no read base under it (length 0) has no UMI."""
+    R = rs.count
+    per_read = [[None, None] for _ in range(R)]
+    tagged, texts, rows = [], [], []
+    if sc.umis is not None:
+        span_len = {(side, si): span[1] - span[0] + 1 for side, si, _ai, span in pl.umi_adapters(range(len(pl.sets)))}
+        found = []
+        for side, (sets, first, length, covered) in enumerate(sc.umis):
+            for r in np.nonzero((sets >= 0) & (length > 0))[0].tolist():
+                found.append((r, side, int(sets[r]), int(first[r]), int(length[r]), int(covered[r])))
+        found.sort()
+        for r, side, si, first, length, covered in found:
+            at = int(rs.offsets[r]) + first
+            assert 0 <= first and first + length <= int(rs.lengths[r])
+            bases = rs.arena[at:at + length].tobytes().decode("latin-1")
+            per_read[r][side] = (pl.sets[si].name, first, length, covered, bases)
+            tagged.append(r)
+            texts.append(("UMI_end=" if side else "UMI_start=") + bases)
+            rows.append("%s\t%s\t%s\t%d\t%d\t%d\t%d\t%s\n" % (rs.name(r).split(" ")[0], "end" if side else "start", pl.sets[si].name, first,
+                                                                length, covered, span_len[(side, si)], bases))
+        if tagged:
+            rs.annotate(tagged, texts)
+    return [tuple(x) for x in per_read], "".join(rows)
 
 
 def _upload(rs, dev, lo=0, hi=None):
@@ -531,20 +575,28 @@ class _Scan:
     bin_names: Optional[List[str]]           # None when not demultiplexing
     calls: Optional[List[str]]               # bin name per read, "none" without a call
     middle_cigars: Optional[List[str]] = None   # per row of `hits`, "read_first|adapter_first|CIGAR" (report_middle_paths)
+    umis: Optional[list] = None              # run(umi=True): Pipeline.end_umis on the host: per side (set, first, length, covered) [R]
 
 
 def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=lambda *a, **k: None, explain=None, read_base=0,
-                  gather=None, explain_paths=False, middle_paths=False):
+                  gather=None, explain_paths=False, middle_paths=False, umi=False):
     """_scan_reads for R resident reads, then everything a run needs of it on the host -> _Scan.  The hits' reads are numbered
     from read_base.  gather: called with the device tensors (start_trim, end_trim, bin index, hits [H, 4]) before they leave the
     device -> the same four for the reads the _Scan is to cover (run() gathers every rank's there).  middle_paths: with the
-    path of every middle hit (never together with gather)."""
+    path of every middle hit (never together with gather).  umi: with Pipeline.end_umis of the reads, after phase B (never
+    together with gather)."""
     dev = pl.device
     mp_parts = [] if middle_paths else None
     start_trim, end_trim, ci, hits = _scan_reads(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, explain, explain_paths,
                                                  mp_parts)
+    umis = None
+    if umi and R and match_idx:
+        assert gather is None
+        umis = pl.end_umis(reads, match_idx)
     if hasattr(pl.aligner, "sync"):
         pl.aligner.sync()
+    if umis is not None:
+        umis = [tuple(x.cpu().numpy() for x in side) for side in umis]
     if hits is not None and hits.read.numel():
         h = torch.stack([hits.read + read_base, hits.adapter.to(torch.int64), hits.start.to(torch.int64),
                          hits.end.to(torch.int64)], dim=1)
@@ -569,7 +621,7 @@ def _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap=l
             heads = heads.cpu().numpy()
             middle_cigars += ["%d|%d|%s" % (int(hd[1]), int(hd[2]), cigar(t)) for hd, t in zip(heads, decode_paths(heads, ops.cpu().numpy()))]
         assert len(middle_cigars) == h.shape[0]
-    return _Scan(start_trim.cpu().numpy(), end_trim.cpu().numpy(), h, identity, names, calls, middle_cigars)
+    return _Scan(start_trim.cpu().numpy(), end_trim.cpu().numpy(), h, identity, names, calls, middle_cigars, umis)
 
 
 def _concat_explain(blocks):
@@ -648,7 +700,8 @@ def _stream_block_bytes():
 
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
-                 report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False) -> Optional[RunResult]:
+                 report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False,
+                 umi_report: str = None) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -656,7 +709,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     that is per read in Porechop (phases B and C, barcode calls, splitting, naming), so the output files are the ones
     run() writes.  Plain FASTA files (cut where a line begins with '>') and the gzip forms of both stream the same way.
     report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths and
-    report_middle_paths as in run().
+    report_middle_paths as in run().  umi / umi_report as in run(): every block's reads are tagged before the block goes to
+    the writer, the UMI report is appended block after block (the same bytes as a whole run's).
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
@@ -686,7 +740,13 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     res = RunResult(n_reads=0, read_type="FASTQ" if first.is_fastq else "FASTA")     # (plain FASTA streams too: cut at '>' lines)
     busy = {"load": time.perf_counter() - t_start, "scan": 0.0, "write": 0.0}
 
-    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards)
+    try:
+        panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
+    except UsageError:
+        first.close()
+        if gz_in is not None:
+            gz_in.close()
+        raise
 
     fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
     res.out_format = fmt
@@ -782,10 +842,14 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     st_all, et_all, calls_all = [], [], []
     matching = match_idx = orientation = None
     report_fh, ex_blocks = None, []
+    umi_fh, umis_all = None, []
     try:
         if report is not None:
             report_fh = open(report, "w")
             report_fh.write(report_header(report_paths, report_middle_paths))
+        if umi_report is not None:
+            umi_fh = open(umi_report, "w")
+            umi_fh.write(umi_report_header())
         rs = first
         while rs is not None:
             if failure:
@@ -800,13 +864,18 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 res.barcode_orientation = orientation
             ex_parts = [] if report is not None else None
             sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, explain=ex_parts, explain_paths=report_paths,
-                               middle_paths=report_middle_paths)
+                               middle_paths=report_middle_paths, umi=umi)
             if barcode_dir is not None:
                 calls_all.extend(sc.calls)
             if report is not None:
                 ex = _host_explain(ex_parts, R, pl, match_idx, sc, None, report_paths)
                 report_fh.write(report_rows(ex, [rs.name(i) for i in range(R)], rs.lengths))
                 ex_blocks.append(ex)
+            if umi:
+                block_umis, umi_rows = _tag_umis(rs, sc, pl)
+                umis_all.extend(block_umis)
+                if umi_fh is not None:
+                    umi_fh.write(umi_rows)
             pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
             res.middle_hit_reads += n_split
             res.n_reads += R
@@ -833,12 +902,16 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
             gz_in.close()
         if report_fh is not None:
             report_fh.close()
+        if umi_fh is not None:
+            umi_fh.close()
     if report is not None and ex_blocks:
         res.explain = _concat_explain(ex_blocks)
+    if umi:
+        res.umis = umis_all
     if failure:
         # a streamed run that fails part-way (a later block that cannot be parsed, a full disk) has already written the
         # earlier blocks: a whole-file run would have written nothing, so nothing is left behind here either
-        for path in list(paths) + ([report] if report is not None else []):
+        for path in list(paths) + ([report] if report is not None else []) + ([umi_report] if umi_report is not None else []):
             try:
                 if path and path != "-" and os.path.isfile(path):
                     os.remove(path)
@@ -1028,7 +1101,7 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
         adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False,
-        report_middle_paths: bool = False, wildcards: bool = False) -> RunResult:
+        report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False, umi_report: str = None) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1048,6 +1121,14 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     entry of middle_hits its path as read_first|adapter_first|CIGAR in trimmed-read coordinates, against the read masked as
     its round of mask-and-realign saw it (Pipeline.middle_hit_paths, Aligner.middle_paths).  Without
     it every report is byte for byte what it is without this option.
+
+    umi=True (with wildcards=True) keeps the UMIs the trim would throw away: the read bases under the degenerate letters of
+    the matching sets' start and end adapters (Pipeline.end_umis), taken from the input as they stand
+    -- the end side is NOT reverse-complemented.  A read with one gets UMI_start=<bases> and / or UMI_end=<bases> at the end of
+    its header, on every piece written of it; RunResult.umis holds, per read, (start, end), each None or (set name, first
+    base in the read, length, covered span rows, bases).  umi_report=PATH writes one TSV row per extracted UMI
+    (UMI_REPORT_COLUMNS, a '#' header line), in input order, start before end.  Trims, calls and sequences are what they are
+    without the option; off, so is every byte.  Not available in a sharded run.
 
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
@@ -1073,11 +1154,18 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         raise UsageError("Error: --report_middle_paths needs --report")
     if report is not None and sharded:
         raise UsageError("Error: the per-read report is not available in a sharded run (one process per GPU): run it in a single process")
+    if umi and not wildcards:
+        raise UsageError("Error: --umi needs --wildcards")
+    if umi_report is not None and not umi:
+        raise UsageError("Error: --umi_report needs --umi")
+    if umi and sharded:
+        raise UsageError("Error: UMI extraction is not available in a sharded run (one process per GPU): run it in a single process")
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
-                                report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards)
+                                report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards,
+                                umi=umi, umi_report=umi_report)
         if streamed is not None:
             return streamed
 
@@ -1105,7 +1193,11 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     check_idx = check_idx[(check_idx >= lo_r) & (check_idx < hi_r)] - lo_r
     lap("load")
 
-    panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards)
+    try:
+        panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
+    except UsageError:
+        rs.close()
+        raise
     try:
         reads = _upload(rs, pl.device, lo_r, hi_r)
         lap("upload", sync=True)
@@ -1125,7 +1217,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
 
         ex_parts = [] if report is not None else None
         sc = _scan_to_host(pl, reads, R, match_idx, opts, barcode_dir, orientation, lap, ex_parts, read_base=lo_r,
-                           gather=gather if sharded else None, explain_paths=report_paths, middle_paths=report_middle_paths)
+                           gather=gather if sharded else None, explain_paths=report_paths, middle_paths=report_middle_paths, umi=umi)
         if rank != 0:
             res.start_trim, res.end_trim = sc.st, sc.et
             return res                                           # rank 0 writes
@@ -1139,6 +1231,13 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
                 fh.write(report_header(report_paths, report_middle_paths))
                 fh.write(report_rows(res.explain, [rs.name(i) for i in range(R)], rs.lengths))
             lap("report")
+        if umi:
+            res.umis, umi_rows = _tag_umis(rs, sc, pl)
+            if umi_report is not None:
+                with open(umi_report, "w") as fh:
+                    fh.write(umi_report_header())
+                    fh.write(umi_rows)
+            lap("umi")
 
         # ---- which pieces of which reads -------------------------------------------------
         fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
