@@ -322,6 +322,24 @@ int pc_umi_extract(pc_ctx *ctx, const void *d_arena, const int64_t *d_win_off, c
  * PC_ERR_BAD_ARG for an index outside the table. */
 int pc_umi_span(pc_ctx *ctx, int adapter, int *first, int *last);
 
+/* UMI neighbours: which of n keys lie within max_dist edits of one another (csrc/pc_umi_dist.h, csrc/pc_umi_groups.hip) --
+ * the all-against-all pass behind UMI groups.  All pointers but `ctx` are device memory.
+ *   * Key k is up to 64 bases as two bit planes d_planes[k] = {p0, p1} and a length d_len[k]: base t has code c (A C G T/U =
+ *     0 1 2 3), bit t of p0 is c & 1, bit t of p1 is c >> 1.  Plane bits at and above the length are ignored.
+ *   * Every pair i < j whose unit-cost edit distance (Levenshtein) is <= max_dist is reported ONCE as d_pairs[slot] =
+ *     {i, j, distance}, in no particular order.  *d_found is zeroed by the call on `stream` and counts ALL such pairs; only
+ *     those that draw a slot below `cap` are written.  *d_found > cap therefore means the list is INCOMPLETE: call again
+ *     with cap >= *d_found.  An incomplete list must never be consumed as proof that a key has no neighbour.
+ *   * max_len bounds the lengths: <= 32 runs the 32-bit kernel, anything else the 64-bit one.  A key whose length is
+ *     outside 0 .. max_len has no pairs, is counted in the context's error word and surfaces as PC_ERR_INTERNAL at pc_sync.
+ *   * PC_ERR_BAD_ARG before anything is launched: n < 0, n > 2^31 - 1, max_len or max_dist outside 0 .. 64, cap < 0, d_found
+ *     NULL.  n < 2 zeroes *d_found and launches nothing else.
+ *   * Nothing outside the three input arrays is read; every index and the counter are 64-bit; no host round trip;
+ *     asynchronous on `stream`.  PC_UMI_NO_PRUNE=1 (read per call) runs the DP for every pair instead of settling most of
+ *     them by the lower bound: the same pairs, for tests and measurements. */
+int pc_umi_neighbours(pc_ctx *ctx, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                      int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,

@@ -398,6 +398,37 @@ class Aligner:
               "pc_umi_extract")
         return records, umi
 
+    # ---- UMI neighbours (pc_umi_groups.hip umi_neighbours_kernel, pc_umi_dist.h) -----------------------------------------
+    def umi_neighbours(self, planes, lens, max_dist, cap=None, stream=None):
+        """Every pair i < j of n UMI keys whose edit distance is <= max_dist (pc_umi_neighbours).  planes int64[n, 2] (the bit
+        planes p0, p1 of umi_groups.pack), lens int32[n]: CUDA tensors.  -> int32[m, 3] CUDA tensor {i, j, distance} of ALL
+        such pairs, sorted by (i, j).  The list handed on is never incomplete: `found` is read after a sync, and when it is
+        above cap (default: max(4 n, 1024)) the call is made again with cap = found -- a truncated list taken as proof of "no
+        neighbour" would be wrong grouping.  max_len comes from lens.max().  A length outside 0..64 raises at the sync."""
+        import torch
+        assert planes.is_cuda and lens.is_cuda and planes.dtype == torch.int64 and lens.dtype == torch.int32
+        assert planes.is_contiguous() and lens.is_contiguous()
+        n = int(lens.shape[0])
+        assert tuple(planes.shape) == (n, 2)
+        max_len = min(64, max(0, int(lens.max().item()))) if n else 0
+        cap = max(4 * n, 1024) if cap is None else int(cap)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        found = torch.zeros(1, dtype=torch.int64, device=lens.device)
+        while True:
+            pairs = torch.empty((cap, 3), dtype=torch.int32, device=lens.device)
+            check(self.lib.pc_umi_neighbours(self._ctx, planes.data_ptr(), lens.data_ptr(), n, max_len, int(max_dist), pairs.data_ptr(),
+                                             cap, found.data_ptr(), ctypes.c_void_p(s)), "pc_umi_neighbours")
+            self.sync(s)
+            m = int(found.item())
+            if m <= cap:
+                break
+            cap = m
+        pairs = pairs[:m]
+        if m:
+            order = torch.argsort(pairs[:, 0].to(torch.int64) * n + pairs[:, 1].to(torch.int64))
+            pairs = pairs[order]
+        return pairs.contiguous()
+
     # ---- paths of middle hits (pc_paths.hip) ----------------------------------------------------------------------------
     def middle_paths_cols(self, max_len):
         """The widest window (columns) a hit of middle_paths can have over reads of up to max_len bases

@@ -25,6 +25,7 @@
 #include "pc_slow.h"
 #include "pc_paths.h"
 #include "pc_umi.h"
+#include "pc_umi_dist.h"
 #include "pc_middle_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
@@ -1239,6 +1240,26 @@ int pc_umi_extract(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
         a.first = first; a.count = std::min<int64_t>(P, n - first);
         if (pck::launch_umi(a, stream)) return PC_ERR_NO_DEVICE;
     }
+    return PC_OK;
+}
+
+int pc_umi_neighbours(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                      int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream_v)
+{
+    if (!c || !d_found || n < 0 || n > (int64_t)INT32_MAX || cap < 0) return PC_ERR_BAD_ARG;
+    if (max_len < 0 || max_len > pcud::MAX_LEN || max_dist < 0 || max_dist > pcud::MAX_LEN) return PC_ERR_BAD_ARG;
+    if (n >= 2 && (!d_planes || !d_len || (cap > 0 && !d_pairs))) return PC_ERR_BAD_ARG;
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipMemsetAsync(d_found, 0, sizeof(int64_t), stream));
+    if (n < 2) return PC_OK;
+    const char *e = getenv("PC_UMI_NO_PRUNE");                       // read per call: the DP for every pair
+    pck::UmiNeighboursArgs a{};
+    a.planes = d_planes; a.len = d_len; a.n = n; a.max_len = max_len; a.max_dist = max_dist;
+    a.prune = (e && atoi(e) != 0) ? 0 : 1;
+    a.pairs = d_pairs; a.cap = cap; a.found = (unsigned long long *)d_found;
+    a.err = c->d_err.as<uint32_t>();
+    if (pck::launch_umi_neighbours(a, stream)) return PC_ERR_NO_DEVICE;
     return PC_OK;
 }
 

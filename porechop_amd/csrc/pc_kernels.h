@@ -467,4 +467,18 @@ struct UmiArgs {
 };
 int launch_umi(const UmiArgs &a, void *stream);
 
+// umi_neighbours_kernel (pc_umi_groups.hip): every pair i < j of n keys whose edit distance (pc_umi_dist.h) is <= max_dist.
+struct UmiNeighboursArgs {
+    const uint64_t *planes;      // [n][2] bit planes p0, p1
+    const int32_t *len;          // [n]
+    int64_t n;
+    int32_t max_len, max_dist;
+    int32_t prune;               // 0: the DP runs for every pair (PC_UMI_NO_PRUNE)
+    int32_t *pairs;              // [cap][3] {i, j, distance}
+    int64_t cap;
+    unsigned long long *found;   // every pair within max_dist, written or not
+    uint32_t *err;
+};
+int launch_umi_neighbours(const UmiNeighboursArgs &a, void *stream);
+
 }  // namespace pck

@@ -9,7 +9,12 @@ command line of `python -m porechop_amd` (the reference's option set, unchanged 
   --umi              (with --wildcards) the read bases under an adapter's degenerate letters are kept: reads whose start or
                      end adapter has such letters get UMI_start=<bases> and / or UMI_end=<bases> at the end of their header
                      (DESIGN.md section 16);
-  --umi_report PATH  (with --umi) one TSV row per extracted UMI, in input order.
+  --umi_report PATH  (with --umi) one TSV row per extracted UMI, in input order;
+  --umi_groups PATH  (with --umi) which reads come from one molecule: one TSV row per read with a UMI key -- its group, the
+                     key, the reads of the key and of the group, the group's representative.  The
+                     distinct keys are compared all against all on the GPU by edit distance;
+                     --umi_group_by start|end|both (default: both when both adapters carry a UMI), --umi_max_dist N (2),
+                     --umi_group_method directional|cluster, --umi_group_max_keys N (refuse more distinct keys than N).
 It composes with the explain report: --report PATH, --report_paths, --report_middle_paths (porechop_amd.explain)."""
 import sys
 
@@ -23,6 +28,13 @@ def build_custom_parser(prog="porechop_amd.custom"):
     p.add_argument("--wildcards", action="store_true", help="IUPAC letters in adapters stand for their sets of bases")
     p.add_argument("--umi", action="store_true", help="tag every read with the bases under its adapters' degenerate letters (needs --wildcards)")
     p.add_argument("--umi_report", metavar="PATH", help="one TSV row per extracted UMI (needs --umi)")
+    p.add_argument("--umi_groups", metavar="PATH", help="one TSV row per read with a UMI key: its group of reads of one molecule (needs --umi)")
+    p.add_argument("--umi_group_by", choices=["start", "end", "both"], default=None,
+                   help="the UMIs that make a read's key (default: both when both adapters carry one, else the side that does)")
+    p.add_argument("--umi_max_dist", type=int, default=2, help="keys within this many edits are neighbours (default: 2)")
+    p.add_argument("--umi_group_method", choices=["directional", "cluster"], default="directional",
+                   help="directional: a key joins a neighbour with at least 2n-1 of its n reads; cluster: connected components")
+    p.add_argument("--umi_group_max_keys", type=int, default=1 << 20, help="refuse to compare more distinct keys than this (default: 1048576)")
     p.add_argument("--report", help="per-read explain report (TSV), written in input order")
     p.add_argument("--report_paths", action="store_true", help="append start_cigars / end_cigars to the report")
     p.add_argument("--report_middle_paths", action="store_true", help="append middle_cigars to the report")
@@ -64,6 +76,9 @@ def main(argv=None):
         kw = dict(report=a.report, report_paths=a.report_paths, report_middle_paths=a.report_middle_paths)
     if a.umi or a.umi_report is not None:
         kw.update(umi=a.umi, umi_report=a.umi_report)
+    if a.umi_groups is not None:
+        kw.update(umi=a.umi, umi_groups=a.umi_groups, umi_group_by=a.umi_group_by, umi_max_dist=a.umi_max_dist,
+                  umi_group_method=a.umi_group_method, umi_group_max_keys=a.umi_group_max_keys)
     run_cli(a, adapter_panel=panel, wildcards=a.wildcards, **kw)
 
 

@@ -77,6 +77,8 @@ class RunResult:
     explain: Optional["RunExplain"] = None                       # run(..., report=PATH): why every read was trimmed and called
     # run(..., umi=True): per read (start, end), each None or (set name, first base in the read, length, covered, bases)
     umis: Optional[List[tuple]] = None
+    # run(..., umi_groups=PATH): per read None (no key) or (group id from 1, the group's representative key)
+    umi_groups: Optional[List[Optional[tuple]]] = None
 
 
 @dataclass
@@ -399,6 +401,49 @@ def _tag_umis(rs, sc, pl):
     return [tuple(x) for x in per_read], "".join(rows)
 
 
+def _check_umi_group_options(umi, umi_groups, by, max_dist, method):
+    """The refusals of run(umi_groups=PATH) that need no panel."""
+    from . import umi_groups as ug
+    if umi_groups is None:
+        return
+    if not umi:
+        raise UsageError("Error: --umi_groups needs --umi")
+    if by is not None and by not in ug.BY:
+        raise UsageError("Error: --umi_group_by must be one of start, end, both (got %r)" % (by,))
+    if method not in ug.METHODS:
+        raise UsageError("Error: --umi_group_method must be one of directional, cluster (got %r)" % (method,))
+    if not 0 <= int(max_dist) <= ug.MAX_KEY:
+        raise UsageError("Error: --umi_max_dist must lie in 0..%d" % ug.MAX_KEY)
+
+
+def _umi_group_by(pl, by):
+    """Which UMIs make a read's key: `by` as given when the panel has a span on every side it names (else a UsageError), and for
+    None "both" when the panel has spans on both sides, else the side that has one."""
+    sides = {side for side, _si, _ai, _span in pl.umi_adapters(range(len(pl.sets)))}
+    if by is None:
+        return "both" if sides == {0, 1} else ("start" if 0 in sides else "end")
+    for side, word in ((0, "start"), (1, "end")):
+        if by in (word, "both") and side not in sides:
+            raise UsageError("Error: --umi_group_by %s needs degenerate letters in a %s adapter: the panel has none there" % (by, word))
+    return by
+
+
+def _group_umis(path, umis, names, pl, by, max_dist, method, max_keys):
+    """run(umi_groups=PATH) after the last read: the reads' keys, the pairs of distinct keys within max_dist edits -- on the
+    GPU when the aligner has umi_neighbours, in numpy otherwise --, the groups (porechop_amd.umi_groups) and the TSV ->
+    RunResult.umi_groups."""
+    from . import umi_groups as ug
+    try:
+        per_read, rows = ug.assign(umis, names, by, int(max_dist), method, int(max_keys), pl.aligner, pl.device)
+    except OverflowError as e:
+        raise UsageError("Error: %s distinct UMI keys are more than --umi_group_max_keys %d allows: the all-against-all pass grows "
+                         "with the square of their number; raise --umi_group_max_keys to run it all the same" % (e.args[0], int(max_keys)))
+    with open(path, "w") as fh:
+        fh.write(ug.groups_header())
+        fh.write(rows)
+    return per_read
+
+
 def _upload(rs, dev, lo=0, hi=None):
     """Reads [lo, hi) of a ReadSet (default: all of it, None for no ReadSet) on the device -> DeviceReads, None when there are
     none.  A range takes its slice of the arena and 64 bytes past it (>= 16 must be readable past the end: the kernels fetch 16
@@ -701,7 +746,8 @@ def _stream_block_bytes():
 def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, aligner=None,
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
                  report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False,
-                 umi_report: str = None) -> Optional[RunResult]:
+                 umi_report: str = None, umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2,
+                 umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -710,11 +756,13 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     run() writes.  Plain FASTA files (cut where a line begins with '>') and the gzip forms of both stream the same way.
     report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths and
     report_middle_paths as in run().  umi / umi_report as in run(): every block's reads are tagged before the block goes to
-    the writer, the UMI report is appended block after block (the same bytes as a whole run's).
+    the writer, the UMI report is appended block after block (the same bytes as a whole run's).  umi_groups and its options
+    as in run(): the groups are made after the last block, over the UMIs of all blocks.
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
     import threading
+    _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
     block_bytes = block_bytes or _stream_block_bytes()
     size = os.path.getsize(input_path)
     t_start = time.perf_counter()
@@ -742,6 +790,12 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
 
     try:
         panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
+        try:
+            group_by = _umi_group_by(pl, umi_group_by) if umi_groups is not None else None
+        except UsageError:
+            if aligner is None:
+                pl.close()
+            raise
     except UsageError:
         first.close()
         if gz_in is not None:
@@ -843,6 +897,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     matching = match_idx = orientation = None
     report_fh, ex_blocks = None, []
     umi_fh, umis_all = None, []
+    names_all, groups_all = [], None
     try:
         if report is not None:
             report_fh = open(report, "w")
@@ -871,6 +926,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                 ex = _host_explain(ex_parts, R, pl, match_idx, sc, None, report_paths)
                 report_fh.write(report_rows(ex, [rs.name(i) for i in range(R)], rs.lengths))
                 ex_blocks.append(ex)
+            if umi_groups is not None:
+                names_all.extend(rs.name(i).split(" ")[0] for i in range(R))
             if umi:
                 block_umis, umi_rows = _tag_umis(rs, sc, pl)
                 umis_all.extend(block_umis)
@@ -885,6 +942,11 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
             busy["scan"] += time.perf_counter() - t0
             to_write.put((rs, pr, ps_, pn_, num, piece_bins, read_bases))
             rs = loaded.get()
+        if umi_groups is not None and not failure:
+            try:
+                groups_all = _group_umis(umi_groups, umis_all, names_all, pl, group_by, umi_max_dist, umi_group_method, umi_group_max_keys)
+            except UsageError as e:                      # too many keys: like any failure part-way, nothing is left behind
+                failure.append(e)
     finally:
         stop.set()
         to_write.put(None)
@@ -908,10 +970,13 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
         res.explain = _concat_explain(ex_blocks)
     if umi:
         res.umis = umis_all
+    if umi_groups is not None:
+        res.umi_groups = groups_all
     if failure:
         # a streamed run that fails part-way (a later block that cannot be parsed, a full disk) has already written the
         # earlier blocks: a whole-file run would have written nothing, so nothing is left behind here either
-        for path in list(paths) + ([report] if report is not None else []) + ([umi_report] if umi_report is not None else []):
+        for path in list(paths) + ([report] if report is not None else []) + ([umi_report] if umi_report is not None else []) + (
+                [umi_groups] if umi_groups is not None else []):
             try:
                 if path and path != "-" and os.path.isfile(path):
                     os.remove(path)
@@ -1101,7 +1166,9 @@ def run_sharded(input_path, output, barcode_dir, opts: Options, device=None, ali
 
 def run(input_path, output=None, barcode_dir=None, options: Options = None, device=None, aligner=None,
         adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False,
-        report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False, umi_report: str = None) -> RunResult:
+        report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False, umi_report: str = None,
+        umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2, umi_group_method: str = "directional",
+        umi_group_max_keys: int = 1 << 20) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1129,6 +1196,17 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     base in the read, length, covered span rows, bases).  umi_report=PATH writes one TSV row per extracted UMI
     (UMI_REPORT_COLUMNS, a '#' header line), in input order, start before end.  Trims, calls and sequences are what they are
     without the option; off, so is every byte.  Not available in a sharded run.
+
+    umi_groups=PATH (with umi=True) says which reads come from one molecule (porechop_amd.umi_groups).  A
+    read's key is its UMI of the side umi_group_by names ("start", "end", or "both": START+END, for reads that have both;
+    None: "both" when the panel has degenerate letters on both sides, else the side that has them), upper-cased with U -> T.
+    The distinct keys are the nodes; two are a pair when their edit distance is <= umi_max_dist (Aligner.umi_neighbours: all
+    against all on the GPU); a key that is empty, above 64 bases or holds a letter outside A C G T has no pairs.
+    umi_group_method "directional": by count descending, then key, a node not yet grouped founds a group and takes what it
+    reaches over pairs with count(a) >= 2 count(b) - 1; "cluster": connected components.  PATH gets a '#' header line and one
+    row per read with a key, in input order (umi_groups.GROUP_COLUMNS); RunResult.umi_groups holds, per read, None or
+    (group, representative).  More linkable distinct keys than umi_group_max_keys are a UsageError, and then nothing is
+    written.  Headers are not tagged with the group: a streamed run has written its blocks before the last UMI is known.
 
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
@@ -1160,12 +1238,15 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         raise UsageError("Error: --umi_report needs --umi")
     if umi and sharded:
         raise UsageError("Error: UMI extraction is not available in a sharded run (one process per GPU): run it in a single process")
+    _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
+    group_kw = {} if umi_groups is None else dict(umi_groups=umi_groups, umi_group_by=umi_group_by, umi_max_dist=umi_max_dist,
+                                                  umi_group_method=umi_group_method, umi_group_max_keys=umi_group_max_keys)
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
                                 report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards,
-                                umi=umi, umi_report=umi_report)
+                                umi=umi, umi_report=umi_report, **group_kw)
         if streamed is not None:
             return streamed
 
@@ -1195,6 +1276,12 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
 
     try:
         panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
+        try:
+            group_by = _umi_group_by(pl, umi_group_by) if umi_groups is not None else None
+        except UsageError:
+            if aligner is None:
+                pl.close()
+            raise
     except UsageError:
         rs.close()
         raise
@@ -1238,6 +1325,10 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
                     fh.write(umi_report_header())
                     fh.write(umi_rows)
             lap("umi")
+        if umi_groups is not None:
+            res.umi_groups = _group_umis(umi_groups, res.umis, [rs.name(i).split(" ")[0] for i in range(R)], pl, group_by, umi_max_dist,
+                                         umi_group_method, umi_group_max_keys)
+            lap("umi_groups")
 
         # ---- which pieces of which reads -------------------------------------------------
         fmt, gz = _resolve_format(opts, output, barcode_dir, res.read_type, input_path)
