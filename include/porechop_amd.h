@@ -51,7 +51,8 @@ enum {
     PC_ERR_UNSUPPORTED_SCORES = -2, /* a score above 2^20 in magnitude, or sums that leave the 32-bit range */
     PC_ERR_BAD_ARG = -3,
     PC_ERR_ADAPTER_TOO_LONG = -4,   /* adapter longer than PC_MAX_ADAPTER_ANY */
-    PC_ERR_INTERNAL = -5            /* a kernel reported an inconsistency (never expected) */
+    PC_ERR_INTERNAL = -5,           /* a kernel reported an inconsistency (never expected) */
+    PC_ERR_OVER_BUDGET = -6         /* pc_consensus_round: one group alone needs more scratch than the budget allows */
 };
 
 #define PC_MAX_ADAPTER 128        /* the packed 16-bit kernels' limit; longer adapters take the plain-int32 kernel ... */
@@ -339,6 +340,38 @@ int pc_umi_span(pc_ctx *ctx, int adapter, int *first, int *last);
  *     them by the lower bound: the same pairs, for tests and measurements. */
 int pc_umi_neighbours(pc_ctx *ctx, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
                       int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream);
+
+/* UMI consensus, one round: every member of every group is aligned to its group's template, the alignments vote, the votes
+ * are called (csrc/pc_consensus.h states the rule, csrc/pc_consensus.hip the kernels).  Arrays named h_ are HOST memory, those
+ * named d_ device memory.
+ *   * Group g (0 <= g < n_groups) has the template d_tmpl_arena[h_tmpl_off[g] .. + h_tmpl_len[g]) and the members
+ *     h_group_first[g] .. h_group_first[g + 1] - 1 (h_group_first holds n_groups + 1 entries, from 0 up to n_members); member m
+ *     is d_arena[d_member_off[m] .. + d_member_len[m]) and d_member_group[m] names its group.  All offsets are 64-bit.
+ *   * Alignment: the banded global unit-cost edit distance of pc_consensus.h, 1 <= band <= 127.  Per member d_member_out[m] =
+ *     {status, distance}: 0 accepted, 1 rejected (distance * 100 > max_err_pct * max(lengths); the distance is 0x3fffffff when
+ *     no path stays inside the band), 2 invalid (distance -1).
+ *   * d_voters[g] = accepted members + tmpl_counts (1 when the template is itself a read of the group and stands for it, 0
+ *     when it is an earlier consensus).  The template votes for its own base in every column either way.
+ *   * d_cons: group g's consensus starts at byte sum over h < g of (5 min(h_tmpl_len[h], max_len) + 4) -- room for the longest
+ *     sequence the votes can give -- and d_cons_len[g] says how many bytes are valid.
+ *   * d_votes: NULL, or the counters of ALL groups, group g's 21 la + 16 counters (la = min(h_tmpl_len[g], max_len)) behind those
+ *     of the groups before it, in pc_consensus.h's layout: for tests and debugging.
+ *   * Slices.  The groups are taken in slices whose votes (4 bytes a counter) and trace (members x (longest template + 1) x 64
+ *     bytes) stay under 4096 MB (PC_CONSENSUS_SCRATCH_MB, read per call); a slice is never fewer than one group, and a group
+ *     that alone is above the budget is refused before anything is launched: PC_ERR_OVER_BUDGET, *refused_group (when not
+ *     NULL, else -1) names it.
+ *   * PC_ERR_BAD_ARG before anything is launched: band outside 1 .. 127, max_len outside 1 .. 2^24, max_err_pct outside 0 .. 100,
+ *     tmpl_counts outside 0 .. 1, a negative count, a template length < 1, a negative template offset, h_group_first not rising
+ *     from 0 to n_members.  n_groups == 0 or n_members == 0 does nothing at all.
+ *   * A template or member above max_len, a member naming a group other than the one h_group_first puts it in, or a walk that
+ *     leaves its band is counted in the context's error word and surfaces as PC_ERR_INTERNAL at pc_sync; such a member is
+ *     invalid and casts no vote, such a group's consensus is empty.  Nothing is read or written outside the arrays.
+ *   * The call waits for `stream` first (its scratch may still serve the call before), then enqueues and returns. */
+int pc_consensus_round(pc_ctx *ctx, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off, const int32_t *h_tmpl_len,
+                       const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off, const int32_t *d_member_len,
+                       const int32_t *d_member_group, int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts,
+                       uint8_t *d_cons, int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes,
+                       int64_t *refused_group, void *stream);
 
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read

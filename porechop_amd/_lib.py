@@ -30,7 +30,7 @@ EXPORTS = [
     "pc_set_wildcards", "pc_letter_set",
     "pc_scan_device_floored_flags", "pc_round_select", "pc_mask_rule_gate", "pc_mask_rule_must_realign",
     "pc_umi_extract", "pc_umi_span", "pc_readset_annotate",
-    "pc_umi_neighbours",
+    "pc_umi_neighbours", "pc_consensus_round",
 ]
 
 
@@ -114,6 +114,9 @@ def load_library():
     L.pc_umi_span.restype = c_int
     L.pc_umi_neighbours.argtypes = [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_i64, c_vp, c_vp]
     L.pc_umi_neighbours.restype = c_int
+    L.pc_consensus_round.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_int, c_int,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i64), c_vp]
+    L.pc_consensus_round.restype = c_int
     L.pc_sync.argtypes = [c_vp, c_vp]
     L.pc_sync.restype = c_int
     L.pc_copy_windows.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_int, c_vp]

@@ -429,6 +429,71 @@ class Aligner:
             pairs = pairs[order]
         return pairs.contiguous()
 
+    # ---- UMI consensus, one round (pc_consensus.hip, pc_consensus.h) ------------------------------------------------------
+    def consensus_round(self, arena, tmpl_off, tmpl_len, member_off, member_len, member_group, band, max_err_pct, max_len=65535,
+                        tmpl_counts=1, tmpl_arena=None, return_votes=False, stream=None):
+        """One round of the UMI consensus (pc_consensus_round): every member aligned to its group's template inside `band`, the
+        votes, the call.  arena: CUDA uint8 tensor holding the members (and the templates, unless tmpl_arena is given: another
+        CUDA uint8 tensor).  tmpl_off int64[G], tmpl_len int32[G], member_off int64[M], member_len int32[M], member_group
+        int32[M]: numpy arrays, the members ordered by group.  tmpl_counts: 1 when the template is a read of its group and
+        stands for it among the voters, 0 when it is an earlier consensus.
+        -> consensus.Round (numpy): cons the consensus bytes of all groups back to back, lens[G], status[M] (0 accepted, 1
+        rejected, 2 invalid), distance[M], voters[G], and votes (a list of uint32 arrays, 21 la + 16 counters per group) when
+        return_votes, else None.  Only the sequences, lengths and per-member words come back from the device.  The call syncs:
+        a length above max_len raises here.  A group that alone exceeds PC_CONSENSUS_SCRATCH_MB raises consensus.OverBudget
+        with its index; bad arguments raise before anything is launched."""
+        import torch
+        from . import consensus as pcc
+        assert arena.is_cuda and arena.dtype == torch.uint8 and arena.is_contiguous()
+        tmpl_arena = arena if tmpl_arena is None else tmpl_arena
+        assert tmpl_arena.is_cuda and tmpl_arena.dtype == torch.uint8 and tmpl_arena.is_contiguous()
+        tmpl_off = np.ascontiguousarray(tmpl_off, dtype=np.int64)
+        tmpl_len = np.ascontiguousarray(tmpl_len, dtype=np.int32)
+        member_off = np.ascontiguousarray(member_off, dtype=np.int64)
+        member_len = np.ascontiguousarray(member_len, dtype=np.int32)
+        member_group = np.ascontiguousarray(member_group, dtype=np.int32)
+        G, M = int(tmpl_len.shape[0]), int(member_len.shape[0])
+        assert tmpl_off.shape == (G,) and member_off.shape == (M,) and member_group.shape == (M,)
+        assert M == 0 or (np.all(np.diff(member_group) >= 0) and 0 <= int(member_group[0]) and int(member_group[-1]) < G), "members go in ordered by group"
+        first = np.ascontiguousarray(np.searchsorted(member_group, np.arange(G + 1)), dtype=np.int64)
+        la = np.clip(tmpl_len.astype(np.int64), 0, max(int(max_len), 0))
+        cons_off = np.concatenate([[0], np.cumsum(pcc.cons_capacity(la))]).astype(np.int64)
+        vote_off = np.concatenate([[0], np.cumsum(pcc.votes_per_group(la))]).astype(np.int64)
+        dev = arena.device
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        cons = torch.empty(int(cons_off[-1]) + 16, dtype=torch.uint8, device=dev)
+        lens = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
+        voters = torch.zeros(max(G, 1), dtype=torch.int32, device=dev)
+        out = torch.zeros((max(M, 1), 2), dtype=torch.int32, device=dev)
+        votes = torch.zeros(int(vote_off[-1]) + 16, dtype=torch.int32, device=dev) if return_votes else None
+        d_off, d_len, d_grp = (torch.from_numpy(x).to(dev) if M else torch.zeros(1, dtype=torch.from_numpy(x).dtype, device=dev)
+                               for x in (member_off, member_len, member_group))
+        refused = ctypes.c_int64(-1)
+        rc = self.lib.pc_consensus_round(self._ctx, arena.data_ptr(), tmpl_arena.data_ptr(), tmpl_off.ctypes.data, tmpl_len.ctypes.data,
+                                         first.ctypes.data, G, d_off.data_ptr(), d_len.data_ptr(), d_grp.data_ptr(), M, int(band),
+                                         int(max_err_pct), int(max_len), int(tmpl_counts), cons.data_ptr(), lens.data_ptr(),
+                                         voters.data_ptr(), out.data_ptr(), votes.data_ptr() if votes is not None else None,
+                                         ctypes.byref(refused), ctypes.c_void_p(s))
+        if rc == -6:
+            raise pcc.OverBudget(int(refused.value))
+        check(rc, "pc_consensus_round")
+        self.sync(s)
+        h_lens = lens[:G].cpu().numpy()
+        total = int(h_lens.sum())
+        if total:
+            d_lens = lens[:G].to(torch.int64)
+            starts = torch.from_numpy(cons_off[:G]).to(dev) - (torch.cumsum(d_lens, 0) - d_lens)
+            at = torch.repeat_interleave(starts, d_lens) + torch.arange(total, dtype=torch.int64, device=dev)
+            h_cons = cons[at].cpu().numpy()
+        else:
+            h_cons = np.zeros(0, dtype=np.uint8)
+        h_out = out[:M].cpu().numpy()
+        h_votes = None
+        if votes is not None:
+            flat = votes.cpu().numpy().view(np.uint32)
+            h_votes = [flat[vote_off[g]:vote_off[g + 1]].copy() for g in range(G)]
+        return pcc.Round(h_cons, h_lens, h_out[:, 0].copy(), h_out[:, 1].copy(), voters[:G].cpu().numpy(), h_votes)
+
     # ---- paths of middle hits (pc_paths.hip) ----------------------------------------------------------------------------
     def middle_paths_cols(self, max_len):
         """The widest window (columns) a hit of middle_paths can have over reads of up to max_len bases

@@ -26,6 +26,7 @@
 #include "pc_paths.h"
 #include "pc_umi.h"
 #include "pc_umi_dist.h"
+#include "pc_consensus.h"
 #include "pc_middle_paths.h"
 #include "pc_jit.h"
 #include "pc_kernels.h"
@@ -102,6 +103,8 @@ struct pc_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // host-API staging
     DevBuf d_arena, d_woff, d_wlen, d_out;
+    // pc_consensus_round: a slice's trace and votes, the call's per-group tables
+    DevBuf d_cons_trace, d_cons_votes, d_cons_meta;
     // pc_phase_b_reduce: job / bin tables in two slots (pinned host staging + device copy each); a slot is reused
     // once the reduce kernel that read it two calls ago has finished (red_done), so a call never waits for the
     // scan it was enqueued behind
@@ -855,6 +858,7 @@ const char *pc_strerror(int code)
         case PC_ERR_BAD_ARG: return "bad argument";
         case PC_ERR_ADAPTER_TOO_LONG: return "adapter longer than PC_MAX_ADAPTER_ANY (or its trace too large)";
         case PC_ERR_INTERNAL: return "kernel reported an internal inconsistency";
+        case PC_ERR_OVER_BUDGET: return "one consensus group alone needs more scratch than PC_CONSENSUS_SCRATCH_MB allows";
         default: return "unknown error";
     }
 }
@@ -915,7 +919,8 @@ void pc_destroy(pc_ctx *c)
                       &c->d_wlen2, &c->d_col0, &c->d_ntot, &c->d_frow, &c->d_fscore, &c->d_tcols, &c->d_perm, &c->d_bucket_cnt, &c->d_bucket_slot[0], &c->d_bucket_slot[1], &c->d_err, &c->d_arena,
                       &c->d_woff, &c->d_wlen, &c->d_out, &c->d_red_slot[0], &c->d_red_slot[1], &c->d_work, &c->d_units, &c->d_pf_tables, &c->d_pf_meta, &c->d_sd_bitmaps, &c->d_sd_first,
                       &c->d_sd_entries, &c->d_sd_meta, &c->d_sd_eq, &c->d_sd_cand, &c->d_sd_count, &c->d_slow_ad, &c->d_slow_state,
-                      &c->d_slow_trace, &c->d_paths_trace, &c->d_middle_paths_trace, &c->d_umi_ops};
+                      &c->d_slow_trace, &c->d_paths_trace, &c->d_middle_paths_trace, &c->d_umi_ops, &c->d_cons_trace, &c->d_cons_votes,
+                      &c->d_cons_meta};
     if (c->h_sd_count) (void)hipHostFree(c->h_sd_count);
     c->h_table_slot[0].release(); c->h_table_slot[1].release();
     for (DevBuf *b : bufs) b->release();
@@ -1260,6 +1265,97 @@ int pc_umi_neighbours(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len,
     a.pairs = d_pairs; a.cap = cap; a.found = (unsigned long long *)d_found;
     a.err = c->d_err.as<uint32_t>();
     if (pck::launch_umi_neighbours(a, stream)) return PC_ERR_NO_DEVICE;
+    return PC_OK;
+}
+
+// votes and trace one slice of pc_consensus_round may take, unless PC_CONSENSUS_SCRATCH_MB says otherwise
+static constexpr size_t kConsensusScratchMB = 4096;
+
+int pc_consensus_round(pc_ctx *c, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off, const int32_t *h_tmpl_len,
+                       const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off, const int32_t *d_member_len,
+                       const int32_t *d_member_group, int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts,
+                       uint8_t *d_cons, int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes,
+                       int64_t *refused_group, void *stream_v)
+{
+    if (refused_group) *refused_group = -1;
+    if (!c || n_groups < 0 || n_members < 0 || n_groups > (int64_t)INT32_MAX || n_members > (int64_t)INT32_MAX) return PC_ERR_BAD_ARG;
+    if (band < 1 || band > pcc::MAX_BAND || max_len < 1 || max_len > pcc::MAX_LEN_LIMIT) return PC_ERR_BAD_ARG;
+    if (max_err_pct < 0 || max_err_pct > 100 || tmpl_counts < 0 || tmpl_counts > 1) return PC_ERR_BAD_ARG;
+    if (n_groups == 0 || n_members == 0) return PC_OK;
+    if (!d_arena || !d_tmpl_arena || !h_tmpl_off || !h_tmpl_len || !h_group_first || !d_member_off || !d_member_len || !d_member_group ||
+        !d_cons || !d_cons_len || !d_voters || !d_member_out)
+        return PC_ERR_BAD_ARG;
+    if (h_group_first[0] != 0 || h_group_first[n_groups] != n_members) return PC_ERR_BAD_ARG;
+    for (int64_t g = 0; g < n_groups; ++g)
+        if (h_tmpl_len[g] < 1 || h_tmpl_off[g] < 0 || h_group_first[g + 1] < h_group_first[g]) return PC_ERR_BAD_ARG;
+
+    // the per-group tables: a template above max_len is the kernels' to report, and is sized as max_len here
+    std::vector<int64_t> meta((size_t)n_groups * 3 + ((size_t)n_groups + 1) / 2);
+    int64_t *vote_off = meta.data() + n_groups, *cons_off = meta.data() + 2 * n_groups;
+    int32_t *tmpl_len = (int32_t *)(meta.data() + 3 * n_groups);
+    int64_t votes_at = 0, cons_at = 0;
+    for (int64_t g = 0; g < n_groups; ++g) {
+        const int64_t la = std::min(h_tmpl_len[g], max_len);
+        meta[(size_t)g] = h_tmpl_off[g];
+        vote_off[g] = votes_at; cons_off[g] = cons_at; tmpl_len[g] = h_tmpl_len[g];
+        votes_at += pcc::votes_per_group(la);
+        cons_at += pcc::cons_capacity(la);
+    }
+    // slices of whole groups whose votes and trace fit the budget; never fewer than one group
+    size_t budget = kConsensusScratchMB << 20;
+    if (const char *e = getenv("PC_CONSENSUS_SCRATCH_MB")) { if (atol(e) > 0) budget = (size_t)atol(e) << 20; }
+    struct Slice { int64_t g0, g1, rows; size_t votes, trace; };
+    std::vector<Slice> slices;
+    for (int64_t g0 = 0; g0 < n_groups;) {
+        Slice s{g0, g0, 0, 0, 0};
+        while (s.g1 < n_groups) {
+            const int64_t la = std::min(h_tmpl_len[s.g1], max_len);
+            const int64_t rows = std::max(s.rows, la + 1), members = h_group_first[s.g1 + 1] - h_group_first[g0];
+            const size_t votes = s.votes + (size_t)pcc::votes_per_group(la) * 4;
+            const size_t trace = (size_t)members * (size_t)rows * pcc::TRACE_ROW_BYTES;
+            if (votes + trace > budget) break;
+            s.g1 += 1; s.rows = rows; s.votes = votes; s.trace = trace;
+        }
+        if (s.g1 == g0) {                                           // this group alone is above the budget
+            if (refused_group) *refused_group = g0;
+            return PC_ERR_OVER_BUDGET;
+        }
+        slices.push_back(s);
+        g0 = s.g1;
+    }
+    size_t votes_max = 0, trace_max = 0;
+    for (const Slice &s : slices) { votes_max = std::max(votes_max, s.votes); trace_max = std::max(trace_max, s.trace); }
+
+    (void)hipSetDevice(c->device);
+    hipStream_t stream = (stream_v == PC_STREAM_CONTEXT) ? c->stream : (hipStream_t)stream_v;
+    HIP_TRY(hipStreamSynchronize(stream));                           // the buffers below may still serve the call before this one
+    int rc;
+    if ((rc = c->d_cons_meta.ensure(meta.size() * 8))) return rc;
+    if ((rc = c->d_cons_trace.ensure(trace_max + 256))) return rc;
+    if (!d_votes && (rc = c->d_cons_votes.ensure(votes_max + 256))) return rc;
+    HIP_TRY(hipMemcpy(c->d_cons_meta.p, meta.data(), meta.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d_voters, 0, (size_t)n_groups * 4, stream));
+
+    pck::ConsensusArgs a{};
+    a.arena = (const uint8_t *)d_arena; a.tmpl_arena = (const uint8_t *)d_tmpl_arena;
+    a.tmpl_off = c->d_cons_meta.as<int64_t>(); a.vote_off = a.tmpl_off + n_groups; a.cons_off = a.tmpl_off + 2 * n_groups;
+    a.tmpl_len = (const int32_t *)(a.tmpl_off + 3 * n_groups);
+    a.member_off = d_member_off; a.member_len = d_member_len; a.member_group = d_member_group;
+    a.n_groups_all = n_groups;
+    a.trace = c->d_cons_trace.as<uint8_t>();
+    a.band = band; a.max_err_pct = max_err_pct; a.max_len = max_len; a.tmpl_counts = tmpl_counts;
+    a.member_out = d_member_out; a.voters = d_voters; a.cons = d_cons; a.cons_len = d_cons_len;
+    a.err = c->d_err.as<uint32_t>();
+    for (const Slice &s : slices) {
+        a.first_group = s.g0; a.n_groups = s.g1 - s.g0;
+        a.first_member = h_group_first[s.g0]; a.n_members = h_group_first[s.g1] - h_group_first[s.g0];
+        a.rows = s.rows;
+        if (d_votes) { a.votes = d_votes; a.vote_base = 0; }
+        else { a.votes = c->d_cons_votes.as<uint32_t>(); a.vote_base = vote_off[s.g0]; }
+        HIP_TRY(hipMemsetAsync(a.votes + (vote_off[s.g0] - a.vote_base), 0, s.votes, stream));
+        if (pck::launch_consensus_pileup(a, stream)) return PC_ERR_NO_DEVICE;
+        if (pck::launch_consensus_call(a, stream)) return PC_ERR_NO_DEVICE;
+    }
     return PC_OK;
 }
 

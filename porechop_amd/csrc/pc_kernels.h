@@ -481,4 +481,33 @@ struct UmiNeighboursArgs {
 };
 int launch_umi_neighbours(const UmiNeighboursArgs &a, void *stream);
 
+// consensus_pileup_kernel / consensus_call_kernel (pc_consensus.hip): one round of the UMI consensus over a slice of groups
+// (pc_consensus.h).  Group arrays are indexed by the group's number in the call, member arrays by the member's.
+struct ConsensusArgs {
+    const uint8_t *arena;        // the members' bytes
+    const uint8_t *tmpl_arena;   // the templates' bytes
+    const int64_t *tmpl_off;     // [groups]
+    const int32_t *tmpl_len;     // [groups]
+    const int64_t *vote_off;     // [groups] first counter of the group in the call's numbering
+    const int64_t *cons_off;     // [groups] first consensus byte of the group
+    const int64_t *member_off;   // [members]
+    const int32_t *member_len;   // [members]
+    const int32_t *member_group; // [members]
+    int64_t first_member, n_members;     // the slice
+    int64_t first_group, n_groups;
+    int64_t n_groups_all;
+    uint32_t *votes;             // counter vote_off[g] - vote_base + ... of the slice
+    int64_t vote_base;
+    uint8_t *trace;              // [slice member][rows][64]
+    int64_t rows;                // longest template of the slice + 1
+    int32_t band, max_err_pct, max_len, tmpl_counts;
+    int32_t *member_out;         // [members][2] {status, distance}
+    int32_t *voters;             // [groups]
+    uint8_t *cons;
+    int32_t *cons_len;           // [groups]
+    uint32_t *err;
+};
+int launch_consensus_pileup(const ConsensusArgs &a, void *stream);
+int launch_consensus_call(const ConsensusArgs &a, void *stream);
+
 }  // namespace pck

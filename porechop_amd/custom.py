@@ -14,7 +14,13 @@ command line of `python -m porechop_amd` (the reference's option set, unchanged 
                      key, the reads of the key and of the group, the group's representative.  The
                      distinct keys are compared all against all on the GPU by edit distance;
                      --umi_group_by start|end|both (default: both when both adapters carry a UMI), --umi_max_dist N (2),
-                     --umi_group_method directional|cluster, --umi_group_max_keys N (refuse more distinct keys than N).
+                     --umi_group_method directional|cluster, --umi_group_max_keys N (refuse more distinct keys than N);
+  --umi_consensus PATH  (with --umi) one consensus sequence per group of reads, as FASTA: the members of a
+                     group are aligned to its median-length member inside a band on the GPU, vote per column, and the call is
+                     the next round's template.  --umi_consensus_report PATH (a TSV row per group), --umi_consensus_min_reads N
+                     (3), --umi_consensus_max_reads N (256), --umi_consensus_band N (64), --umi_consensus_rounds N (2),
+                     --umi_consensus_max_err_pct N (30), --umi_consensus_max_len N (65535).  The reads stay resident: the input
+                     is not streamed.
 It composes with the explain report: --report PATH, --report_paths, --report_middle_paths (porechop_amd.explain)."""
 import sys
 
@@ -35,6 +41,14 @@ def build_custom_parser(prog="porechop_amd.custom"):
     p.add_argument("--umi_group_method", choices=["directional", "cluster"], default="directional",
                    help="directional: a key joins a neighbour with at least 2n-1 of its n reads; cluster: connected components")
     p.add_argument("--umi_group_max_keys", type=int, default=1 << 20, help="refuse to compare more distinct keys than this (default: 1048576)")
+    p.add_argument("--umi_consensus", metavar="PATH", help="one consensus sequence per UMI group, FASTA (needs --umi)")
+    p.add_argument("--umi_consensus_report", metavar="PATH", help="one TSV row per UMI group: members, used, rejected, skipped, rounds, length, status")
+    p.add_argument("--umi_consensus_min_reads", type=int, default=3, help="groups with fewer members get no sequence (default: 3)")
+    p.add_argument("--umi_consensus_max_reads", type=int, default=256, help="only a group's first N members take part (default: 256)")
+    p.add_argument("--umi_consensus_band", type=int, default=64, help="half width of the alignment band around the stretched diagonal, 1..127 (default: 64)")
+    p.add_argument("--umi_consensus_rounds", type=int, default=2, help="rounds: a round's consensus is the next one's template (default: 2)")
+    p.add_argument("--umi_consensus_max_err_pct", type=int, default=30, help="a member further than this from the template sits the round out (default: 30)")
+    p.add_argument("--umi_consensus_max_len", type=int, default=65535, help="groups whose template is longer get no sequence (default: 65535)")
     p.add_argument("--report", help="per-read explain report (TSV), written in input order")
     p.add_argument("--report_paths", action="store_true", help="append start_cigars / end_cigars to the report")
     p.add_argument("--report_middle_paths", action="store_true", help="append middle_cigars to the report")
@@ -79,6 +93,13 @@ def main(argv=None):
     if a.umi_groups is not None:
         kw.update(umi=a.umi, umi_groups=a.umi_groups, umi_group_by=a.umi_group_by, umi_max_dist=a.umi_max_dist,
                   umi_group_method=a.umi_group_method, umi_group_max_keys=a.umi_group_max_keys)
+    if a.umi_consensus is not None or a.umi_consensus_report is not None:
+        kw.update(umi=a.umi, umi_consensus=a.umi_consensus, umi_consensus_report=a.umi_consensus_report,
+                  umi_group_by=a.umi_group_by, umi_max_dist=a.umi_max_dist, umi_group_method=a.umi_group_method,
+                  umi_group_max_keys=a.umi_group_max_keys, umi_consensus_min_reads=a.umi_consensus_min_reads,
+                  umi_consensus_max_reads=a.umi_consensus_max_reads, umi_consensus_band=a.umi_consensus_band,
+                  umi_consensus_rounds=a.umi_consensus_rounds, umi_consensus_max_err_pct=a.umi_consensus_max_err_pct,
+                  umi_consensus_max_len=a.umi_consensus_max_len)
     run_cli(a, adapter_panel=panel, wildcards=a.wildcards, **kw)
 
 

@@ -79,6 +79,9 @@ class RunResult:
     umis: Optional[List[tuple]] = None
     # run(..., umi_groups=PATH): per read None (no key) or (group id from 1, the group's representative key)
     umi_groups: Optional[List[Optional[tuple]]] = None
+    # run(..., umi_consensus=PATH): one dict per group, in group order (porechop_amd.consensus.call_groups): group,
+    # representative, members, used, rejected, skipped, rounds, length, status, sequence (bytes; None unless status is "called")
+    consensus: Optional[List[dict]] = None
 
 
 @dataclass
@@ -438,10 +441,59 @@ def _group_umis(path, umis, names, pl, by, max_dist, method, max_keys):
     except OverflowError as e:
         raise UsageError("Error: %s distinct UMI keys are more than --umi_group_max_keys %d allows: the all-against-all pass grows "
                          "with the square of their number; raise --umi_group_max_keys to run it all the same" % (e.args[0], int(max_keys)))
-    with open(path, "w") as fh:
-        fh.write(ug.groups_header())
-        fh.write(rows)
+    if path is not None:                                        # run(umi_consensus=PATH) alone makes the groups and writes no TSV
+        with open(path, "w") as fh:
+            fh.write(ug.groups_header())
+            fh.write(rows)
     return per_read
+
+
+CONSENSUS_OPTIONS = ("min_reads", "max_reads", "band", "rounds", "max_err_pct", "max_len")
+
+
+def _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, values):
+    """The refusals of run(umi_consensus=PATH) that need no panel; values: the six numeric options in CONSENSUS_OPTIONS' order."""
+    from . import consensus as cs
+    if umi_consensus_report is not None and umi_consensus is None:
+        raise UsageError("Error: --umi_consensus_report needs --umi_consensus")
+    if umi_consensus is None:
+        return
+    if not umi:
+        raise UsageError("Error: --umi_consensus needs --umi")
+    if sharded:
+        raise UsageError("Error: the UMI consensus is not available in a sharded run (one process per GPU): run it in a single process")
+    try:
+        bad = cs.check_options(*[int(v) for v in values])
+    except (TypeError, ValueError):
+        bad = ("band", "and the other numeric options must be whole numbers")
+    if bad:
+        raise UsageError("Error: --umi_consensus_%s %s" % bad)
+
+
+def _consensus(fasta, report, res, rs, reads, pr, num, pl, values):
+    """run(umi_consensus=PATH) after the piece plan: the groups' members (reads written as exactly one piece), the rounds over
+    the arena _upload made -- on the library when the aligner has consensus_round, in numpy otherwise -- and the two files ->
+    RunResult.consensus."""
+    from . import consensus as cs
+    lengths = np.asarray(rs.lengths, dtype=np.int64)
+    groups = cs.members(res.umi_groups, lengths, res.start_trim, res.end_trim, pr, num)
+    seq_off = np.asarray(rs.offsets, dtype=np.int64) + np.asarray(res.start_trim, dtype=np.int64)
+    seq_len = np.maximum(lengths - np.asarray(res.end_trim, dtype=np.int64) - np.asarray(res.start_trim, dtype=np.int64), 0)
+    written = []
+    try:
+        out = cs.call_groups(groups, rs.arena, seq_off, seq_len, *[int(v) for v in values], aligner=pl.aligner,
+                             dev_arena=reads.arena if reads is not None else None, device=pl.device)
+        for path, text in ((fasta, cs.fasta_text(out)), (report, cs.report_text(out))):
+            if path is not None:
+                written.append(path)
+                with open(path, "w") as fh:
+                    fh.write(text)
+    except Exception:
+        for path in written:
+            if os.path.isfile(path):
+                os.remove(path)
+        raise
+    return out
 
 
 def _upload(rs, dev, lo=0, hi=None):
@@ -747,7 +799,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
                  report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False,
                  umi_report: str = None, umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2,
-                 umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20) -> Optional[RunResult]:
+                 umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20, umi_consensus: str = None) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -762,6 +814,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     without the check reads): the caller loads the whole file."""
     import queue
     import threading
+    if umi_consensus is not None:
+        raise UsageError("Error: --umi_consensus is not available in a streamed run: the reads must stay resident; use run()")
     _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
     block_bytes = block_bytes or _stream_block_bytes()
     size = os.path.getsize(input_path)
@@ -1168,7 +1222,9 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         adapter_panel: List[AdapterSet] = None, report: str = None, report_paths: bool = False,
         report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False, umi_report: str = None,
         umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2, umi_group_method: str = "directional",
-        umi_group_max_keys: int = 1 << 20) -> RunResult:
+        umi_group_max_keys: int = 1 << 20, umi_consensus: str = None, umi_consensus_report: str = None,
+        umi_consensus_min_reads: int = 3, umi_consensus_max_reads: int = 256, umi_consensus_band: int = 64, umi_consensus_rounds: int = 2,
+        umi_consensus_max_err_pct: int = 30, umi_consensus_max_len: int = 65535) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1208,6 +1264,19 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     (group, representative).  More linkable distinct keys than umi_group_max_keys are a UsageError, and then nothing is
     written.  Headers are not tagged with the group: a streamed run has written its blocks before the last UMI is known.
 
+    umi_consensus=PATH (with umi=True) writes ONE CONSENSUS SEQUENCE PER GROUP of reads (porechop_amd.consensus; DESIGN.md section
+    18).  The groups are made with the grouping options above whether or not umi_groups=PATH is given (the groups TSV is written
+    only when it is).  A group's members are its reads that are written as exactly one piece with at least one base left, as
+    their trimmed sequences; a group of at least umi_consensus_min_reads members is called from its first umi_consensus_max_reads
+    members: the lower-median member is the template, every other member is aligned to it inside umi_consensus_band (a member
+    more than umi_consensus_max_err_pct percent away sits the round out), the alignments vote per column and insertion slot,
+    and the call is the template of the next of umi_consensus_rounds rounds.  PATH gets a FASTA record per called group
+    (">umi_group_<id> key=<representative> reads=<members> used=<accepted in the last round> rounds=<r> length=<L>"),
+    umi_consensus_report=PATH a TSV with one row per group (consensus.REPORT_COLUMNS, a '#' header line) that says why a group
+    has no sequence; RunResult.consensus holds both.  The rounds run over the arena already on the device (Aligner.
+    consensus_round), so with umi_consensus given run() takes this plain driver whatever the input's size: the reads must be
+    resident.  Not available in run_streamed or in a sharded run.  Off, every byte and every launch is what it was.
+
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
     file of sized members and a `cat` of gzip members take run_sharded: every rank parses, scans and WRITES only its own
@@ -1239,11 +1308,17 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     if umi and sharded:
         raise UsageError("Error: UMI extraction is not available in a sharded run (one process per GPU): run it in a single process")
     _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
+    consensus_values = (umi_consensus_min_reads, umi_consensus_max_reads, umi_consensus_band, umi_consensus_rounds, umi_consensus_max_err_pct,
+                        umi_consensus_max_len)
+    _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, consensus_values)
+    if umi_consensus is not None and umi_groups is None:         # the groups are made all the same; only the TSV is not written
+        _check_umi_group_options(umi, "", umi_group_by, umi_max_dist, umi_group_method)
+    grouping = umi_groups is not None or umi_consensus is not None
     group_kw = {} if umi_groups is None else dict(umi_groups=umi_groups, umi_group_by=umi_group_by, umi_max_dist=umi_max_dist,
                                                   umi_group_method=umi_group_method, umi_group_max_keys=umi_group_max_keys)
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
-            and not sharded):
+            and not sharded and umi_consensus is None):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
                                 report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards,
                                 umi=umi, umi_report=umi_report, **group_kw)
@@ -1277,7 +1352,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     try:
         panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
         try:
-            group_by = _umi_group_by(pl, umi_group_by) if umi_groups is not None else None
+            group_by = _umi_group_by(pl, umi_group_by) if grouping else None
         except UsageError:
             if aligner is None:
                 pl.close()
@@ -1325,7 +1400,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
                     fh.write(umi_report_header())
                     fh.write(umi_rows)
             lap("umi")
-        if umi_groups is not None:
+        if grouping:
             res.umi_groups = _group_umis(umi_groups, res.umis, [rs.name(i).split(" ")[0] for i in range(R)], pl, group_by, umi_max_dist,
                                          umi_group_method, umi_group_max_keys)
             lap("umi_groups")
@@ -1335,6 +1410,16 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         res.out_format = fmt
         pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
         res.middle_hit_reads = n_split
+        if umi_consensus is not None:
+            lap("plan_output")
+            try:
+                res.consensus = _consensus(umi_consensus, umi_consensus_report, res, rs, reads, pr, num, pl, consensus_values)
+            except Exception:                                    # nothing of this run is left behind
+                for path in (umi_report, umi_groups, report):
+                    if path is not None and os.path.isfile(path):
+                        os.remove(path)
+                raise
+            lap("umi_consensus")
 
         lap("plan_output")
         # ---- write -------------------------------------------------------------------------
