@@ -341,6 +341,16 @@ int pc_umi_span(pc_ctx *ctx, int adapter, int *first, int *last);
 int pc_umi_neighbours(pc_ctx *ctx, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
                       int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream);
 
+/* UMI neighbours over BOTH STRANDS of a molecule: pc_umi_neighbours' contract -- the same arguments, checks, counter, cap and
+ * PC_UMI_NO_PRUNE -- except that a pair is FOUR int32, d_pairs[slot] = {i, j, d, flip} (d_pairs holds 4 * cap of them):
+ *   * mirror(key) is the key of the reverse complement: base t of it is 3 - base(len - 1 - t) (csrc/pc_umi_dist.h).  A read of
+ *     the other strand of a molecule shows the key START+END as rc(END)+rc(START) = mirror(START+END).
+ *   * d = min(d_same, d_mirror) with d_same the edit distance of key i and key j and d_mirror that of key i and mirror(key j)
+ *     (= that of mirror(key i) and key j); flip = 1 iff d_mirror < d_same, a tie gives 0.  The pair i < j is reported once iff
+ *     d <= max_dist, and d and flip are exact whenever it is.  A key is never paired with itself. */
+int pc_umi_neighbours_stranded(pc_ctx *ctx, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                               int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream);
+
 /* UMI consensus, one round: every member of every group is aligned to its group's template, the alignments vote, the votes
  * are called (csrc/pc_consensus.h states the rule, csrc/pc_consensus.hip the kernels).  Arrays named h_ are HOST memory, those
  * named d_ device memory.
@@ -372,6 +382,19 @@ int pc_consensus_round(pc_ctx *ctx, const void *d_arena, const void *d_tmpl_aren
                        const int32_t *d_member_group, int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts,
                        uint8_t *d_cons, int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes,
                        int64_t *refused_group, void *stream);
+
+/* pc_consensus_round with a strand per member: d_member_strand[m] (device memory, n_members bytes) != 0 reads member m as its
+ * REVERSE COMPLEMENT -- its base j is the complement of d_arena[d_member_off[m] + d_member_len[m] - 1 - j]: A <-> T, C <-> G, U
+ * as T, any other byte stays a byte that matches nothing and casts no vote.  The member's bytes are not changed; alignment,
+ * votes and call are those of the materialised reverse complement, in the template's coordinates.  Templates are never
+ * flipped: a caller that wants a consensus in the other orientation reverse-complements it on the host.  d_member_strand NULL
+ * means all 0, and that call IS pc_consensus_round: the same kernels, the same bytes.  Everything else as above. */
+int pc_consensus_round_stranded(pc_ctx *ctx, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off,
+                                const int32_t *h_tmpl_len, const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off,
+                                const int32_t *d_member_len, const int32_t *d_member_group, const uint8_t *d_member_strand,
+                                int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts, uint8_t *d_cons,
+                                int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
+                                void *stream);
 
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read

@@ -399,12 +399,15 @@ class Aligner:
         return records, umi
 
     # ---- UMI neighbours (pc_umi_groups.hip umi_neighbours_kernel, pc_umi_dist.h) -----------------------------------------
-    def umi_neighbours(self, planes, lens, max_dist, cap=None, stream=None):
+    def umi_neighbours(self, planes, lens, max_dist, cap=None, stream=None, strands=False):
         """Every pair i < j of n UMI keys whose edit distance is <= max_dist (pc_umi_neighbours).  planes int64[n, 2] (the bit
         planes p0, p1 of umi_groups.pack), lens int32[n]: CUDA tensors.  -> int32[m, 3] CUDA tensor {i, j, distance} of ALL
         such pairs, sorted by (i, j).  The list handed on is never incomplete: `found` is read after a sync, and when it is
         above cap (default: max(4 n, 1024)) the call is made again with cap = found -- a truncated list taken as proof of "no
-        neighbour" would be wrong grouping.  max_len comes from lens.max().  A length outside 0..64 raises at the sync."""
+        neighbour" would be wrong grouping.  max_len comes from lens.max().  A length outside 0..64 raises at the sync.
+        strands=True (pc_umi_neighbours_stranded): -> int32[m, 4] {i, j, d, flip}, d the smaller of the distance as the keys stand
+        and the distance with key j mirrored (umi_groups.mirror_key: the molecule's other strand), flip 1 iff the mirrored one
+        is the smaller; the same retry."""
         import torch
         assert planes.is_cuda and lens.is_cuda and planes.dtype == torch.int64 and lens.dtype == torch.int32
         assert planes.is_contiguous() and lens.is_contiguous()
@@ -414,10 +417,12 @@ class Aligner:
         cap = max(4 * n, 1024) if cap is None else int(cap)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         found = torch.zeros(1, dtype=torch.int64, device=lens.device)
+        entry, name, width = ((self.lib.pc_umi_neighbours_stranded, "pc_umi_neighbours_stranded", 4) if strands else
+                              (self.lib.pc_umi_neighbours, "pc_umi_neighbours", 3))
         while True:
-            pairs = torch.empty((cap, 3), dtype=torch.int32, device=lens.device)
-            check(self.lib.pc_umi_neighbours(self._ctx, planes.data_ptr(), lens.data_ptr(), n, max_len, int(max_dist), pairs.data_ptr(),
-                                             cap, found.data_ptr(), ctypes.c_void_p(s)), "pc_umi_neighbours")
+            pairs = torch.empty((cap, width), dtype=torch.int32, device=lens.device)
+            check(entry(self._ctx, planes.data_ptr(), lens.data_ptr(), n, max_len, int(max_dist), pairs.data_ptr(), cap, found.data_ptr(),
+                        ctypes.c_void_p(s)), name)
             self.sync(s)
             m = int(found.item())
             if m <= cap:
@@ -431,12 +436,13 @@ class Aligner:
 
     # ---- UMI consensus, one round (pc_consensus.hip, pc_consensus.h) ------------------------------------------------------
     def consensus_round(self, arena, tmpl_off, tmpl_len, member_off, member_len, member_group, band, max_err_pct, max_len=65535,
-                        tmpl_counts=1, tmpl_arena=None, return_votes=False, stream=None):
+                        tmpl_counts=1, tmpl_arena=None, return_votes=False, stream=None, member_strand=None):
         """One round of the UMI consensus (pc_consensus_round): every member aligned to its group's template inside `band`, the
         votes, the call.  arena: CUDA uint8 tensor holding the members (and the templates, unless tmpl_arena is given: another
         CUDA uint8 tensor).  tmpl_off int64[G], tmpl_len int32[G], member_off int64[M], member_len int32[M], member_group
         int32[M]: numpy arrays, the members ordered by group.  tmpl_counts: 1 when the template is a read of its group and
-        stands for it among the voters, 0 when it is an earlier consensus.
+        stands for it among the voters, 0 when it is an earlier consensus.  member_strand: None, or uint8[M] (numpy) -- a member
+        whose strand is 1 is read as its reverse complement (pc_consensus_round_stranded); None is pc_consensus_round itself.
         -> consensus.Round (numpy): cons the consensus bytes of all groups back to back, lens[G], status[M] (0 accepted, 1
         rejected, 2 invalid), distance[M], voters[G], and votes (a list of uint32 arrays, 21 la + 16 counters per group) when
         return_votes, else None.  Only the sequences, lengths and per-member words come back from the device.  The call syncs:
@@ -469,11 +475,17 @@ class Aligner:
         d_off, d_len, d_grp = (torch.from_numpy(x).to(dev) if M else torch.zeros(1, dtype=torch.from_numpy(x).dtype, device=dev)
                                for x in (member_off, member_len, member_group))
         refused = ctypes.c_int64(-1)
-        rc = self.lib.pc_consensus_round(self._ctx, arena.data_ptr(), tmpl_arena.data_ptr(), tmpl_off.ctypes.data, tmpl_len.ctypes.data,
-                                         first.ctypes.data, G, d_off.data_ptr(), d_len.data_ptr(), d_grp.data_ptr(), M, int(band),
-                                         int(max_err_pct), int(max_len), int(tmpl_counts), cons.data_ptr(), lens.data_ptr(),
-                                         voters.data_ptr(), out.data_ptr(), votes.data_ptr() if votes is not None else None,
-                                         ctypes.byref(refused), ctypes.c_void_p(s))
+        head = (self._ctx, arena.data_ptr(), tmpl_arena.data_ptr(), tmpl_off.ctypes.data, tmpl_len.ctypes.data, first.ctypes.data, G,
+                d_off.data_ptr(), d_len.data_ptr(), d_grp.data_ptr())
+        tail = (M, int(band), int(max_err_pct), int(max_len), int(tmpl_counts), cons.data_ptr(), lens.data_ptr(), voters.data_ptr(),
+                out.data_ptr(), votes.data_ptr() if votes is not None else None, ctypes.byref(refused), ctypes.c_void_p(s))
+        if member_strand is None:
+            rc = self.lib.pc_consensus_round(*head, *tail)
+        else:
+            member_strand = np.ascontiguousarray(member_strand, dtype=np.uint8)
+            assert member_strand.shape == (M,)
+            d_strand = torch.from_numpy(member_strand).to(dev) if M else torch.zeros(1, dtype=torch.uint8, device=dev)
+            rc = self.lib.pc_consensus_round_stranded(*head, d_strand.data_ptr(), *tail)
         if rc == -6:
             raise pcc.OverBudget(int(refused.value))
         check(rc, "pc_consensus_round")

@@ -26,6 +26,8 @@ for _c, _letters in enumerate(("Aa", "Cc", "Gg", "TtUu")):
     for _l in _letters:
         _CODE[ord(_l)] = _c
 _LETTER = np.frombuffer(b"ACGT", dtype=np.uint8)
+_COMP_CODE = np.array([3, 2, 1, 0, 4], dtype=np.uint8)        # pcc::comp_code
+_COMPLEMENT = bytes.maketrans(b"ACGT", b"TGCA")
 
 # One round over several groups.  cons: the consensus bytes of all groups back to back (uint8), lens int32[groups], status and
 # distance int32[members], voters int32[groups], votes None or a list of uint32 arrays (21 la + 16 counters per group).
@@ -39,6 +41,17 @@ class OverBudget(RuntimeError):
 def codes(seq):
     """bytes / uint8 array -> base codes (A C G T = 0..3, U as T, either case, anything else 4)."""
     return _CODE[np.frombuffer(seq, dtype=np.uint8) if isinstance(seq, (bytes, bytearray)) else np.asarray(seq, dtype=np.uint8)]
+
+
+def reverse_complement_codes(b):
+    """Codes of a member -> the codes it shows when read as strand 1: base j is the complement of base lb - 1 - j (0 <-> 3,
+    1 <-> 2, 4 stays 4)."""
+    return _COMP_CODE[np.asarray(b, dtype=np.uint8)[::-1]]
+
+
+def reverse_complement(seq):
+    """A consensus (bytes over A C G T) in the other orientation."""
+    return seq.translate(_COMPLEMENT)[::-1]
 
 
 def votes_per_group(la):
@@ -168,10 +181,12 @@ def call(votes, a, voters):
     return out[keep].tobytes()
 
 
-def round_host(tmpls, member_seqs, member_group, band, max_err_pct, max_len=DEFAULTS["max_len"], tmpl_counts=1, return_votes=False):
+def round_host(tmpls, member_seqs, member_group, band, max_err_pct, max_len=DEFAULTS["max_len"], tmpl_counts=1, return_votes=False,
+               member_strand=None):
     """One round in numpy: tmpls a list of byte strings (one per group), member_seqs a list of byte strings, member_group their
     groups -> Round.  A template or member outside 1 / 0 .. max_len is what the library reports at sync(): here its members are
-    ST_INVALID with distance -1, and such a group's consensus is empty."""
+    ST_INVALID with distance -1, and such a group's consensus is empty.  member_strand: None (all 0) or one 0 / 1 per member --
+    a member of strand 1 is read as its reverse complement (pc_consensus_round_stranded); templates are never flipped."""
     G, M = len(tmpls), len(member_seqs)
     if G == 0 or M == 0:                                         # the library's no-op
         return Round(np.zeros(0, dtype=np.uint8), np.zeros(G, dtype=np.int32), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32),
@@ -185,6 +200,8 @@ def round_host(tmpls, member_seqs, member_group, band, max_err_pct, max_len=DEFA
     for m in range(M):
         g = int(member_group[m])
         b = codes(member_seqs[m])
+        if member_strand is not None and int(member_strand[m]):
+            b = reverse_complement_codes(b)
         if not fine[g] or len(b) > max_len:
             status[m], distance[m] = ST_INVALID, -1
             continue
@@ -203,7 +220,8 @@ def round_host(tmpls, member_seqs, member_group, band, max_err_pct, max_len=DEFA
 
 # ---- members and templates ----------------------------------------------------------------------------------------------------
 def members(umi_groups, lengths, start_trim, end_trim, piece_read, piece_number):
-    """Which reads are members of which group.  umi_groups as RunResult.umi_groups (per read None or (group, representative)),
+    """Which reads are members of which group.  umi_groups as RunResult.umi_groups (per read None or (group, representative) --
+    or (group, representative, strand) of a run over both strands; the strand is not looked at here),
     the trims per read, and the piece plan (per piece its read and its number: 0 for an unsplit read).  A member is a read of a
     group that is written as exactly ONE piece -- not split or discarded -- with at least one base left; its sequence is the
     trimmed read [start_trim, length - end_trim).  -> [(group, representative, [reads in input order])] in group order."""
@@ -216,7 +234,7 @@ def members(umi_groups, lengths, start_trim, end_trim, piece_read, piece_number)
     for r, entry in enumerate(umi_groups):
         if entry is None:
             continue
-        g, rep = entry
+        g, rep = entry[0], entry[1]
         reads = by_group.setdefault(g, (rep, []))[1]
         if single[r] and int(lengths[r]) - int(end_trim[r]) - int(start_trim[r]) >= 1:
             reads.append(r)
@@ -232,12 +250,14 @@ def template(lens):
 
 # ---- the rounds ----------------------------------------------------------------------------------------------------------------
 def _round(aligner, arena, dev_arena, device, tmpl_bytes, tmpl_src, seq_off, seq_len, member_reads, member_group, band, max_err_pct,
-           max_len, tmpl_counts):
+           max_len, tmpl_counts, member_strand=None):
     """One round over the open groups on the library when the aligner has consensus_round, in numpy otherwise.  tmpl_src: per
-    group the read that is the template (round 1), or None when tmpl_bytes holds earlier consensus sequences."""
+    group the read that is the template (round 1), or None when tmpl_bytes holds earlier consensus sequences.  member_strand:
+    None, or per member whether this round reads it as its reverse complement."""
+    strand_kw = {} if member_strand is None else dict(member_strand=np.asarray(member_strand, dtype=np.uint8))
     if aligner is None or not hasattr(aligner, "consensus_round"):
         return round_host(tmpl_bytes, [arena[seq_off[r]:seq_off[r] + seq_len[r]].tobytes() for r in member_reads], member_group, band,
-                          max_err_pct, max_len, tmpl_counts)
+                          max_err_pct, max_len, tmpl_counts, **strand_kw)
     import torch
     tmpl_len = np.array([len(t) for t in tmpl_bytes], dtype=np.int32)
     if tmpl_src is not None:
@@ -247,16 +267,22 @@ def _round(aligner, arena, dev_arena, device, tmpl_bytes, tmpl_src, seq_off, seq
         tmpl_arena = torch.from_numpy(np.frombuffer(b"".join(tmpl_bytes) + bytes(64), dtype=np.uint8).copy()).to(device)
     return aligner.consensus_round(dev_arena, tmpl_off, tmpl_len, np.asarray([seq_off[r] for r in member_reads], dtype=np.int64),
                                    np.asarray([seq_len[r] for r in member_reads], dtype=np.int32), np.asarray(member_group, dtype=np.int32),
-                                   band, max_err_pct, max_len=max_len, tmpl_counts=tmpl_counts, tmpl_arena=tmpl_arena)
+                                   band, max_err_pct, max_len=max_len, tmpl_counts=tmpl_counts, tmpl_arena=tmpl_arena, **strand_kw)
 
 
 def call_groups(groups, arena, seq_off, seq_len, min_reads=3, max_reads=256, band=64, rounds=2, max_err_pct=30, max_len=65535,
-                aligner=None, dev_arena=None, device=None):
+                aligner=None, dev_arena=None, device=None, read_strand=None):
     """The consensus of every group.  groups as members() gives them; arena the reads' bytes (numpy uint8), seq_off / seq_len per
     READ the offset and length of its trimmed sequence in it; dev_arena the same arena on the device (for an aligner with
     consensus_round).  -> one dict per group, in group order: group, representative, members, used (accepted in the last
     round, the template read included), rejected, skipped (members beyond max_reads, or above max_len), rounds, length, status,
-    sequence (bytes, None unless status is "called")."""
+    sequence (bytes, None unless status is "called").
+    read_strand: None, or per READ its strand in its group (0: the orientation of the founder's canonical key, 1: the other
+    strand; umi_groups.assign(strands=True)).  Round 1 runs in the orientation of its template read: the device is given
+    strand(member) ^ strand(template read), and when the template read is of strand 1 the round's consensus is
+    reverse-complemented here, on its way to being the next round's template; from round 2 on the device is given
+    strand(member).  Every sequence returned is in the group's strand-0 orientation, and every dict gains `minus`: how many of
+    the members that enter the pile-up (the template read included) are read as their reverse complement."""
     bad = check_options(min_reads, max_reads, band, rounds, max_err_pct, max_len)
     if bad:
         raise ValueError("%s %s" % bad)
@@ -265,6 +291,8 @@ def call_groups(groups, arena, seq_off, seq_len, min_reads=3, max_reads=256, ban
         taking = [r for r in reads if seq_len[r] >= 1][:max_reads]      # (a read without a base is no member: counted as skipped)
         row = dict(group=g, representative=rep, members=len(reads), used=0, rejected=0, skipped=len(reads) - len(taking), rounds=0, length=0,
                    status=CALLED, sequence=None)
+        if read_strand is not None:
+            row["minus"] = 0
         out.append(row)
         if len(reads) < min_reads:
             row["status"] = FEW_READS
@@ -279,21 +307,26 @@ def call_groups(groups, arena, seq_off, seq_len, min_reads=3, max_reads=256, ban
             row["status"] = FEW_READS
             continue
         row.update(part=part, first=first, tmpl=arena[seq_off[first]:seq_off[first] + seq_len[first]].tobytes())
+        if read_strand is not None:
+            row["minus"] = sum(int(read_strand[r]) for r in part)
         open_.append(row)
     for rnd in range(1, int(rounds) + 1):
         if not open_:
             break
         while True:
             member_reads, member_group = [], []
+            member_strand = None if read_strand is None else []
             for k, row in enumerate(open_):
                 for r in row["part"]:
                     if rnd > 1 or r != row["first"]:
                         member_reads.append(r)
                         member_group.append(k)
+                        if member_strand is not None:        # round 1 runs in the orientation of its template read
+                            member_strand.append(int(read_strand[r]) ^ (int(read_strand[row["first"]]) if rnd == 1 else 0))
             try:
                 res = _round(aligner, arena, dev_arena, device, [row["tmpl"] for row in open_],
                              [row["first"] for row in open_] if rnd == 1 else None, seq_off, seq_len, member_reads, member_group, int(band),
-                             int(max_err_pct), int(max_len), 1 if rnd == 1 else 0)
+                             int(max_err_pct), int(max_len), 1 if rnd == 1 else 0, member_strand)
                 break
             except OverBudget as e:                                  # that group is refused; the others go on
                 open_.pop(int(e.args[0]))["status"] = OVER_BUDGET
@@ -312,6 +345,8 @@ def call_groups(groups, arena, seq_off, seq_len, min_reads=3, max_reads=256, ban
                 row["status"] = EMPTY if not seq else TOO_LONG
                 continue
             unchanged = seq == row["tmpl"]
+            if rnd == 1 and read_strand is not None and int(read_strand[row["first"]]):
+                seq = reverse_complement(seq)                        # the template read was of strand 1: now the group's orientation
             row["tmpl"] = seq
             if not unchanged:                                        # a round that returns its template ends the group
                 still.append(row)
@@ -327,13 +362,18 @@ def call_groups(groups, arena, seq_off, seq_len, min_reads=3, max_reads=256, ban
 
 # ---- writers -------------------------------------------------------------------------------------------------------------------
 def fasta_text(results):
-    """One record per called group, in group order."""
-    return "".join(">umi_group_%d key=%s reads=%d used=%d rounds=%d length=%d\n%s\n" % (
-        r["group"], r["representative"], r["members"], r["used"], r["rounds"], r["length"], r["sequence"].decode("ascii"))
+    """One record per called group, in group order.  Results of a run over both strands (dicts with `minus`) say minus=<members
+    read as their reverse complement> after reads=."""
+    return "".join(">umi_group_%d key=%s reads=%d%s used=%d rounds=%d length=%d\n%s\n" % (
+        r["group"], r["representative"], r["members"], " minus=%d" % r["minus"] if "minus" in r else "", r["used"], r["rounds"], r["length"],
+        r["sequence"].decode("ascii"))
         for r in results if r["status"] == CALLED)
 
 
-def report_text(results):
-    """The TSV: a '#' header and one row per group."""
-    return "#" + "\t".join(REPORT_COLUMNS) + "\n" + "".join(
-        "%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s\n" % tuple(r[c] for c in REPORT_COLUMNS) for r in results)
+def report_text(results, minus=None):
+    """The TSV: a '#' header and one row per group; a last column `minus` for the results of a run over both strands (minus:
+    None reads that off the results)."""
+    minus = (bool(results) and all("minus" in r for r in results)) if minus is None else bool(minus)
+    return "#" + "\t".join(REPORT_COLUMNS + (("minus",) if minus else ())) + "\n" + "".join(
+        "%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s" % tuple(r[c] for c in REPORT_COLUMNS) + ("\t%d" % r["minus"] if minus else "") + "\n"
+        for r in results)

@@ -1248,8 +1248,8 @@ int pc_umi_extract(pc_ctx *c, const void *d_arena, const int64_t *d_win_off, con
     return PC_OK;
 }
 
-int pc_umi_neighbours(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
-                      int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream_v)
+static int umi_neighbours_call(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                               int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream_v, bool stranded)
 {
     if (!c || !d_found || n < 0 || n > (int64_t)INT32_MAX || cap < 0) return PC_ERR_BAD_ARG;
     if (max_len < 0 || max_len > pcud::MAX_LEN || max_dist < 0 || max_dist > pcud::MAX_LEN) return PC_ERR_BAD_ARG;
@@ -1264,8 +1264,20 @@ int pc_umi_neighbours(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len,
     a.prune = (e && atoi(e) != 0) ? 0 : 1;
     a.pairs = d_pairs; a.cap = cap; a.found = (unsigned long long *)d_found;
     a.err = c->d_err.as<uint32_t>();
-    if (pck::launch_umi_neighbours(a, stream)) return PC_ERR_NO_DEVICE;
+    if (stranded ? pck::launch_umi_neighbours_stranded(a, stream) : pck::launch_umi_neighbours(a, stream)) return PC_ERR_NO_DEVICE;
     return PC_OK;
+}
+
+int pc_umi_neighbours(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                      int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream_v)
+{
+    return umi_neighbours_call(c, d_planes, d_len, n, max_len, max_dist, d_pairs, cap, d_found, stream_v, false);
+}
+
+int pc_umi_neighbours_stranded(pc_ctx *c, const uint64_t *d_planes, const int32_t *d_len, int64_t n, int max_len, int max_dist,
+                               int32_t *d_pairs, int64_t cap, int64_t *d_found, void *stream_v)
+{
+    return umi_neighbours_call(c, d_planes, d_len, n, max_len, max_dist, d_pairs, cap, d_found, stream_v, true);
 }
 
 // votes and trace one slice of pc_consensus_round may take, unless PC_CONSENSUS_SCRATCH_MB says otherwise
@@ -1276,6 +1288,18 @@ int pc_consensus_round(pc_ctx *c, const void *d_arena, const void *d_tmpl_arena,
                        const int32_t *d_member_group, int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts,
                        uint8_t *d_cons, int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes,
                        int64_t *refused_group, void *stream_v)
+{
+    return pc_consensus_round_stranded(c, d_arena, d_tmpl_arena, h_tmpl_off, h_tmpl_len, h_group_first, n_groups, d_member_off, d_member_len,
+                                       d_member_group, nullptr, n_members, band, max_err_pct, max_len, tmpl_counts, d_cons, d_cons_len,
+                                       d_voters, d_member_out, d_votes, refused_group, stream_v);
+}
+
+int pc_consensus_round_stranded(pc_ctx *c, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off,
+                                const int32_t *h_tmpl_len, const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off,
+                                const int32_t *d_member_len, const int32_t *d_member_group, const uint8_t *d_member_strand,
+                                int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts, uint8_t *d_cons,
+                                int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
+                                void *stream_v)
 {
     if (refused_group) *refused_group = -1;
     if (!c || n_groups < 0 || n_members < 0 || n_groups > (int64_t)INT32_MAX || n_members > (int64_t)INT32_MAX) return PC_ERR_BAD_ARG;
@@ -1340,7 +1364,7 @@ int pc_consensus_round(pc_ctx *c, const void *d_arena, const void *d_tmpl_arena,
     a.arena = (const uint8_t *)d_arena; a.tmpl_arena = (const uint8_t *)d_tmpl_arena;
     a.tmpl_off = c->d_cons_meta.as<int64_t>(); a.vote_off = a.tmpl_off + n_groups; a.cons_off = a.tmpl_off + 2 * n_groups;
     a.tmpl_len = (const int32_t *)(a.tmpl_off + 3 * n_groups);
-    a.member_off = d_member_off; a.member_len = d_member_len; a.member_group = d_member_group;
+    a.member_off = d_member_off; a.member_len = d_member_len; a.member_group = d_member_group; a.member_strand = d_member_strand;
     a.n_groups_all = n_groups;
     a.trace = c->d_cons_trace.as<uint8_t>();
     a.band = band; a.max_err_pct = max_err_pct; a.max_len = max_len; a.tmpl_counts = tmpl_counts;

@@ -29,6 +29,12 @@
 // sum of its four counters exceeds `voters`; its base is its leader, ties to the smallest code.  Output order: gap 0's slots,
 // column 0, gap 1's slots, ..., gap la's slots: at most 5 la + 4 bytes.
 //
+// STRAND.  A member of strand 1 is read as its REVERSE COMPLEMENT: its base j (0-based) is the complement of the stored byte
+// lb - 1 - j -- on codes 0 <-> 3, 1 <-> 2, code 4 stays 4 (comp_code); U reads as T, whose complement is A.  member_byte() is the
+// one place that says so: the device's two refills of a member's bytes go through it, and everything downstream (DP, trace,
+// walk, votes, call) sees a member of strand 1 exactly as it would see the materialised reverse complement.  Templates are
+// never flipped.
+//
 // Plain C++ for the host and the device: no runtime include.  fill() is the serial form of the DP (the device sweeps a row
 // with its wave and a min-plus prefix scan: the same values, hence the same trace); walk(), the call rule and the layouts
 // are the device's own code.
@@ -64,6 +70,28 @@ PCC_HD int code(uint8_t ch)
     case 't': case 'u': return 3;
     default: return 4;
     }
+}
+
+// the code of the complementary base: A <-> T, C <-> G; code 4 stays 4
+PCC_HD int comp_code(int c) { return c < 4 ? 3 - c : 4; }
+// a letter whose code is comp_code(code(ch)): what a member of strand 1 shows where its stored byte is ch ('N' for code 4)
+PCC_HD uint8_t comp_letter(uint8_t ch)
+{
+    switch (ch | 0x20) {
+    case 'a': return 'T';
+    case 'c': return 'G';
+    case 'g': return 'C';
+    case 't': case 'u': return 'A';
+    default: return 'N';
+    }
+}
+
+// byte `at` (0 <= at < lb) of a member stored at mb as its strand shows it: the stored byte, or for strand 1 the letter of the
+// complement of the stored byte lb - 1 - at
+PCC_HD uint8_t member_byte(const uint8_t *mb, int64_t lb, int64_t at, bool reverse)
+{
+    const uint8_t b = mb[reverse ? lb - 1 - at : at];              // one load either way: no branch around it
+    return reverse ? comp_letter(b) : b;
 }
 
 PCC_HD int width(int band) { return 2 * band + 1; }

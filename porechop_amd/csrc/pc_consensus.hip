@@ -1,7 +1,7 @@
 // pc_consensus.hip -- one round of the UMI consensus on the device: the pile-up of every member on its group's template and
 // the call of the votes (the rule: pc_consensus.h).
 //
-// consensus_pileup_kernel<CPL>: ONE WAVE PER (member, template) PAIR, a block is one wave.  The wave sweeps the band row by
+// consensus_pileup_kernel<CPL, STRANDED>: ONE WAVE PER (member, template) PAIR, a block is one wave.  The wave sweeps the band row by
 // row; lane t owns the CPL = ceil(W / 64) consecutive cells k = t CPL .. t CPL + CPL - 1 of every row (W = 2 band + 1).
 //   * The previous row lives in LDS (W dwords).  A row's band starts sh = centre(i) - centre(i - 1) columns to the right of
 //     the row above, so cell k reads the old cells k + sh (above) and k + sh - 1 (diagonal): two LDS reads at a wave-uniform
@@ -20,6 +20,11 @@
 //     code the host test runs).  All 64 lanes walk the one path together, so that they can refill the walk's view together:
 //     64 trace rows (4 KB, sixteen bytes a lane and load) and 256 member bases are staged in LDS, and a step reads LDS, not
 //     HBM.  Lane 0 adds the votes with integer atomics: the sums do not depend on the order of arrival.
+//   * STRAND.  With ConsensusArgs.member_strand the instantiations <CPL, true> run and read a member whose strand is 1 as its
+//     reverse complement: the two places that fetch a member's bytes from global memory -- the s_member refill of the row loop
+//     and StagedSeq's refill for the walk -- go through pcc::member_byte, wave-uniform on the member's strand (a block is one
+//     wave and one member).  Everything after the staging is the same code; the votes land in template coordinates either
+//     way.  Without member_strand <CPL, false> runs: the kernel as it was, instruction for instruction.
 //   * A template or member length outside its range, a member of a group outside the slice or a walk that leaves its band
 //     adds one to the context's error word; such a member is ST_INVALID and casts no vote.
 //
@@ -93,21 +98,25 @@ struct StagedTrace {
     }
 };
 
-// The member's bases [first, first + kWalkBases) in LDS, refilled so that the base asked for is the window's last.
+// The member's bases [first, first + kWalkBases) in LDS, refilled so that the base asked for is the window's last.  STRANDED:
+// a member with `reverse` set is staged as its reverse complement (pcc::member_byte).
+template <bool STRANDED>
 struct StagedSeq {
     const uint8_t *g;
     uint8_t *lds;
     int64_t first;
     int lb, lane;
+    bool reverse;
+    static constexpr int kUnroll = STRANDED ? 1 : kWalkBases / 64;     // (see consensus_pileup_kernel)
     __device__ uint8_t operator()(int64_t j)
     {
         if (j < first || j >= first + kWalkBases) {
             wave_sync();
             first = j >= kWalkBases ? j - (kWalkBases - 1) : 0;
-#pragma unroll
+#pragma unroll kUnroll
             for (int t = 0; t < kWalkBases / 64; ++t) {
                 const int64_t at = first + t * 64 + lane;
-                if (at < (int64_t)lb) lds[t * 64 + lane] = g[at];
+                if (at < (int64_t)lb) lds[t * 64 + lane] = STRANDED ? pcc::member_byte(g, lb, at, reverse) : g[at];
             }
             wave_sync();
         }
@@ -115,7 +124,11 @@ struct StagedSeq {
     }
 };
 
-template <int CPL>
+// STRANDED: the member's strand is read once, at the top, and kept as ONE scalar (a byte load lands in a vector register, and a
+// comparison of that would hold a lane mask), and the three refills stay ROLLED loops: the row loop stands at the ceiling of
+// the scalar registers, and with the refills unrolled as they are without the strand the flag spilled two to four of them;
+// rolled, the kernel needs one scalar register fewer than without the strand.
+template <int CPL, bool STRANDED>
 __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
 {
     __shared__ int32_t s_row[64 * CPL];
@@ -126,6 +139,8 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
 
     const int lane = threadIdx.x;
     const int64_t slot = blockIdx.x, m = a.first_member + slot;
+    const bool reverse = STRANDED && __builtin_amdgcn_readfirstlane((int)a.member_strand[m]) != 0;
+    constexpr int kUnrollMember = STRANDED ? 1 : kMemberWin / 64, kUnrollTmpl = STRANDED ? 1 : kTmplRows / 64;       // (full without the strand)
     int32_t *out = a.member_out + 2 * m;
     const int64_t g = a.member_group[m];
     int la = 0, lb = a.member_len[m];
@@ -164,7 +179,7 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
         if (i - 1 >= t_first + kTmplRows) {                // (wave-uniform) the next kTmplRows bases of the template
             wave_sync();
             t_first = i - 1;
-#pragma unroll
+#pragma unroll kUnrollTmpl
             for (int t = 0; t < kTmplRows / 64; ++t) {
                 const int at = t_first + t * 64 + lane;
                 if (at < la) s_tmpl[t * 64 + lane] = ta[at];
@@ -178,10 +193,10 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
             wave_sync();
             m_first = need_lo;
             m_end = m_first + kMemberWin < (int64_t)lb ? m_first + kMemberWin : (int64_t)lb;
-#pragma unroll
+#pragma unroll kUnrollMember
             for (int t = 0; t < kMemberWin / 64; ++t) {
                 const int64_t at = m_first + t * 64 + lane;
-                if (at < m_end) s_member[t * 64 + lane] = mb[at];
+                if (at < m_end) s_member[t * 64 + lane] = STRANDED ? pcc::member_byte(mb, lb, at, reverse) : mb[at];
             }
             wave_sync();
         }
@@ -242,7 +257,7 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
     } else {
         VoteAdder votes{a.votes + (a.vote_off[g] - a.vote_base), lane == 0};
         StagedTrace staged{trace, (uint8_t *)s_trace, (int64_t)la + 1, la, lane};          // (first = la + 1: nothing staged yet)
-        StagedSeq bases{mb, s_bases, (int64_t)lb + 1, lb, lane};
+        StagedSeq<STRANDED> bases{mb, s_bases, (int64_t)lb + 1, lb, lane, reverse};
         if (!pcc::walk(bases, la, lb, band, staged, votes)) status = pcc::ST_INVALID;
     }
     if (lane != 0) return;
@@ -310,13 +325,21 @@ int launch_consensus_pileup(const ConsensusArgs &a, void *stream)
 {
     if (a.n_members <= 0) return 0;
     const dim3 grid((unsigned)a.n_members), block(64);
-    switch (pcc::cells_per_lane(a.band)) {
-    case 1: hipLaunchKernelGGL(consensus_pileup_kernel<1>, grid, block, 0, (hipStream_t)stream, a); break;
-    case 2: hipLaunchKernelGGL(consensus_pileup_kernel<2>, grid, block, 0, (hipStream_t)stream, a); break;
-    case 3: hipLaunchKernelGGL(consensus_pileup_kernel<3>, grid, block, 0, (hipStream_t)stream, a); break;
-    case 4: hipLaunchKernelGGL(consensus_pileup_kernel<4>, grid, block, 0, (hipStream_t)stream, a); break;
-    default: return 1;
+    const int cpl = pcc::cells_per_lane(a.band);
+    if (cpl < 1 || cpl > 4) return 1;
+#define PCK_PILEUP(STRANDED)                                                                                                    \
+    switch (cpl) {                                                                                                              \
+    case 1: hipLaunchKernelGGL((consensus_pileup_kernel<1, STRANDED>), grid, block, 0, (hipStream_t)stream, a); break;          \
+    case 2: hipLaunchKernelGGL((consensus_pileup_kernel<2, STRANDED>), grid, block, 0, (hipStream_t)stream, a); break;          \
+    case 3: hipLaunchKernelGGL((consensus_pileup_kernel<3, STRANDED>), grid, block, 0, (hipStream_t)stream, a); break;          \
+    default: hipLaunchKernelGGL((consensus_pileup_kernel<4, STRANDED>), grid, block, 0, (hipStream_t)stream, a); break;         \
     }
+    if (!a.member_strand) {
+        PCK_PILEUP(false)                                  // instruction for instruction the kernels from before the strands
+    } else {
+        PCK_PILEUP(true)
+    }
+#undef PCK_PILEUP
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

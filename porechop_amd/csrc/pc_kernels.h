@@ -474,12 +474,14 @@ struct UmiNeighboursArgs {
     int64_t n;
     int32_t max_len, max_dist;
     int32_t prune;               // 0: the DP runs for every pair (PC_UMI_NO_PRUNE)
-    int32_t *pairs;              // [cap][3] {i, j, distance}
+    int32_t *pairs;              // [cap][3] {i, j, distance}; the stranded kernel: [cap][4] {i, j, distance, flip}
     int64_t cap;
     unsigned long long *found;   // every pair within max_dist, written or not
     uint32_t *err;
 };
 int launch_umi_neighbours(const UmiNeighboursArgs &a, void *stream);
+// umi_neighbours_stranded_kernel: distance = min(d(i, j), d(i, mirror(j))), flip = 1 iff the mirrored comparison is the smaller
+int launch_umi_neighbours_stranded(const UmiNeighboursArgs &a, void *stream);
 
 // consensus_pileup_kernel / consensus_call_kernel (pc_consensus.hip): one round of the UMI consensus over a slice of groups
 // (pc_consensus.h).  Group arrays are indexed by the group's number in the call, member arrays by the member's.
@@ -506,6 +508,8 @@ struct ConsensusArgs {
     uint8_t *cons;
     int32_t *cons_len;           // [groups]
     uint32_t *err;
+    // (last, so that every field above keeps its place in the kernels' arguments)
+    const uint8_t *member_strand;// [members] or NULL (all 0): 1 = the member is read as its reverse complement
 };
 int launch_consensus_pileup(const ConsensusArgs &a, void *stream);
 int launch_consensus_call(const ConsensusArgs &a, void *stream);

@@ -24,6 +24,16 @@
 // the four |n_a[c] - n_b[c]|, the maximum of the three is (SAD + |la - lb|) / 2, exactly (SAD and la - lb have one parity,
 // and |la - lb| <= SAD): lower_bound_packed computes that from compositions packed one count to a byte.
 //
+// MIRROR.  mirror(k, len) is the key of the reverse complement: base t of the result is 3 - base(len - 1 - t).  A molecule read
+// from its other strand shows the key START+END as rc(END)+rc(START), which is mirror() of the concatenation.  Both planes are
+// bit-reversed within len and inverted under the length mask (3 - c flips both bits of c); len 0 gives the empty key, and
+// mirror(mirror(k)) = k under the mask.  Reversal and complement are both isometries of the edit distance, so
+// d(a, mirror(b)) = d(mirror(a), b).  mirror_composition(comp) is the composition of the mirrored key: the counts of A and T and
+// of C and G change places, and since composition() packs one count to a byte in the order A C G T (A in the lowest byte), that
+// is the reversal of the word's four bytes.  lower_bound_packed(composition(a), la, mirror_composition(composition(b)), lb) is
+// a lower bound on d(a, mirror(b)): mirror(b) has length lb and that composition, and the proof above is about any two keys --
+// apply it to a and mirror(b).
+//
 // Plain C++ for the host and the device: no runtime include, usable from pc_umi_groups.hip and tests/host/test_umi_dist.cpp.
 #pragma once
 #include <stdint.h>
@@ -136,5 +146,33 @@ PCUD_HD int lower_bound_packed(uint32_t ca, int la, uint32_t cb, int lb)
     }
     return (sad + (la > lb ? la - lb : lb - la)) >> 1;
 }
+
+// the 64 bits of x in reverse order
+PCUD_HD uint64_t reverse64(uint64_t x)
+{
+#if defined(__clang__)
+    return __builtin_bitreverse64(x);
+#else
+    x = ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0f0f0f0f0f0f0f0full) | ((x & 0x0f0f0f0f0f0f0f0full) << 4);
+    return __builtin_bswap64(x);
+#endif
+}
+
+// the key of the reverse complement: base t is 3 - base(len - 1 - t); the bits at and above len are 0
+PCUD_HD Key mirror(Key k, int len)
+{
+    Key r = {0, 0};
+    if (len <= 0) return r;
+    if (len > 64) len = 64;
+    const uint64_t m = len_mask(len);
+    r.p0 = ~(reverse64(k.p0) >> (64 - len)) & m;
+    r.p1 = ~(reverse64(k.p1) >> (64 - len)) & m;
+    return r;
+}
+
+// composition() of the mirrored key: A <-> T and C <-> G, i.e. the four count bytes (A C G T from the lowest) in reverse order
+PCUD_HD uint32_t mirror_composition(uint32_t comp) { return __builtin_bswap32(comp); }
 
 }  // namespace pcud

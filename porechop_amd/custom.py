@@ -21,6 +21,11 @@ command line of `python -m porechop_amd` (the reference's option set, unchanged 
                      (3), --umi_consensus_max_reads N (256), --umi_consensus_band N (64), --umi_consensus_rounds N (2),
                      --umi_consensus_max_err_pct N (30), --umi_consensus_max_len N (65535).  The reads stay resident: the input
                      is not streamed.
+  --umi_strands      (with --umi, --umi_groups or --umi_consensus, and START+END keys) both strands of a molecule are one group: a
+                     read of the minus strand shows the key START+END as rc(END)+rc(START), so keys are compared as they stand
+                     and mirrored, the groups TSV gains a strand column (+ / -), and the consensus piles the - reads up as
+                     their reverse complements and is written in the group's + orientation (minus=<n> in its header).  List
+                     the UMI adapter in both orientations, as two sets, so that minus-strand reads have UMIs at all (README).
 It composes with the explain report: --report PATH, --report_paths, --report_middle_paths (porechop_amd.explain)."""
 import sys
 
@@ -49,6 +54,9 @@ def build_custom_parser(prog="porechop_amd.custom"):
     p.add_argument("--umi_consensus_rounds", type=int, default=2, help="rounds: a round's consensus is the next one's template (default: 2)")
     p.add_argument("--umi_consensus_max_err_pct", type=int, default=30, help="a member further than this from the template sits the round out (default: 30)")
     p.add_argument("--umi_consensus_max_len", type=int, default=65535, help="groups whose template is longer get no sequence (default: 65535)")
+    p.add_argument("--umi_strands", action="store_true",
+                   help="group and call across both strands of a molecule: a key START+END also matches its mirror rc(END)+rc(START) "
+                        "(needs --umi, --umi_groups or --umi_consensus, and keys of both sides)")
     p.add_argument("--report", help="per-read explain report (TSV), written in input order")
     p.add_argument("--report_paths", action="store_true", help="append start_cigars / end_cigars to the report")
     p.add_argument("--report_middle_paths", action="store_true", help="append middle_cigars to the report")
@@ -100,6 +108,8 @@ def main(argv=None):
                   umi_consensus_max_reads=a.umi_consensus_max_reads, umi_consensus_band=a.umi_consensus_band,
                   umi_consensus_rounds=a.umi_consensus_rounds, umi_consensus_max_err_pct=a.umi_consensus_max_err_pct,
                   umi_consensus_max_len=a.umi_consensus_max_len)
+    if a.umi_strands:
+        kw.update(umi=a.umi, umi_strands=True, umi_group_by=a.umi_group_by)
     run_cli(a, adapter_panel=panel, wildcards=a.wildcards, **kw)
 
 

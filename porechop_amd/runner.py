@@ -419,10 +419,26 @@ def _check_umi_group_options(umi, umi_groups, by, max_dist, method):
         raise UsageError("Error: --umi_max_dist must lie in 0..%d" % ug.MAX_KEY)
 
 
-def _umi_group_by(pl, by):
+def _check_umi_strand_options(umi, umi_strands, grouping, by):
+    """The refusals of run(umi_strands=True) that need no panel."""
+    if not umi_strands:
+        return
+    if not umi:
+        raise UsageError("Error: --umi_strands needs --umi")
+    if not grouping:
+        raise UsageError("Error: --umi_strands needs --umi_groups or --umi_consensus")
+    if by is not None and by != "both":
+        raise UsageError("Error: --umi_strands needs --umi_group_by both (got %r): the mirror of a one-sided key lies at the read's other "
+                         "end, and which end that is belongs to the protocol" % (by,))
+
+
+def _umi_group_by(pl, by, strands=False):
     """Which UMIs make a read's key: `by` as given when the panel has a span on every side it names (else a UsageError), and for
     None "both" when the panel has spans on both sides, else the side that has one."""
     sides = {side for side, _si, _ai, _span in pl.umi_adapters(range(len(pl.sets)))}
+    if strands and sides != {0, 1}:
+        raise UsageError("Error: --umi_strands needs degenerate letters in a start and in an end adapter (--umi_group_by both): the panel "
+                         "has them on one side only")
     if by is None:
         return "both" if sides == {0, 1} else ("start" if 0 in sides else "end")
     for side, word in ((0, "start"), (1, "end")):
@@ -431,19 +447,21 @@ def _umi_group_by(pl, by):
     return by
 
 
-def _group_umis(path, umis, names, pl, by, max_dist, method, max_keys):
+def _group_umis(path, umis, names, pl, by, max_dist, method, max_keys, strands=False):
     """run(umi_groups=PATH) after the last read: the reads' keys, the pairs of distinct keys within max_dist edits -- on the
     GPU when the aligner has umi_neighbours, in numpy otherwise --, the groups (porechop_amd.umi_groups) and the TSV ->
-    RunResult.umi_groups."""
+    RunResult.umi_groups.  strands (umi_strands=True): across both strands of a molecule -- the entries gain the read's strand,
+    the TSV its eighth column."""
     from . import umi_groups as ug
+    strand_kw = dict(strands=True) if strands else {}
     try:
-        per_read, rows = ug.assign(umis, names, by, int(max_dist), method, int(max_keys), pl.aligner, pl.device)
+        per_read, rows = ug.assign(umis, names, by, int(max_dist), method, int(max_keys), pl.aligner, pl.device, **strand_kw)
     except OverflowError as e:
         raise UsageError("Error: %s distinct UMI keys are more than --umi_group_max_keys %d allows: the all-against-all pass grows "
                          "with the square of their number; raise --umi_group_max_keys to run it all the same" % (e.args[0], int(max_keys)))
     if path is not None:                                        # run(umi_consensus=PATH) alone makes the groups and writes no TSV
         with open(path, "w") as fh:
-            fh.write(ug.groups_header())
+            fh.write(ug.groups_header(**strand_kw))
             fh.write(rows)
     return per_read
 
@@ -470,7 +488,7 @@ def _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, shard
         raise UsageError("Error: --umi_consensus_%s %s" % bad)
 
 
-def _consensus(fasta, report, res, rs, reads, pr, num, pl, values):
+def _consensus(fasta, report, res, rs, reads, pr, num, pl, values, strands=False):
     """run(umi_consensus=PATH) after the piece plan: the groups' members (reads written as exactly one piece), the rounds over
     the arena _upload made -- on the library when the aligner has consensus_round, in numpy otherwise -- and the two files ->
     RunResult.consensus."""
@@ -480,10 +498,11 @@ def _consensus(fasta, report, res, rs, reads, pr, num, pl, values):
     seq_off = np.asarray(rs.offsets, dtype=np.int64) + np.asarray(res.start_trim, dtype=np.int64)
     seq_len = np.maximum(lengths - np.asarray(res.end_trim, dtype=np.int64) - np.asarray(res.start_trim, dtype=np.int64), 0)
     written = []
+    strand_kw = dict(read_strand=[0 if e is None else int(e[2]) for e in res.umi_groups]) if strands else {}
     try:
         out = cs.call_groups(groups, rs.arena, seq_off, seq_len, *[int(v) for v in values], aligner=pl.aligner,
-                             dev_arena=reads.arena if reads is not None else None, device=pl.device)
-        for path, text in ((fasta, cs.fasta_text(out)), (report, cs.report_text(out))):
+                             dev_arena=reads.arena if reads is not None else None, device=pl.device, **strand_kw)
+        for path, text in ((fasta, cs.fasta_text(out)), (report, cs.report_text(out, minus=True) if strands else cs.report_text(out))):
             if path is not None:
                 written.append(path)
                 with open(path, "w") as fh:
@@ -799,7 +818,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                  adapter_panel: List[AdapterSet] = None, block_bytes: int = None, report: str = None,
                  report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False,
                  umi_report: str = None, umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2,
-                 umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20, umi_consensus: str = None) -> Optional[RunResult]:
+                 umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20, umi_consensus: str = None,
+                 umi_strands: bool = False) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -809,7 +829,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     report: the per-read report of run(), appended block after block (the same bytes as a whole run's); report_paths and
     report_middle_paths as in run().  umi / umi_report as in run(): every block's reads are tagged before the block goes to
     the writer, the UMI report is appended block after block (the same bytes as a whole run's).  umi_groups and its options
-    as in run(): the groups are made after the last block, over the UMIs of all blocks.
+    as in run(): the groups are made after the last block, over the UMIs of all blocks; umi_strands as in run().
     -> None when the input is not streamable (a directory, irregular records, a damaged gzip stream, or a first block
     without the check reads): the caller loads the whole file."""
     import queue
@@ -817,6 +837,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     if umi_consensus is not None:
         raise UsageError("Error: --umi_consensus is not available in a streamed run: the reads must stay resident; use run()")
     _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
+    _check_umi_strand_options(umi, umi_strands, umi_groups is not None, umi_group_by)
     block_bytes = block_bytes or _stream_block_bytes()
     size = os.path.getsize(input_path)
     t_start = time.perf_counter()
@@ -845,7 +866,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     try:
         panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
         try:
-            group_by = _umi_group_by(pl, umi_group_by) if umi_groups is not None else None
+            group_by = _umi_group_by(pl, umi_group_by, bool(umi_strands)) if umi_groups is not None else None
         except UsageError:
             if aligner is None:
                 pl.close()
@@ -998,7 +1019,8 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
             rs = loaded.get()
         if umi_groups is not None and not failure:
             try:
-                groups_all = _group_umis(umi_groups, umis_all, names_all, pl, group_by, umi_max_dist, umi_group_method, umi_group_max_keys)
+                groups_all = _group_umis(umi_groups, umis_all, names_all, pl, group_by, umi_max_dist, umi_group_method, umi_group_max_keys,
+                                         bool(umi_strands))
             except UsageError as e:                      # too many keys: like any failure part-way, nothing is left behind
                 failure.append(e)
     finally:
@@ -1224,7 +1246,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2, umi_group_method: str = "directional",
         umi_group_max_keys: int = 1 << 20, umi_consensus: str = None, umi_consensus_report: str = None,
         umi_consensus_min_reads: int = 3, umi_consensus_max_reads: int = 256, umi_consensus_band: int = 64, umi_consensus_rounds: int = 2,
-        umi_consensus_max_err_pct: int = 30, umi_consensus_max_len: int = 65535) -> RunResult:
+        umi_consensus_max_err_pct: int = 30, umi_consensus_max_len: int = 65535, umi_strands: bool = False) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1277,6 +1299,19 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     consensus_round), so with umi_consensus given run() takes this plain driver whatever the input's size: the reads must be
     resident.  Not available in run_streamed or in a sharded run.  Off, every byte and every launch is what it was.
 
+    umi_strands=True (with umi=True, umi_groups or umi_consensus, and START+END keys: umi_group_by "both" or None on a panel with
+    degenerate letters on both sides) groups and calls ACROSS BOTH STRANDS of a molecule (DESIGN.md sections 17 and 18).  A read of
+    the minus strand shows the key START+END as rc(END)+rc(START), its mirror; the panel must list the UMI adapter in both
+    orientations, as two sets, for such reads to have UMIs at all.  The nodes are the distinct canonical keys (the smaller of a
+    key and its mirror, counts summed over both), two keys are a pair when they are within umi_max_dist as they stand or with
+    one of them mirrored (Aligner.umi_neighbours(strands=True)), and every read gets a strand: + is the orientation of its
+    group's founding canonical key, - the other.  The groups TSV keeps its seven columns with the key as read and gains an
+    eighth, strand; RunResult.umi_groups entries become (group, representative, strand 0 / 1).  The consensus piles the - reads
+    up as their reverse complements (Aligner.consensus_round(member_strand=...)), every sequence written is in the group's +
+    orientation, the FASTA header gains minus=<members read as reverse complement> after reads=, the report TSV a minus
+    column, RunResult.consensus dicts `minus`.  Headers of written reads are not changed and reads are not re-oriented.  Off,
+    every byte and every launch is what it was.
+
     Under torch.distributed (one process per GPU) the reads are sharded over the ranks and the adapter-set presence
     table of phase A is MAX-all-reduced (the only cross-read quantity in Porechop).  A plain FASTQ or FASTA file, a gzip
     file of sized members and a `cat` of gzip members take run_sharded: every rank parses, scans and WRITES only its own
@@ -1314,8 +1349,11 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     if umi_consensus is not None and umi_groups is None:         # the groups are made all the same; only the TSV is not written
         _check_umi_group_options(umi, "", umi_group_by, umi_max_dist, umi_group_method)
     grouping = umi_groups is not None or umi_consensus is not None
+    _check_umi_strand_options(umi, umi_strands, grouping, umi_group_by)
     group_kw = {} if umi_groups is None else dict(umi_groups=umi_groups, umi_group_by=umi_group_by, umi_max_dist=umi_max_dist,
                                                   umi_group_method=umi_group_method, umi_group_max_keys=umi_group_max_keys)
+    if umi_strands:
+        group_kw["umi_strands"] = True
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
             and not sharded and umi_consensus is None):
@@ -1352,7 +1390,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     try:
         panel, pl = _open_pipeline(opts, device, aligner, adapter_panel, wildcards, umi)
         try:
-            group_by = _umi_group_by(pl, umi_group_by) if grouping else None
+            group_by = _umi_group_by(pl, umi_group_by, bool(umi_strands)) if grouping else None
         except UsageError:
             if aligner is None:
                 pl.close()
@@ -1402,7 +1440,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
             lap("umi")
         if grouping:
             res.umi_groups = _group_umis(umi_groups, res.umis, [rs.name(i).split(" ")[0] for i in range(R)], pl, group_by, umi_max_dist,
-                                         umi_group_method, umi_group_max_keys)
+                                         umi_group_method, umi_group_max_keys, bool(umi_strands))
             lap("umi_groups")
 
         # ---- which pieces of which reads -------------------------------------------------
@@ -1413,7 +1451,8 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         if umi_consensus is not None:
             lap("plan_output")
             try:
-                res.consensus = _consensus(umi_consensus, umi_consensus_report, res, rs, reads, pr, num, pl, consensus_values)
+                res.consensus = _consensus(umi_consensus, umi_consensus_report, res, rs, reads, pr, num, pl, consensus_values,
+                                           bool(umi_strands))
             except Exception:                                    # nothing of this run is left behind
                 for path in (umi_report, umi_groups, report):
                     if path is not None and os.path.isfile(path):
