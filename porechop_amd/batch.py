@@ -820,8 +820,8 @@ class Aligner:
               "pc_unpack_windows")
         return dst
 
-    # ---- the glue of the middle scan as single launches (pc_middle.hip); Pipeline.phase_c keeps the torch formulation for
-    # aligners without them (the test stand-ins)
+    # ---- the glue of the middle scan as single launches (pc_middle.hip).  middle.TorchGlue is the same contract in torch
+    # expressions, for aligners without them (the test stand-ins); middle.choose_glue picks one per call
     STAT_BIG = 1 << 40
 
     def trim_windows(self, off, length, start_trim, end_trim):

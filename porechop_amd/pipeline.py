@@ -21,7 +21,10 @@ import os
 import numpy as np
 import torch
 
-from .batch import MODE_AUTO, MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS, mask_rule_gate
+from .batch import MODE_AUTO, MODE_SCORE, MODE_TRACE, MODE_TRACE_AT, MODE_TWO_PASS, NO_FLOOR, Aligner, RESULT_INTS
+# the middle scan's glue, its pure helpers and the loop of phase_c live in middle.py; the helpers keep their names here
+from .middle import (MiddleHits, MiddleScan, _identities, _round6, add_stat, choose_glue, middle_mask_tables, must_realign_torch,
+                     set_positions, switch_on, trimmed_interval)
 
 # phase B is pruned (exactly: see "Exact pruning of phase B" below) from this many (sequence, side) jobs on; measured on
 # MI355X, 1 M reads: 198 jobs 192 -> 122 ms; with the 4-6 jobs of a run without barcodes tracing everything is faster
@@ -121,17 +124,6 @@ class DeviceReads:
 
 
 @dataclass
-class MiddleHits:
-    read: torch.Tensor       # int64 [H]   read index
-    adapter: torch.Tensor    # int32 [H]   index into Pipeline.middle_adapters
-    start: torch.Tensor      # int32 [H]   read_start in trimmed-read coordinates
-    end: torch.Tensor        # int32 [H]   read_end (exclusive)
-    identity: torch.Tensor   # float64 [H] full-adapter identity
-    rounds: int = 0
-    alignments: int = 0
-
-
-@dataclass
 class EndExplain:
     """Why phase B trimmed and called each read as it did (Pipeline.phase_b_explain; the layout of the tensors is that of
     pc_phase_b_explain, include/porechop_amd.h)."""
@@ -144,74 +136,6 @@ class EndExplain:
     # phase_b_explain(paths=True): the path of every hit, row for row with `hits` (Aligner.align_paths' heads and operations)
     path_heads: Optional[torch.Tensor] = None                     # int32 [H, 4]  path_len, read_first, adapter_first, opens
     path_ops: Optional[torch.Tensor] = None                       # int32 [H, pitch]
-
-
-def must_realign_torch(a, cur, read_start, read_end, rs, re, floored_positive):
-    """pcm::must_realign (csrc/pc_mask_rule.h) over tensors that broadcast against one another, for aligners without the native
-    selection step; tests/test_mask_rule_pipeline_cpu.py holds it against the header's function record by record."""
-    changed = torch.where(read_start == -1, torch.full_like(read_start, 0 if floored_positive else 1, dtype=torch.bool),
-                          (re > rs) & ((read_start < 0) | (read_end < read_start) | ((read_start < re) & (read_end >= rs))))
-    return (changed & (a > cur)) | (a == cur)
-
-
-def _round6(x):
-    """float("%f" % x) for non-negative doubles: the value Python parses back from the C side's six printed decimals.
-    The quotient is a TRUE division by a one-element device tensor: `tensor / 1e6` with a Python scalar is evaluated by
-    PyTorch as a multiplication by the rounded reciprocal, which lands one ulp off the correctly rounded value for about
-    one identity in seven (seen as 33 of 238 presence-table entries differing from the host's in the last bit)."""
-    million = torch.full((1,), 1e6, dtype=torch.float64, device=x.device)
-    return torch.round(x * 1e6) / million
-
-
-def _identities(rec):
-    """float64 (full, partial) exactly as nanopore_read.py:476-491 parses them: the C side prints
-    (100.0*matches)/len with %f and Python float()s it back; rounding the unrounded double to six decimals
-    reproduces the printed digits as long as no value lies within 5e-7 of a rounding boundary without being on
-    it -- identities are ratios of small integers (len <= a few hundred), whose six-decimal digits are never
-    within 1e-8 of a tie."""
-    m = rec[..., 5].to(torch.float64)
-    partial = _round6(100.0 * m / rec[..., 6].to(torch.float64))
-    full = _round6(100.0 * m / rec[..., 7].to(torch.float64))
-    return full, partial
-
-
-def trimmed_interval(length, start_trim, end_trim):
-    """[s, e) of seq[start_trim : len(seq) - end_trim] with Python's slice semantics, the whole read
-    when both trims are 0 (nanopore_read.py:56-62): a start beyond the end clamps, a negative end
-    index counts from the end.  Tensors in, int64 tensors out (e < s means empty)."""
-    ln = length.to(torch.int64)
-    s_pos = torch.clamp(start_trim.to(torch.int64), max=ln)
-    e_pos = ln - end_trim.to(torch.int64)
-    e_pos = torch.where(e_pos < 0, torch.clamp(ln + e_pos, min=0), e_pos)
-    untouched = (start_trim == 0) & (end_trim == 0)
-    s_pos = torch.where(untouched, torch.zeros_like(s_pos), s_pos)
-    e_pos = torch.where(untouched, ln, e_pos)
-    return s_pos, e_pos
-
-
-def middle_mask_tables(read, start, end):
-    """What Aligner.middle_paths needs to see each middle hit's read masked as its round of mask-and-realign saw it, from the
-    hit list alone (MiddleHits lists a read's hits in discovery order; masking never moves a coordinate).
-    read int64 [H], start / end int32 [H] -> (intervals int32 [H, 2], mask_base int64 [H], mask_count int32 [H]):
-    intervals are the hits' [start, end) stably sorted by read -- no interval is copied twice -- and hit h at rank k within
-    its read gets mask_base = its read's first row and mask_count = k: the rows of its read's earlier hits."""
-    H = int(read.shape[0])
-    dev = read.device
-    if H == 0:
-        return (torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
-                torch.zeros(0, dtype=torch.int32, device=dev))
-    order = torch.sort(read, stable=True).indices
-    sorted_read = read[order]
-    row = torch.arange(H, dtype=torch.int64, device=dev)
-    first = torch.ones(H, dtype=torch.bool, device=dev)
-    first[1:] = sorted_read[1:] != sorted_read[:-1]
-    first_row = torch.cummax(torch.where(first, row, torch.zeros_like(row)), 0).values
-    intervals = torch.stack([start[order], end[order]], dim=1).to(torch.int32).contiguous()
-    mask_base = torch.empty(H, dtype=torch.int64, device=dev)
-    mask_base[order] = first_row
-    mask_count = torch.empty(H, dtype=torch.int32, device=dev)
-    mask_count[order] = (row - first_row).to(torch.int32)
-    return intervals, mask_base, mask_count
 
 
 def call_barcodes(nbins: int, start_scores: torch.Tensor, end_scores: torch.Tensor, barcode_threshold: float,
@@ -381,7 +305,7 @@ class Pipeline:
                 sorted_jobs.append((j[0], order_of[key][1], order_of[key][2]) + tuple(j[3:]))
             orders = [order_of[(id(j[1]), id(j[2]))][0] for j in jobs]
             jobs = sorted_jobs
-        if os.environ.get("PC_NO_FUSE", "0") not in ("", "0"):        # (timing experiments: every adapter alone, exact rows, two read streams)
+        if switch_on("PC_NO_FUSE"):        # (timing experiments: every adapter alone, exact rows, two read streams)
             fuse = False
         groups = {}
         for k, j in enumerate(jobs):
@@ -531,7 +455,7 @@ class Pipeline:
                 pos += int(counts[k])
                 cjobs.append((j[0], j[1][sel], j[2][sel])); cwhere.append(w)
         self.stats["pairs_end"] += sum(int(j[1].shape[0]) for j in jobs)
-        self.stats["pairs_end_traced_after_pruning"] = self.stats.get("pairs_end_traced_after_pruning", 0) + int(counts.sum())
+        add_stat(self.stats, "pairs_end_traced_after_pruning", int(counts.sum()))
         if not cjobs:
             return best_start, best_end
         outs = self._scan_jobs(self._ends_arena(reads), cjobs, MODE_TRACE, self.p.end_size)
@@ -608,7 +532,7 @@ class Pipeline:
                 off, wl = off.to(torch.int64).contiguous(), wl.to(torch.int32).contiguous()
                 for _, si, ai, _span in mine:
                     recs, umi = self.aligner.umis(self._ends_arena(reads), off, wl, ai, side, rule=rule, max_len=p.end_size)
-                    self.stats["umi_pairs"] = self.stats.get("umi_pairs", 0) + R
+                    add_stat(self.stats, "umi_pairs", R)
                     better = (umi[:, 0] == 0) & ((best_set < 0) | (recs[:, 4] > best_score))      # strict: the earlier adapter keeps a tie
                     best_set = torch.where(better, torch.full_like(best_set, si), best_set)
                     best_score = torch.where(better, recs[:, 4], best_score)
@@ -721,7 +645,7 @@ class Pipeline:
         job_adapter = np.array([j[0] for j in jobs], dtype=np.int32)
         words = (R + 63) // 64
         best_full = torch.zeros((2, R), dtype=torch.float64, device=dev)   # best traced full identity of a call pair, per side
-        trace_at = getattr(al, "trace_at", False) and os.environ.get("PC_NO_TRACE_AT", "0") in ("", "0")
+        trace_at = getattr(al, "trace_at", False) and not switch_on("PC_NO_TRACE_AT")
 
         def trace(mask, counts):
             cnt = counts.cpu().numpy()                                   # the round's one host round trip
@@ -776,14 +700,14 @@ class Pipeline:
         mask2, counts2 = select(2, mask_prev=mask1, trims=(st1, et1))
         n2 = trace(mask2, counts2)
         self.stats["pairs_end"] += J * R
-        self.stats["pairs_end_traced_after_pruning"] = self.stats.get("pairs_end_traced_after_pruning", 0) + n1 + n2
+        add_stat(self.stats, "pairs_end_traced_after_pruning", n1 + n2)
         # which pairs hold a traced record: the reductions skip the others without loading them (pc_phase_b_reduce_masked)
         self._traced_mask = torch.bitwise_or(mask1, mask2)
         return rec, rec_off
 
     def _masked_kw(self, mask):
         """Keyword for phase_b_reduce: the traced-pairs mask, where the aligner's reduction takes one (the GPU library's does)."""
-        if mask is None or not getattr(self.aligner, "reduce_takes_mask", False) or os.environ.get("PC_NO_REDUCE_MASK", "0") not in ("", "0"):
+        if mask is None or not getattr(self.aligner, "reduce_takes_mask", False) or switch_on("PC_NO_REDUCE_MASK"):
             return {}
         return {"traced_mask": mask.contiguous()}
 
@@ -798,7 +722,7 @@ class Pipeline:
         """Phase B hands its rule to the scan (Aligner.scan_device(end_rule=...)): needs the library's reduction, the packed
         kernels for every pair and an aligner that offers the call.  PC_NO_END_FLOOR=1 switches it off."""
         return self.native_reduce and getattr(self.aligner, "end_rule", False) and hasattr(self.aligner, "floor_skipped") and \
-            self.packed_kernels() and os.environ.get("PC_NO_END_FLOOR", "0") in ("", "0")
+            self.packed_kernels() and not switch_on("PC_NO_END_FLOOR")
 
     def _prune_b(self, prune, njobs):
         """prune=None: the exact pruning of phase B where it pays -- a barcode panel's worth of jobs (with a handful of
@@ -903,7 +827,7 @@ class Pipeline:
                 # (the pairs of this call alone; phase C waits for the trims in its first lines, so this wait costs no second one.
                 # They also stand in the running total that phase C reads for its own floors: noted as seen)
                 skipped = self.aligner.floor_skipped()[0]
-                self.stats["pairs_end_skipped_by_rule"] = self.stats.get("pairs_end_skipped_by_rule", 0) + skipped
+                add_stat(self.stats, "pairs_end_skipped_by_rule", skipped)
                 self._floor_seen += skipped
             return start_trim, end_trim
         outs = self._scan_jobs(self._ends_arena(reads), jobs, MODE_TRACE, p.end_size)
@@ -1094,74 +1018,79 @@ class Pipeline:
             gidx.append(groups.setdefault(hint[a], len(groups)))
         G = len(groups)
         members = [[b for b in range(B) if gidx[b] == g] for g in range(G)]
-        al = self.aligner
-        if (packed_reads is None or packed_reads.arena is not None) and G <= LEAN_PREFILTER_GROUPS and hasattr(al, "prefilter_defer_count") \
-                and hasattr(torch, "nonzero_static") and os.environ.get("PC_NO_LEAN_PREFILTER", "0") in ("", "0"):
-            # ONE host round trip for the whole stage (a handful of sets: the usual run).  The library's seed stage leaves its
-            # candidate count on the device (pc_prefilter_defer_count), the survivors of every set are counted on the device,
-            # the counts come back together, and the windows are listed by nonzero_static (no further synchronisation).
-            adl, kl = [aidx[a] for a in a_list], [ks[a] for a in a_list]
+        adl, kl = [aidx[a] for a in a_list], [ks[a] for a in a_list]
+        packed = packed_reads is not None and packed_reads.arena is None
+        if not packed and G <= LEAN_PREFILTER_GROUPS and hasattr(self.aligner, "prefilter_defer_count") \
+                and hasattr(torch, "nonzero_static") and not switch_on("PC_NO_LEAN_PREFILTER"):
+            scan_off, survivors = off, self._survivors_by_count(arena, pf_off, pf_len, max_len, adl, kl, members, order)
+        else:
+            arena, scan_off, survivors = self._survivors_by_rows(arena, off, length, pf_off, pf_len, max_len, adl, kl, gidx, G, order,
+                                                                 packed_reads if packed else None)
+        # per surviving (set, windows): one job per sequence of the set, scanned in one call -> the sparse triple
+        cjobs, cmeta = [], []
+        for g, sel in survivors:
+            so, sl = scan_off[sel], length[sel]
+            for b in members[g]:
+                cjobs.append((adl[b], so, sl, hint[a_list[b]])); cmeta.append((b, sel))
+        if not cjobs:
+            return empty
+        outs = self._scan_jobs(arena, cjobs, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len)
+        add_stat(self.stats, "pairs_middle_scanned_after_prefilter", sum(int(j[1].shape[0]) for j in cjobs))
+        sb = torch.cat([torch.full((int(sel.shape[0]),), b, dtype=torch.int64, device=dev) for b, sel in cmeta])
+        return sb, torch.cat([sel for _, sel in cmeta]), torch.cat(outs)
 
-            def survivors(defer):
-                al.prefilter_defer_count(defer)
-                try:
-                    mask = al.prefilter_mask(arena, pf_off, pf_len, max_len, adl, kl)
-                finally:
-                    al.prefilter_defer_count(False)
-                words = int(mask.shape[1])
-                gm = []
-                for g in range(G):
-                    for wd in range(words):
-                        bits = sum(1 << (b % 32) for b in members[g] if b // 32 == wd)
-                        gm.append(bits - (1 << 32) if bits >= (1 << 31) else bits)
-                if hasattr(al, "group_survivors") and os.environ.get("PC_NO_FUSED_GLUE", "0") in ("", "0"):
-                    cand, cnt = al.group_survivors(mask, self._const(gm, torch.int32).view(G, words))
-                    return [cand[g] for g in range(G)], cnt.cpu().numpy()               # the one synchronisation of this stage
-                cands = []
-                for g in range(G):
-                    c = None
-                    for wd in range(words):
-                        if gm[g * words + wd]:
-                            t = (mask[:, wd] & gm[g * words + wd]) != 0
-                            c = t if c is None else (c | t)
-                    cands.append(c)
-                return cands, torch.stack([c.sum() for c in cands]).cpu().numpy()      # the one synchronisation of this stage
-            cands, counts = survivors(True)
-            if al.prefilter_overflowed():                # (rare: the seed list overflowed -- the mask above is incomplete)
-                cands, counts = survivors(False)
-                self.stats["prefilter_overflow_reruns"] = self.stats.get("prefilter_overflow_reruns", 0) + 1
-            self.stats["pairs_middle_prefiltered"] = self.stats.get("pairs_middle_prefiltered", 0) + B * n
-            cjobs, cmeta = [], []
+    def _survivors_by_count(self, arena, pf_off, pf_len, max_len, adl, kl, members, order):
+        """The windows that survive the prefilter for each adapter set, with ONE host round trip for the whole stage (a handful
+        of sets: the usual run).  The library's seed stage leaves its candidate count on the device (pc_prefilter_defer_count),
+        the survivors of every set are counted on the device, the counts come back together, and the windows are listed by
+        nonzero_static (no further synchronisation).  -> an iterator of (set, windows int64) over the sets with survivors."""
+        al, G = self.aligner, len(members)
+        glue = choose_glue(al)
+
+        def survivors(defer):
+            al.prefilter_defer_count(defer)
+            try:
+                mask = al.prefilter_mask(arena, pf_off, pf_len, max_len, adl, kl)
+            finally:
+                al.prefilter_defer_count(False)
+            words = int(mask.shape[1])
+            gm = []
             for g in range(G):
-                if counts[g]:
-                    sel = torch.nonzero_static(cands[g], size=int(counts[g])).flatten()
-                    if order is not None:
-                        sel = order[sel]
-                    so, sl = off[sel], length[sel]
-                    for b in members[g]:
-                        cjobs.append((aidx[a_list[b]], so, sl, hint[a_list[b]])); cmeta.append((b, sel))
-            if not cjobs:
-                return empty
-            outs = self._scan_jobs(arena, cjobs, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len)
-            self.stats["pairs_middle_scanned_after_prefilter"] = self.stats.get("pairs_middle_scanned_after_prefilter", 0) + \
-                sum(int(j[1].shape[0]) for j in cjobs)
-            sb = torch.cat([torch.full((int(sel.shape[0]),), b, dtype=torch.int64, device=dev) for b, sel in cmeta])
-            return sb, torch.cat([sel for _, sel in cmeta]), torch.cat(outs)
+                for wd in range(words):
+                    bits = sum(1 << (b % 32) for b in members[g] if b // 32 == wd)
+                    gm.append(bits - (1 << 32) if bits >= (1 << 31) else bits)
+            cand, cnt = glue.group_survivors(mask, self._const(gm, torch.int32).view(G, words))
+            return cand, cnt.cpu().numpy()                                             # the one synchronisation of this stage
+        cand, counts = survivors(True)
+        if al.prefilter_overflowed():                    # (rare: the seed list overflowed -- the mask above is incomplete)
+            cand, counts = survivors(False)
+            add_stat(self.stats, "prefilter_overflow_reruns", 1)
+        add_stat(self.stats, "pairs_middle_prefiltered", len(adl) * int(pf_off.shape[0]))
+        for g in range(G):
+            if counts[g]:
+                sel = set_positions(cand[g], int(counts[g]))
+                yield g, (sel if order is None else order[sel])
+
+    def _survivors_by_rows(self, arena, off, length, pf_off, pf_len, max_len, adl, kl, gidx, G, order, packed_reads):
+        """The same from the prefilter's sparse rows (a barcode panel's many sets, packed-only reads): one compaction over all
+        sets.  -> (the arena to scan, the windows' offsets in it, an iterator of (set, windows int64)); packed-only reads
+        (packed_reads: the prefilter scans the PLANE, `off` in bases) get an arena of the surviving windows' bytes alone --
+        unless the packed route refuses the adapter list, which falls back to unpacking everything."""
+        dev, n = self.device, int(off.shape[0])
         got = None
-        if packed_reads is not None and packed_reads.arena is None:
+        if packed_reads is not None:
             kw = {"total": True} if self.p.packed_total else {}       # (only then: aligners without the keyword keep working)
-            got = self.aligner.prefilter_rows(packed_reads.plane, pf_off, pf_len, max_len, [aidx[a] for a in a_list], [ks[a] for a in a_list],
-                                              packed=True, **kw)
+            got = self.aligner.prefilter_rows(packed_reads.plane, pf_off, pf_len, max_len, adl, kl, packed=True, **kw)
             if got is None:
                 arena = packed_reads.materialize(self.aligner)
-                self.stats["packed_route_refused"] = self.stats.get("packed_route_refused", 0) + 1
+                add_stat(self.stats, "packed_route_refused", 1)
         if got is None:
-            got = self.aligner.prefilter_rows(arena, pf_off, pf_len, max_len, [aidx[a] for a in a_list], [ks[a] for a in a_list])
+            got = self.aligner.prefilter_rows(arena, pf_off, pf_len, max_len, adl, kl)
         rows, bits = got
         if order is not None:
             rows = order[rows]
-        self.stats["pairs_middle_prefiltered"] = self.stats.get("pairs_middle_prefiltered", 0) + B * n
-        if G == B:
+        add_stat(self.stats, "pairs_middle_prefiltered", len(adl) * n)
+        if G == len(adl):
             cand_g = bits
         else:                                            # union over the sequences of a set
             cand_g = torch.zeros((int(rows.shape[0]), G), dtype=torch.int32, device=dev).index_add_(
@@ -1183,24 +1112,11 @@ class Pipeline:
                 self.aligner.unpack_windows(packed_reads.plane, packed_reads.exc, off[urows].contiguous(), ulen, arena, uends)
             scan_off = torch.full((n,), -1, dtype=torch.int64, device=dev)
             scan_off[urows] = uends[:-1]
-            self.stats["bases_unpacked_after_prefilter"] = self.stats.get("bases_unpacked_after_prefilter", 0) + utotal
+            add_stat(self.stats, "bases_unpacked_after_prefilter", utotal)
         else:
             counts = torch.bincount(hitg[:, 0], minlength=G).cpu().numpy()     # the one synchronisation of this stage
-        cjobs, cmeta, pos = [], [], 0
-        for g in range(G):
-            if counts[g]:
-                sel = rows[hitg[pos:pos + int(counts[g]), 1]]
-                pos += int(counts[g])
-                so, sl = scan_off[sel], length[sel]
-                for b in members[g]:
-                    cjobs.append((aidx[a_list[b]], so, sl, hint[a_list[b]])); cmeta.append((b, sel))
-        if not cjobs:
-            return empty
-        outs = self._scan_jobs(arena, cjobs, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len)
-        self.stats["pairs_middle_scanned_after_prefilter"] = self.stats.get("pairs_middle_scanned_after_prefilter", 0) + \
-            sum(int(j[1].shape[0]) for j in cjobs)
-        sb = torch.cat([torch.full((int(sel.shape[0]),), b, dtype=torch.int64, device=dev) for b, sel in cmeta])
-        return sb, torch.cat([sel for _, sel in cmeta]), torch.cat(outs)
+        firsts = np.concatenate([[0], np.cumsum(counts)])
+        return arena, scan_off, ((g, rows[hitg[int(firsts[g]):int(firsts[g + 1]), 1]]) for g in range(G) if counts[g])
 
     def phase_c(self, reads: DeviceReads, start_trim, end_trim, matching: List[int], prove: bool = False,
                 prefilter: bool = False) -> MiddleHits:
@@ -1231,304 +1147,12 @@ class Pipeline:
         substring of the read; pairs farther apart are PROVEN not to be hits and never reach the DP.  The reads
         that survive for one of a set's sequences run the two-pass scan for that set (both of its sequences in one
         pass, on the set's ahead-of-time kernel).  Hits, masks, rounds and alignment counts are identical."""
-        p = self.p
-        dev = self.device
         prove = prove and self.packed_kernels()                # the score bound is derived for the packed kernels' schemes
         ads_sets = self._middle_adapters_with_sets(matching)
-        ads = [a for a, _ in ads_sets]
-        hint = [("set", si) for _, si in ads_sets]
-        self.middle_adapters = ads
-        A = len(ads)
-        empty = MiddleHits(*(torch.empty(0, dtype=dt, device=dev) for dt in
-                             (torch.int64, torch.int32, torch.int32, torch.int32, torch.float64)))
-        R = reads.n
-        if A == 0 or R == 0:
-            return empty
-        # masked_seq = seq[start_trim : len - end_trim] with Python slice semantics (nanopore_read.py:56-62)
-        # (one round trip: how many reads are left after trimming, and the extremes / mean of their lengths)
-        al = self.aligner
-        fused = hasattr(al, "round_consume") and os.environ.get("PC_NO_FUSED_GLUE", "0") in ("", "0")     # pc_middle.hip: one launch each
-        if fused:
-            toff, tlen, st4 = al.trim_windows(reads.off, reads.length, start_trim, end_trim)
-            mm = st4.cpu()
-            mm[2] = (al.STAT_BIG - mm[2]) if int(mm[2]) else 0
-            pos_len = None
-        else:
-            s_pos, e_pos = trimmed_interval(reads.length, start_trim, end_trim)
-            tlen = torch.clamp(e_pos - s_pos, min=0).to(torch.int32)
-            toff = reads.off + s_pos
-            pos_len = tlen > 0
-            big = torch.iinfo(torch.int32).max
-            mm = torch.stack([pos_len.sum(), tlen.max(), torch.where(pos_len, tlen, torch.full_like(tlen, big)).min(),
-                              tlen.sum(dtype=torch.int64)]).cpu()
-        n_live = int(mm[0])
-        if n_live == 0:
-            return empty
-        if n_live == R:
-            live = torch.arange(R, device=dev)
-            loff, llen = toff, tlen
-        else:
-            if pos_len is None:
-                pos_len = tlen > 0
-            live = torch.nonzero_static(pos_len, size=n_live).flatten() if hasattr(torch, "nonzero_static") else torch.nonzero(pos_len).flatten()
-            loff, llen = toff[live], tlen[live]
-        packed_only = reads.arena is None
-        if packed_only and not prefilter:
-            reads.materialize(self.aligner)                          # every pair runs the DP: every base is needed as a byte
-            packed_only = False
-        # (windows of different lengths are handed over longest first even when they differ by a per cent -- 8-kb reads that lost
-        # 0..150 bases to their trims: tiles of nearly one length keep the specialised score kernel on its block-resolved path;
-        # skipping the sort for such batches was measured: 0.3 ms of glue saved, 1.6 ms of scan lost at 1 M reads)
-        max_len, ragged, typ_len = int(mm[1]), bool(int(mm[1]) != int(mm[2])), int(mm[3]) // n_live
-        aidx = [self.seq_index[a[1]] for a in ads]
-
-        def identity_of(rec):
-            full, _ = _identities(rec)
-            return torch.where(rec[..., 0] == -1, torch.zeros_like(full), full)
-
-        # ---- round 0: all adapters x all reads, unmasked -------------------------------------
-        jobs0 = [(ai, loff, llen, h) for ai, h in zip(aidx, hint)]
-        bounds = [self.identity_score_bound(len(self.seqs[ai]), p.middle_threshold) for ai in aidx] if prove else None
-        # The default route hands the same bound down as a score floor per job: the library decides between its two passes which
-        # pairs can still be hits and traces only those (pc_scan_device_floored); the others get the "no alignment" record, which
-        # is "not a hit" below.  PC_NO_PASS2_FLOOR=1: every pair traced.
-        floors = None
-        if not prove and not prefilter and fused and hasattr(al, "floor_skipped") and self.packed_kernels() \
-                and os.environ.get("PC_NO_PASS2_FLOOR", "0") in ("", "0"):
-            floors = [self.identity_score_bound(len(self.seqs[ai]), p.middle_threshold) for ai in aidx]
-            if any(b is None for b in floors):
-                floors = None
-        sparse0 = None
-        if prefilter:
-            ks = [self.aligner.max_edits(len(self.seqs[ai]), p.middle_threshold) for ai in aidx]
-            sparse0 = self._prefiltered_scan(reads.arena, loff, llen, max_len, list(range(A)), aidx, hint, ks, ragged, typ_len,
-                                             packed_reads=reads if packed_only else None)
-            packed_only = packed_only and reads.arena is None         # (the packed route may have been refused: everything unpacked)
-        elif prove and all(b is not None for b in bounds):
-            score = torch.stack(self._scan_jobs(reads.arena, jobs0, MODE_SCORE, max_len, sort_lengths=ragged, typ_len=typ_len))[:, :, 4]      # [A, L]
-            cand = torch.nonzero(score >= self._const(bounds)[:, None])                     # adapter-major
-            counts = torch.bincount(cand[:, 0], minlength=A).cpu().numpy()
-            L = int(live.numel())
-            recs = torch.zeros((A, L, RESULT_INTS), dtype=torch.int32, device=dev)
-            cjobs, csel, pos = [], [], 0
-            for a in range(A):
-                if counts[a]:
-                    sel = cand[pos:pos + int(counts[a]), 1]
-                    pos += int(counts[a])
-                    cjobs.append((aidx[a], loff[sel], llen[sel])); csel.append((a, sel))     # (different windows per adapter: never fused)
-            if cjobs:
-                for (a, sel), o in zip(csel, self._scan_jobs(reads.arena, cjobs, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len)):
-                    recs[a, sel] = o
-            outs = [recs[a] for a in range(A)]
-            # an all-zero record (rs = 0, lengths 0) is "not a hit" below: 0/0 identities are masked
-            fulls = torch.stack([torch.nan_to_num(identity_of(rec), nan=0.0) for rec in outs])
-            self.stats["pairs_middle_traced_after_proof"] = self.stats.get("pairs_middle_traced_after_proof", 0) + int(counts.sum())
-        else:
-            outs = self._scan_jobs(reads.arena, jobs0, MODE_TWO_PASS, max_len, sort_lengths=ragged, typ_len=typ_len, floors=floors)
-            if fused:
-                fulls, hit0_f = al.middle_hits(torch.stack(outs), p.middle_threshold)          # [A, L] each
-            else:
-                fulls = torch.stack([identity_of(rec) for rec in outs])  # [A, L]
-        L_ = int(live.numel())
-        if sparse0 is not None:
-            sa, sw, sr = sparse0                                     # every pair not listed is proven not to be a hit
-            if fused:
-                full_s, hit_s = al.middle_hits(sr.contiguous(), p.middle_threshold)
-            else:
-                full_s = torch.nan_to_num(identity_of(sr), nan=0.0)
-                hit_s = (full_s >= p.middle_threshold) & (sr[:, 0] != -1)
-            dmask = torch.zeros(L_, dtype=torch.int32, device=dev).index_add_(0, sw, hit_s.to(torch.int32)) > 0
-        elif fused and not prove:
-            dmask = hit0_f.any(dim=0)
-        else:
-            hit0 = (fulls >= p.middle_threshold) & torch.stack([rec[:, 0] != -1 for rec in outs])
-            dmask = hit0.any(dim=0)
-        # (one round trip: the dirty reads -- those with a hit -- their number, longest, total padded size and mean length)
-        dstride_all = (llen.to(torch.int64) + (8 + 15)) // 16 * 16
-        zero64 = torch.zeros((), dtype=torch.int64, device=dev)
-        mm2 = torch.stack([dmask.sum(), torch.where(dmask, llen.to(torch.int64), zero64).max(), torch.where(dmask, dstride_all, zero64).sum(),
-                           torch.where(dmask, llen.to(torch.int64), zero64).sum()]).cpu()
-        Dn = int(mm2[0])
-        if Dn > 0:                                                   # dirty reads (indices into live), increasing
-            d_sel = torch.nonzero_static(dmask, size=Dn).flatten() if hasattr(torch, "nonzero_static") else torch.nonzero(dmask).flatten()
-        n_align = A * int(live.numel())                              # alignments the reference performs
-        n_spec = 0                                                   # speculative ones, discarded
-        n_kept = 0                                                   # of the rounds' (A - a0) x active pairs, those the mask rule kept
-        rounds = 0
-        H_read, H_ad, H_s, H_e, H_id = [], [], [], [], []
-        if Dn > 0:
-            if sparse0 is not None:                                  # [A, Dn, 8] from the sparse records of the dirty reads
-                # (no boolean masks -- each is a nonzero, a host round trip: the records of reads that are not dirty all go to
-                # one spare row behind the table)
-                where = torch.full((int(live.numel()),), -1, dtype=torch.int64, device=dev)
-                where[d_sel] = torch.arange(Dn, device=dev)
-                w2 = where[sw]
-                flat = torch.where(w2 >= 0, sa * Dn + w2, torch.full_like(w2, A * Dn))
-                rec_flat = torch.zeros((A * Dn + 1, RESULT_INTS), dtype=torch.int32, device=dev)
-                full_flat = torch.zeros(A * Dn + 1, dtype=torch.float64, device=dev)
-                rec_flat[flat] = sr
-                full_flat[flat] = full_s
-                rec_all = rec_flat[:A * Dn].view(A, Dn, RESULT_INTS)
-                full_all = full_flat[:A * Dn].view(A, Dn)
-            else:
-                rec_all = torch.stack([o[d_sel] for o in outs])      # [A, Dn, 8] for the current masked state
-                full_all = fulls[:, d_sel]
-            # private, maskable copies of the dirty reads, back to back whatever their lengths (each padded
-            # with N to a multiple of 16 bytes plus slack: the kernels read whole dwords)
-            dlen = llen[d_sel].contiguous()
-            dstride = (dlen.to(torch.int64) + (8 + 15)) // 16 * 16
-            d_ends = torch.zeros(Dn + 1, dtype=torch.int64, device=dev)
-            d_ends[1:] = torch.cumsum(dstride, 0)
-            dmax, dtotal, dtyp = int(mm2[1]), int(mm2[2]), int(mm2[3]) // Dn
-            dirty = torch.empty(dtotal + 64, dtype=torch.uint8, device=dev)
-            dirty[dtotal:] = ord("N")
-            d_off = d_ends[:-1]
-            if packed_only:                                         # (d_sel is ascending: torch.unique)
-                self.aligner.unpack_windows(reads.plane, reads.exc, loff[d_sel].contiguous(), dlen, dirty, d_ends, ord("N"))
-            elif hasattr(self.aligner, "copy_windows"):
-                self.aligner.copy_windows(reads.arena, loff[d_sel].contiguous(), dlen, dirty, d_ends, ord("N"))
-            else:                                                    # injected test aligner: the same copy in torch
-                seg = torch.repeat_interleave(torch.arange(Dn, device=dev), dstride)
-                pos = torch.arange(dtotal, device=dev, dtype=torch.int64) - d_off[seg]
-                inside = pos < dlen[seg]
-                src = loff[d_sel][seg] + torch.clamp(pos, max=(dlen.to(torch.int64) - 1)[seg])
-                dirty[:dtotal] = torch.where(inside, reads.arena[src], torch.full_like(src, ord("N"), dtype=torch.uint8))
-            arow = torch.arange(A, device=dev)[:, None]
-            cur = torch.zeros(Dn, dtype=torch.int64, device=dev)     # adapter each dirty read is at
-            act = torch.arange(Dn, device=dev)
-            n_align -= A * Dn                                        # re-counted below as consumed
-            scheduled = A * Dn
-            # The mask rule (csrc/pc_mask_rule.h): a mask only lowers substitution scores, so the record of a pair whose read
-            # interval the mask does not touch -- and, under positive floors, every "no alignment" record -- is provably the one
-            # already held.  A round then scans, per adapter SET (its sequences share one window list and fuse into the dual
-            # kernel), only the reads that have a record of the set the mask can have changed.  Behind the rule's gate (letters
-            # A/C/G/T/U, no wildcards, mismatch <= match); PC_NO_MASK_RULE=1, read per call: every round as before.  The proving
-            # routes keep their rounds (their tables hold all-zero "not computed" records, of which the rule says nothing).
-            use_rule = not prefilter and not prove and os.environ.get("PC_NO_MASK_RULE", "0") in ("", "0") \
-                and mask_rule_gate([self.seqs[ai] for ai in aidx], p.scores, p.wildcards)
-            if use_rule:
-                set_ids = sorted(set(si for _, si in ads_sets))
-                S_ = len(set_ids)
-                set_of = [set_ids.index(si) for _, si in ads_sets]                 # the dense set index of every middle adapter
-                set_adapters = [[a for a in range(A) if set_of[a] == s_] for s_ in range(S_)]
-                set_of_t = self._const(set_of, dtype=torch.int32 if fused else torch.int64)
-                floored_pos = floors is not None and all(f > 0 for f in floors)
-            while True:
-                # consume, per active read: adapters cur.. in order, up to and including the first hit
-                # (one round trip per round: alignments consumed, reads that hit, the first adapter among them, bases to mask --
-                # and, with the rule, how many of the reads that hit need each set: the same buffer)
-                need = None
-                if fused and use_rule:
-                    anyh, a_hit, cnt_all, st4, need = al.round_consume_select(full_all, rec_all, cur, act, p.middle_threshold, set_of_t, S_,
-                                                                              floored_pos)
-                    st_ = st4.cpu()
-                    n_used, n_hit, n_mask = int(st_[0]), int(st_[1]), int(st_[3])
-                    a0 = (al.STAT_BIG - int(st_[2])) if int(st_[2]) else A
-                    r_all = None
-                elif fused:
-                    anyh, a_hit, cnt_all, st4 = al.round_consume(full_all, rec_all, cur, act, p.middle_threshold)
-                    st_ = st4.cpu()
-                    n_used, n_hit, n_mask = int(st_[0]), int(st_[1]), int(st_[3])
-                    a0 = (al.STAT_BIG - int(st_[2])) if int(st_[2]) else A
-                    r_all = None
-                else:
-                    c = cur[act]
-                    hm = (full_all[:, act] >= p.middle_threshold) & (rec_all[:, act, 0] != -1) & (arow >= c[None, :])
-                    anyh = hm.any(dim=0)
-                    a_hit = hm.to(torch.int32).argmax(dim=0)
-                    used = torch.where(anyh, a_hit - c + 1, A - c)
-                    r_all = rec_all[a_hit, act]
-                    cnt_all = torch.where(anyh, torch.clamp(r_all[:, 1] + 1 - r_all[:, 0], min=0), torch.zeros_like(r_all[:, 0])).to(torch.int64)
-                    st_ = torch.stack([used.sum(), anyh.sum(), torch.where(anyh, a_hit, torch.full_like(a_hit, A)).min().to(torch.int64),
-                                       cnt_all.sum()])
-                    if use_rule:
-                        must = must_realign_torch(arow, a_hit[None, :], rec_all[:, act, 0], rec_all[:, act, 1], r_all[:, 0][None, :],
-                                                  (r_all[:, 1] + 1)[None, :], floored_pos) & anyh[None, :]
-                        need = torch.zeros((S_, int(act.numel())), dtype=torch.int32, device=dev).index_add_(0, set_of_t, must.to(torch.int32)) > 0
-                        st_ = torch.cat([st_, need.sum(dim=1)])
-                    st_ = st_.cpu()
-                    n_used, n_hit, a0, n_mask = int(st_[0]), int(st_[1]), int(st_[2]), int(st_[3])
-                n_align += n_used
-                n_spec += scheduled - n_used
-                if n_hit == 0:
-                    break
-                hidx = torch.nonzero_static(anyh, size=n_hit).flatten() if hasattr(torch, "nonzero_static") else torch.nonzero(anyh).flatten()
-                hsel = act[hidx]
-                ah = a_hit[hidx].to(torch.int64)
-                r = rec_all[ah, hsel] if r_all is None else r_all[hidx]
-                rs, re = r[:, 0], r[:, 1] + 1
-                H_read.append(live[d_sel[hsel]]); H_ad.append(ah.to(torch.int32))
-                H_s.append(rs); H_e.append(re); H_id.append(full_all[ah, hsel])
-                # masked_seq[rs:re] = '-' * n: the masked positions of all hits as one index list
-                cnt = cnt_all[hidx]
-                first = torch.cumsum(cnt, 0) - cnt
-                run = torch.repeat_interleave(d_off[hsel] + rs.to(torch.int64) - first, cnt, output_size=n_mask)
-                dirty.index_fill_(0, run + torch.arange(n_mask, device=dev, dtype=torch.int64), ord("-"))   # (x[idx] = scalar uploads the scalar: a round trip)
-                cur[hsel] = ah                                       # the reference re-aligns the adapter that hit
-                act = hsel
-                rounds += 1
-                o_act, l_act = d_off[act], dlen[act]
-                scheduled = (A - a0) * int(act.numel())
-                if use_rule:
-                    # per set with a non-zero count, one job per sequence of the set over the reads that need the set.  The
-                    # windows go longest first (one argsort a round, as _scan_jobs would per window list); one nonzero lists the
-                    # (set, read) pairs set by set, and the host cuts that list at the counts it already holds.
-                    counts = [int(x) for x in st_[4:4 + S_]]
-                    act_s, o_s, l_s, need_h = act, o_act, l_act, need[:, hidx]
-                    if ragged:
-                        perm = torch.argsort(l_act, descending=True, stable=True)
-                        act_s, o_s, l_s, need_h = act[perm], o_act[perm], l_act[perm], need_h[:, perm]
-                    need_flat = need_h.reshape(-1)
-                    flat = torch.nonzero_static(need_flat, size=sum(counts)).flatten() if hasattr(torch, "nonzero_static") \
-                        else torch.nonzero(need_flat).flatten()
-                    which = flat % n_hit
-                    o_f, l_f, act_f = o_s[which], l_s[which], act_s[which]
-                    rjobs, rmeta, at = [], [], 0
-                    for s_ in range(S_):
-                        if counts[s_]:
-                            o_c, l_c, a_c = o_f[at:at + counts[s_]], l_f[at:at + counts[s_]], act_f[at:at + counts[s_]]
-                            at += counts[s_]
-                            for a in set_adapters[s_]:
-                                if a >= a0:
-                                    rjobs.append((aidx[a], o_c, l_c, hint[a])); rmeta.append((a, a_c))
-                    n_kept += scheduled - sum(int(a_c.shape[0]) for _, a_c in rmeta)
-                    if rjobs:
-                        res, out_r, rec_off = self._scan_jobs(dirty, rjobs, MODE_TWO_PASS, dmax, with_layout=True, presorted=ragged, typ_len=dtyp,
-                                                              floors=[floors[a] for a, _ in rmeta] if floors is not None else None,
-                                                              no_skip_underfilled=True)
-                        full_r = al.middle_hits(out_r, p.middle_threshold)[0] if fused else torch.nan_to_num(identity_of(out_r), nan=0.0)
-                        for (a, a_c), r_, ro in zip(rmeta, res, rec_off):
-                            rec_all[a, a_c] = r_
-                            full_all[a, a_c] = full_r[ro:ro + int(a_c.shape[0])]
-                    continue
-                if prefilter:                                        # the masked reads go through the same proof first
-                    rb, rw, rr = self._prefiltered_scan(dirty, o_act, l_act, dmax, list(range(a0, A)), aidx, hint, ks, ragged, dtyp)
-                    outs_r = torch.zeros((A - a0, int(act.numel()), RESULT_INTS), dtype=torch.int32, device=dev)
-                    outs_r[rb, rw] = rr
-                else:
-                    # (a mask round is a launch of few, short units: no row skipping where the library chunks it -- DESIGN.md 4)
-                    outs_r = self._scan_jobs(dirty, [(aidx[a], o_act, l_act, hint[a]) for a in range(a0, A)], MODE_TWO_PASS, dmax,
-                                             sort_lengths=ragged, typ_len=dtyp, floors=floors[a0:] if floors is not None else None,
-                                             no_skip_underfilled=True)
-                if not torch.is_tensor(outs_r):
-                    outs_r = torch.stack(outs_r)                     # [A - a0, active, 8]
-                # (all adapters at once: a loop over the 196 sequences of a barcode panel is ~2 000 tiny launches a round)
-                rec_all[a0:, act] = outs_r
-                full_all[a0:, act] = al.middle_hits(outs_r.contiguous(), p.middle_threshold)[0] if fused else torch.nan_to_num(identity_of(outs_r), nan=0.0)
-        self.stats["pairs_middle"] += n_align
-        self.stats["pairs_middle_speculative"] = self.stats.get("pairs_middle_speculative", 0) + n_spec
-        self.stats["pairs_middle_kept_by_mask_rule"] = self.stats.get("pairs_middle_kept_by_mask_rule", 0) + n_kept
-        if floors is not None:
-            # (the context's running total, read once per call where the device has just been waited for -- the last round's
-            # statistics above, or the dirty-read count -- so the 16-byte copy waits for nothing)
-            total = al.floor_skipped()[1]
-            self.stats["pairs_middle_skipped_by_floor"] = self.stats.get("pairs_middle_skipped_by_floor", 0) + total - self._floor_seen
-            self._floor_seen = total
-        if not H_read:
-            empty.rounds, empty.alignments = rounds, n_align
-            return empty
-        return MiddleHits(torch.cat(H_read), torch.cat(H_ad), torch.cat(H_s), torch.cat(H_e), torch.cat(H_id),
-                          rounds, n_align)
+        self.middle_adapters = [a for a, _ in ads_sets]
+        if not ads_sets or reads.n == 0:
+            return MiddleHits.none(self.device)
+        return MiddleScan(self, reads, ads_sets, prove, prefilter).run(start_trim, end_trim)
 
     def middle_hit_paths(self, reads: DeviceReads, start_trim, end_trim, hits: MiddleHits):
         """The alignment path of every middle hit of phase_c (same reads, trims and matching sets; hits.adapter indexes the
@@ -1546,12 +1170,8 @@ class Pipeline:
                     torch.zeros((0, 1), dtype=torch.int32, device=dev))
         if reads.arena is None:
             reads.materialize(al)                                    # every base of a window is needed as a byte
-        if hasattr(al, "trim_windows"):
-            toff, tlen, _ = al.trim_windows(reads.off, reads.length, start_trim, end_trim)
-        else:
-            s_pos, e_pos = trimmed_interval(reads.length, start_trim, end_trim)
-            tlen = torch.clamp(e_pos - s_pos, min=0).to(torch.int32)
-            toff = reads.off + s_pos
+        glue = choose_glue(al)
+        toff, tlen, _ = glue.trim_windows(reads.off, reads.length, start_trim, end_trim)
         aidx = torch.tensor([self.seq_index[a[1]] for a in self.middle_adapters], dtype=torch.int32, device=dev)
         intervals, mask_base, mask_count = middle_mask_tables(hits.read, hits.start, hits.end)
         read_off = toff[hits.read].to(torch.int64).contiguous()
@@ -1559,7 +1179,7 @@ class Pipeline:
         recs, heads, ops = al.middle_paths(reads.arena, read_off, read_len, aidx[hits.adapter.to(torch.int64)].contiguous(),
                                            hits.end.to(torch.int32).contiguous(), mask_base, mask_count, intervals)
         # (the %f-rounded full identity, from the code phase_c got the hits' from)
-        full = al.middle_hits(recs, self.p.middle_threshold)[0] if hasattr(al, "middle_hits") else _identities(recs)[0]
+        full = glue.middle_hits(recs, self.p.middle_threshold)[0]
         same = (recs[:, 0] == hits.start) & (recs[:, 1] + 1 == hits.end) & (full == hits.identity)
         if not bool(same.all()):
             k = int(torch.nonzero(~same)[0])

@@ -8,12 +8,10 @@ import math
 import numpy as np
 import pytest
 
-from tests import glue_ref, gluegen
+from tests import glue_cases, glue_ref, gluegen
+from tests.glue_cases import SIZES
 
 pytestmark = pytest.mark.gpu
-
-SIZES = [1, 63, 64, 65, 255, 256, 257, 4097]
-STAT_BIG = glue_ref.STAT_BIG
 
 
 @pytest.fixture(scope="module")
@@ -165,146 +163,35 @@ def test_phase_b_reduce_empty_batch(al):
 
 
 # ---- the middle scan's glue (pc_middle.hip) ------------------------------------------------------------------------------
-def trim_inputs(rng, n):
-    length = rng.choice([0, 1, 2, 7, 150, 151, 300, 1000, 5000], size=n).astype(np.int32)
-    st = np.where(rng.random(n) < 0.3, 0, rng.integers(0, 1200, size=n)).astype(np.int32)
-    et = np.where(rng.random(n) < 0.3, 0, rng.integers(0, 2500, size=n)).astype(np.int32)
-    k = rng.random(n)
-    et = np.where(k < 0.1, length + rng.integers(1, 40, size=n), et).astype(np.int32)       # past the length: negative index
-    st = np.where((k >= 0.1) & (k < 0.15), length + rng.integers(0, 3, size=n), st).astype(np.int32)   # start past the end
-    off = np.cumsum(np.concatenate([[5], length[:-1].astype(np.int64) + 3])).astype(np.int64)
-    return off, length, st, et
-
-
-def check_trim_windows(al, off, length, st, et):
-    toff, tlen, stats = al.trim_windows(dev(off), dev(length), dev(st), dev(et))
-    al.sync()
-    toff, tlen = toff.cpu().numpy(), tlen.cpu().numpy()
-    want = [glue_ref.trimmed_interval(int(length[i]), int(st[i]), int(et[i])) for i in range(len(off))]
-    ws = np.array([w[0] for w in want], dtype=np.int64)
-    wl = np.array([w[1] for w in want], dtype=np.int64)
-    assert np.array_equal(tlen, wl)
-    assert np.array_equal(toff, off + ws)
-    assert stats.cpu().tolist() == glue_ref.trim_stats(wl.tolist())
-
-
+# (the case bodies are tests/glue_cases.py's: tests/test_middle_glue_cpu.py holds the torch glue to the same ones)
 @pytest.mark.parametrize("n", SIZES + [1_000_003])
 def test_trim_windows_equals_python_slices(al, n):
-    off, length, st, et = trim_inputs(np.random.default_rng(n), n)
-    check_trim_windows(al, off, length, st, et)
+    glue_cases.trim_windows_equal_python_slices(al, dev, n, al.sync)
 
 
 def test_trim_windows_edges(al):
-    rng = np.random.default_rng(3)
-    off, length, st, et = trim_inputs(rng, 4097)
-    st[:300] = 0
-    et[:300] = 0                                     # both trims 0: the whole read
-    check_trim_windows(al, off, length, st, et)
-    for n in (1, 257, 4097):                          # all-empty batches: "shortest non-empty" stays "none" (0)
-        z = np.zeros(n, dtype=np.int32)
-        check_trim_windows(al, np.arange(n, dtype=np.int64), z, z + 1, z)
-        L = np.full(n, 10, dtype=np.int32)
-        check_trim_windows(al, np.arange(n, dtype=np.int64), L, L, z + 3)
-    e = np.zeros(0, dtype=np.int32)
-    check_trim_windows(al, np.zeros(0, dtype=np.int64), e, e, e)
-
-
-def middle_records(rng, n):
-    recs = gluegen.end_records(rng, n, 5000, 1)
-    return recs
+    glue_cases.trim_windows_edges(al, dev, al.sync)
 
 
 @pytest.mark.parametrize("n", SIZES + [1_000_003])
 def test_middle_hits_equal_the_reference(al, n):
-    rng = np.random.default_rng(n + 1)
-    recs = middle_records(rng, n)
-    F = glue_ref.record_fields(recs)
-    thrs = [90.0, 66.666667, 200.0 / 3, math.nextafter(66.666667, 100), 33.333333, 100.0 / 3] if n < 1_000_000 else [100.0 / 3]
-    t = dev(recs)
-    for thr in thrs:
-        full, hit = al.middle_hits(t, thr)
-        al.sync()
-        wf, wh = zip(*[glue_ref.middle_hit(f, thr) for f in F])
-        assert np.array_equal(full.cpu().numpy(), np.nan_to_num(np.array(wf), nan=0.0)), thr
-        assert hit.cpu().numpy().tolist() == list(wh), thr
+    glue_cases.middle_hits_equal_the_reference(al, dev, n, al.sync)
 
 
 def test_middle_hits_keep_the_batch_shape_and_accept_an_empty_batch(al):
-    import torch
-    rng = np.random.default_rng(2)
-    recs = middle_records(rng, 3 * 65).reshape(3, 65, 8)
-    full, hit = al.middle_hits(dev(recs), 33.333333)
-    al.sync()
-    assert tuple(full.shape) == (3, 65) and tuple(hit.shape) == (3, 65)
-    F = glue_ref.record_fields(recs.reshape(-1, 8))
-    assert hit.cpu().numpy().reshape(-1).tolist() == [glue_ref.middle_hit(f, 33.333333)[1] for f in F]
-    full, hit = al.middle_hits(torch.zeros((0, 8), dtype=torch.int32, device="cuda"), 90.0)
-    al.sync()
-    assert full.numel() == 0 and hit.numel() == 0
+    glue_cases.middle_hits_keep_the_batch_shape_and_accept_an_empty_batch(al, dev, al.sync)
 
 
 @pytest.mark.parametrize("n", SIZES)
 @pytest.mark.parametrize("A", [1, 2, 7, 33])
 def test_round_consume_equals_one_round_of_find_middle_adapters(al, n, A):
-    import torch
-    rng = np.random.default_rng(n * 100 + A)
-    Dn = n + 5                                                   # act: a strict subset of the dirty reads
-    recs = middle_records(rng, A * Dn).reshape(A, Dn, 8)
-    thr = [90.0, 66.666667, 200.0 / 3, 33.333333][(n + A) % 4]
-    F = glue_ref.record_fields(recs.reshape(-1, 8))
-    full_all = np.nan_to_num(np.array([f[0] for f in F]), nan=0.0).reshape(A, Dn)
-    failed = recs[:, :, 0] == -1
-    full_all[failed & (rng.random((A, Dn)) < 0.5)] = 100.0          # -1 records whose `full` is at or above the threshold
-    full_all[failed & (rng.random((A, Dn)) < 0.3)] = thr
-    cur = rng.integers(0, A + 1, size=Dn).astype(np.int64)           # cur == A: nothing left to consume
-    last = rng.random(Dn) < 0.2                                      # a hit at the last adapter only
-    recs[:, last, 0] = -1
-    recs[A - 1, last] = [3, 40, 0, 9, 30, 10, 10, 10]
-    full_all[:, last] = 0.0
-    full_all[A - 1, last] = 100.0
-    cur[last] = np.minimum(cur[last], A - 1)
-    act = np.sort(rng.choice(Dn, size=n, replace=False)).astype(np.int64)
-    rng.shuffle(act)
-    anyh, a_hit, cnt, stats = al.round_consume(dev(full_all), dev(recs), dev(cur), dev(act), thr)
-    al.sync()
-    want_h, want_a, want_c, used, amin = [], [], [], 0, None
-    for d in act.tolist():
-        a, m, u = glue_ref.consume(full_all[:, d].tolist(), recs[:, d, 0].tolist(), (recs[:, d, 1] + 1).tolist(), int(cur[d]), thr)
-        want_h.append(a is not None)
-        want_a.append(0 if a is None else a)
-        want_c.append(m)
-        used += u
-        if a is not None:
-            amin = a if amin is None else min(amin, a)
-    assert anyh.cpu().tolist() == want_h
-    assert a_hit.cpu().tolist() == want_a
-    assert cnt.cpu().tolist() == want_c
-    assert stats.cpu().tolist() == [used, sum(want_h), 0 if amin is None else STAT_BIG - amin, sum(want_c)]
-    e = torch.zeros(0, dtype=torch.int64, device="cuda")
-    anyh, a_hit, cnt, stats = al.round_consume(dev(full_all), dev(recs), dev(cur), e, thr)
-    al.sync()
-    assert anyh.numel() == 0 and stats.cpu().tolist() == [0, 0, 0, 0]
+    glue_cases.round_consume_equals_one_round_of_find_middle_adapters(al, dev, n, A, al.sync)
 
 
 @pytest.mark.parametrize("n", SIZES + [0])
 @pytest.mark.parametrize("words", [1, 3])
 def test_group_survivors_equal_the_masked_any(al, n, words):
-    rng = np.random.default_rng(n * 7 + words)
-    G = 5
-    mask = np.where(rng.random((n, words)) < 0.6, 0, rng.integers(-2**31, 2**31, size=(n, words))).astype(np.int32)
-    mask[::9, -1] = np.int32(-2**31)                             # bit 31 alone
-    gm = rng.integers(-2**31, 2**31, size=(G, words)).astype(np.int32)
-    gm[0] = 0
-    gm[1, :] = 0
-    gm[1, -1] = np.int32(-2**31)                                 # bit 31 set: a negative int32, as pipeline.py builds it
-    gm[2] = np.int32(1)
-    cand, counts = al.group_survivors(dev(mask), dev(gm))
-    al.sync()
-    want = np.array([[any(int(mask[w, k]) & int(gm[g, k]) for k in range(words)) for w in range(n)] for g in range(G)],
-                    dtype=bool).reshape(G, n)
-    assert np.array_equal(cand.cpu().numpy(), want)
-    assert counts.cpu().tolist() == want.sum(axis=1).tolist()
-    assert want[1].any() or n < 9
+    glue_cases.group_survivors_equal_the_masked_any(al, dev, n, words, al.sync)
 
 
 # ---- the index plumbing of the pruned phase B (pc_select.hip) -----------------------------------------------------------
