@@ -221,7 +221,9 @@ int pc_floor_skipped(pc_ctx *ctx, void *stream, int64_t *last_call, int64_t *tot
 /* The score pass of pc_scan_device_floored computes the adapter rows that no alignment reaching its pair's floor can reach
  * only behind a column that announces such an alignment (csrc/pc_bounds.h, row_skip_plan): records of pairs at or above
  * their floor, pc_floor_skipped and everything pass 2 sees are what they are without it.  PC_NO_ROW_SKIP=1 in the
- * environment (read per call) switches it off.  A debug switch, off by default: while it is on, every wave of such a launch
+ * environment (read per call) switches it off.  The kernel that does it holds the shorter adapter of a pair of different
+ * lengths top-aligned (row_skip_plan_top); PC_SKIP_LAYOUT=bottom, read when a kernel is first asked for, compiles the
+ * bottom-aligned variant instead (A/B measurements; results are the same).  A debug switch, off by default: while it is on, every wave of such a launch
  * adds, once, two numbers to two counters of the context: the 4-column blocks its fast path ran (`column_pairs`: blocks, the
  * name is historical) and those among them in which the lower rows were computed.  A stretch of blocks entered from the
  * one-column path starts with the lower rows on whatever the reads hold; its blocks are counted only from the first one

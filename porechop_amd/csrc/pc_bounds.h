@@ -238,6 +238,121 @@ inline int row_skip_r0(int match, int mismatch, int gap_open, int gap_extend, in
     return R;
 }
 
+// ---- The same row skip with the shorter adapter TOP-aligned (pc_jit_source.h, PC_TOP) ---------------------------------
+//
+// Setting.  Register row rho = adapter row rho in BOTH halves: a half of m rows fills register rows 1..m, and the rows
+// m + 1..R of the shorter half are padding BELOW it (a letter that scores 0 against everything).  Nothing a real row
+// computes reads a row below it, so the real rows are what they would be without the padding; a padding row is never a
+// candidate end cell and nothing reads it (its values are maxima and sums of real ones and of 0: inside the same range).
+// r0 is an even register row with 2 <= r0 < min(m_lo, m_hi): the last row of BOTH halves lies below r0, so neither half's
+// end cells have to be tracked by the part that runs in every column.  Per half, with m its rows and F its floor,
+//     theta = F - match * (m - r0)                               and it must be > 0 (refused otherwise),
+//     W_low = max over the halves of (m - r0) + floor(max(0, match * m - F) / g).
+// The variant computes rows <= r0 in every column and rows > r0 only in the columns j'' .. j'' + W_low behind a column
+// j'' with M(r0, j'') >= theta in either half.  Call what it computes M^.
+//
+//  1. M^ <= M everywhere, and rows <= r0 are exact: as above, word for word.
+//  2. Every candidate end cell c of a half -- row m at any column, or the last column at a row 1..m -- with M(c) >= F has
+//     M^(c) = M(c).  If c lies in a row <= r0 there is nothing to show.  Otherwise take an optimal path to c; it lies in
+//     rows <= m (paths only ever go down), starts with score 0 in row 0 or in column 0.
+//       (a) It starts in column 0 in a row > r0: then it has at most m - r0 - 1 diagonals and scores at most
+//           match * (m - r0 - 1) < match * (m - r0) < F because theta > 0.  Contradiction.
+//       (b) So it has cells in row r0; let (r0, j'') be the last one.  The prefix up to it scores <= M(r0, j''); the rest
+//           passes at most m - r0 rows, earns at most `match` per row and nothing from gaps, so M(r0, j'') >= F - match *
+//           (m - r0) = theta: column j'' switches the lower rows on.
+//       (c) The step off row r0 is fed from row r0's exact values of columns j'' - 1 and j'', in columns that are on.
+//       (d) Behind column j'' the path has at most m - r0 diagonal steps and h horizontal gap characters with match * m -
+//           g * h >= F, so it ends at a column <= j'' + (m - r0) + floor((match * m - F) / g) <= j'' + W_low.  By
+//           induction along the path M^ of each of its cells is at least the path's score there; with 1, M^(c) = M(c).
+//  3. The consequences, and the chunked launches' lead-in, are those of the bottom-aligned layout.
+// What the layout buys: no padding sits above r0, so all r0 always-on rows are real in both halves, and theta of the
+// short half is F - match * (m_short - r0) instead of F - match * (R - r0) -- out of random sequence's reach in r0 real
+// rows -- so r0 can sit lower at the same share of columns with the lower rows on.
+// For m_lo == m_hi == R the two layouts are one: the plans agree in every field.
+inline RowSkip row_skip_plan_top(int match, int mismatch, int gap_open, int gap_extend, int R, int r0, int m_lo, int m_hi,
+                                 long F_lo, long F_hi)
+{
+    RowSkip p = {false, 0, 0, 0};
+    if (!row_skip_scheme(match, mismatch, gap_open, gap_extend)) return p;
+    if (m_lo < 1 || m_hi < 1 || m_lo > R || m_hi > R || (m_lo != R && m_hi != R)) return p;
+    const int m_min = m_lo < m_hi ? m_lo : m_hi;
+    if (r0 < 2 || (r0 & 1) || r0 >= m_min) return p;                         // both last rows below r0
+    const long t_lo = F_lo - (long)match * (m_lo - r0), t_hi = F_hi - (long)match * (m_hi - r0);
+    if (t_lo <= 0 || t_hi <= 0) return p;                                    // 2 (a): the column-0 condition
+    if (F_lo > (long)match * m_lo || F_hi > (long)match * m_hi) return p;
+    const long g = -gap_open < -gap_extend ? -(long)gap_open : -(long)gap_extend;
+    const long w_lo = (m_lo - r0) + ((long)match * m_lo - F_lo) / g, w_hi = (m_hi - r0) + ((long)match * m_hi - F_hi) / g;
+    const long w = w_lo > w_hi ? w_lo : w_hi;
+    if (w > (1L << 20)) return p;
+    p.ok = true; p.theta_lo = (int)t_lo; p.theta_hi = (int)t_hi; p.w_low = (int)w;
+    return p;
+}
+
+// The rule for r0 in the top-aligned layout.  The closed form of row_skip_r0 counts ungapped prefixes only; with the
+// short half's threshold out of random sequence's reach the long half decides, and there gapped prefixes are some 260
+// times as frequent as ungapped ones at the rows in question (simulated): the closed form answers 14 for the 28 | 22
+// pair, a row at which the lower rows would be on most of the time.  So the rate is MEASURED instead: the plain affine
+// recurrence of each half's first rows (sets_lo / sets_hi: the rows' 5-bit sets over the read codes, pc_letters.h) over
+// kRowSkipSimColumns columns of seeded uniform random bases, counting per candidate row the columns with M(r0, j) >=
+// theta at the nominal floors of a 90 % threshold.  A wave holds 64 lanes and a block is 4 columns: the share of blocks
+// with the lower rows on is modelled as  events per column * 256 * (W_low / 4 + 1),  and the rule takes the smallest even
+// row, at least four above the last register row and with at most kRowSkipMaxLower rows below it, whose share stays under
+// 1 / 32.  A function of the recipe alone (the seed is fixed), and no part of exactness: a bad row costs time only.
+// Measured on the headline (profiles/score_top_layout_before_after.txt).
+constexpr long kRowSkipSimColumns = 1L << 20;
+inline int row_skip_r0_top(int match, int mismatch, int gap_open, int gap_extend, int R, int m_lo, int m_hi,
+                           const unsigned char *sets_lo, const unsigned char *sets_hi)
+{
+    if (!row_skip_scheme(match, mismatch, gap_open, gap_extend) || match == mismatch) return R;
+    if (m_lo < 1 || m_hi < 1 || m_lo > R || m_hi > R || R > MAX_ADAPTER) return R;
+    const long F[2] = {row_skip_nominal_floor(match, mismatch, gap_open, gap_extend, m_lo),
+                       row_skip_nominal_floor(match, mismatch, gap_open, gap_extend, m_hi)};
+    if (F[0] <= 0 || F[1] <= 0) return R;
+    const int m_min = m_lo < m_hi ? m_lo : m_hi;
+    const int first = R - kRowSkipMaxLower > 2 ? (R - kRowSkipMaxLower + 1) / 2 * 2 : 2;
+    int last = (m_min - 1) / 2 * 2;                                          // even, < m_min
+    if (last > R - 4) last = (R - 4) / 2 * 2;
+    if (last < first) return R;
+    long events[MAX_ADAPTER + 1] = {0};
+    bool usable[MAX_ADAPTER + 1] = {false};
+    RowSkip plan[MAX_ADAPTER + 1];
+    bool any = false;
+    for (int r0 = first; r0 <= last; r0 += 2) {
+        plan[r0] = row_skip_plan_top(match, mismatch, gap_open, gap_extend, R, r0, m_lo, m_hi, F[0], F[1]);
+        usable[r0] = plan[r0].ok; any = any || plan[r0].ok;
+    }
+    if (!any) return R;
+    for (int h = 0; h < 2; ++h) {
+        const unsigned char *sets = h ? sets_hi : sets_lo;
+        long theta[MAX_ADAPTER + 1];
+        for (int r0 = first; r0 <= last; r0 += 2) theta[r0] = usable[r0] ? (h ? plan[r0].theta_hi : plan[r0].theta_lo) : (1L << 40);
+        int M[MAX_ADAPTER + 1], H[MAX_ADAPTER + 1];
+        for (int i = 0; i <= last; ++i) { M[i] = 0; H[i] = -(1 << 28); }
+        uint64_t x = 0x9E3779B97F4A7C15ull;                                  // xorshift64*, 32 bases per draw; both halves read the same columns
+        uint64_t bits = 0; int have = 0;
+        for (long j = 0; j < kRowSkipSimColumns; ++j) {
+            if (!have) { x ^= x >> 12; x ^= x << 25; x ^= x >> 27; bits = x * 0x2545F4914F6CDD1Dull; have = 32; }
+            const int code = (int)(bits & 3); bits >>= 2; --have;
+            int diag = 0, upM = 0, upV = -(1 << 28);
+            for (int i = 1; i <= last; ++i) {
+                const int hh = H[i] + gap_extend > M[i] + gap_open ? H[i] + gap_extend : M[i] + gap_open;
+                const int vv = upV + gap_extend > upM + gap_open ? upV + gap_extend : upM + gap_open;
+                int best = diag + (((sets[i - 1] >> code) & 1) ? match : mismatch);
+                if (hh > best) best = hh;
+                if (vv > best) best = vv;
+                diag = M[i]; M[i] = best; H[i] = hh; upM = best; upV = vv;
+            }
+            for (int r0 = first; r0 <= last; r0 += 2) events[r0] += M[r0] >= theta[r0];
+        }
+    }
+    for (int r0 = first; r0 <= last; r0 += 2) {
+        if (!usable[r0]) continue;
+        const double share = (double)events[r0] / (double)kRowSkipSimColumns * 256.0 * (plan[r0].w_low / 4 + 1);
+        if (share <= 1.0 / 32) return r0;
+    }
+    return R;
+}
+
 // PC_JIT_R0 (measurements): the row the environment asks for in place of row_skip_r0's, for the pair of adapters of m_a and m_b
 // bases.  "20": that row for every pair.  "28|22:20,33|30:22": a row per pair, named by both of its lengths in either order; a
 // pair that is not listed keeps rule_r0.  Anything else -- an empty entry, a missing part, a stray character -- sets *malformed

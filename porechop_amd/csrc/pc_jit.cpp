@@ -107,7 +107,7 @@ struct Entry {
     std::atomic<bool> compile_done{false};
     std::thread worker;
     int R = 0, K = 0, m_lo = 0, m_hi = 0, waves = 2, r0 = 0;
-    bool f16 = false;
+    bool f16 = false, top = false;
     long kren = 0;
 };
 
@@ -133,28 +133,127 @@ struct Derived {
     std::vector<std::string> opts;
     std::vector<int> combos;
     int K = 0, waves = 2, r0 = 0;
+    bool top = false;                          // the row-skipping variant with the shorter adapter top-aligned (pc_bounds.h row_skip_plan_top)
 };
 
 constexpr int kPadLetter = 32, kLetters = 33;    // a letter is a 5-bit set, or the padding row
+
+// the row rule of the top-aligned layout simulates (pcb::row_skip_r0_top: a quarter of a second): once per recipe and process
+int top_rule_r0(const Recipe &rc)
+{
+    static std::mutex mu;
+    static std::map<std::string, int> memo;
+    char buf[96];
+    snprintf(buf, sizeof buf, "|%d,%d,%d,%d|%d", rc.match, rc.mismatch, rc.gap_open, rc.gap_extend, rc.wildcards ? 1 : 0);
+    const std::string key = rc.ad_lo + "|" + rc.ad_hi + buf;
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = memo.find(key);
+    if (it != memo.end()) return it->second;
+    unsigned char sl[pcb::MAX_ADAPTER], sh[pcb::MAX_ADAPTER];
+    for (int i = 0; i < rc.m_lo; ++i) sl[i] = (unsigned char)pcl::letter_set((uint8_t)rc.ad_lo[i], rc.wildcards);
+    for (int i = 0; i < rc.m_hi; ++i) sh[i] = (unsigned char)pcl::letter_set((uint8_t)rc.ad_hi[i], rc.wildcards);
+    const int r0 = pcb::row_skip_r0_top(rc.match, rc.mismatch, rc.gap_open, rc.gap_extend, rc.R, rc.m_lo, rc.m_hi, sl, sh);
+    memo[key] = r0;
+    return r0;
+}
 
 Derived derive(const Recipe &rc)
 {
     Derived d;
     const int R = rc.R;
-    // letters per register row of each half (bottom-aligned): the row's set of read codes (pc_letters.h: one code without
-    // wildcards, so rows are told apart exactly as their Dna5 codes were and the options of such adapters are what they have
-    // always been), kPadLetter = padding row
-    std::vector<int> lo(R, kPadLetter), hi(R, kPadLetter);
+    const char *chk = getenv("PC_JIT_CHECK_RANGE");
+    const bool check_range = chk && *chk && *chk != '0';
+    // the distinct letter pairs of the rows, numbered in row order (pc_letters.h: one code without wildcards, so rows are told
+    // apart exactly as their Dna5 codes were and the options of such adapters are what they have always been)
+    auto number_rows = [&](const std::vector<int> &lo, const std::vector<int> &hi, std::vector<int> &combo_of_row) {
+        d.combos.clear();
+        combo_of_row.assign(R, 0);
+        for (int row = 0; row < R; ++row) {
+            const int c = lo[row] * kLetters + hi[row];
+            int k = -1;
+            for (size_t i = 0; i < d.combos.size(); ++i) if (d.combos[i] == c) k = (int)i;
+            if (k < 0) { k = (int)d.combos.size(); d.combos.push_back(c); }
+            combo_of_row[row] = k;
+        }
+    };
+    auto options = [&](const std::vector<int> &combo_of_row, int K, int waves) {
+        std::string init;
+        for (int row = 0; row < R; ++row) { init += std::to_string(combo_of_row[row]); if (row + 1 < R) init += ","; }
+        d.opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
+                  "-DPC_R=" + std::to_string(R), "-DPC_K=" + std::to_string(K), "-DPC_COMBO_INIT=" + init,
+                  std::string("-DPC_F16=") + (rc.f16 ? "1" : "0"), "-DPC_EPS=" + std::to_string(rc.eps),
+                  "-DPC_OE=(" + std::to_string(rc.gap_open + rc.eps) + ")", "-DPC_CEN=(" + std::to_string(rc.cen) + ")",
+                  "-DPC_KREN=" + std::to_string(rc.kren),
+                  std::string("-DPC_WAVES=") + (getenv("PC_JIT_WAVES") ? getenv("PC_JIT_WAVES") : std::to_string(waves)),
+                  std::string("-DPC_CHECK_RANGE=") + (check_range ? "1" : "0"),
+                  std::string("-DPC_DUAL=") + (rc.ad_lo != rc.ad_hi ? "1" : "0")};
+    };
+    // PC_JIT_R0 overrides a rule's row (measurements): one row for every pair ("20") or a row per pair ("28|22:20,33|30:22"),
+    // pcb::row_skip_r0_override; a malformed text is ignored, a row the layout cannot use means no variant (R)
+    auto overridden = [&](int rule_r0, auto usable) {
+        const char *e = getenv("PC_JIT_R0");
+        if (!e) return rule_r0;
+        bool malformed = false;
+        const int v = pcb::row_skip_r0_override(e, rc.m_lo, rc.m_hi, rule_r0, &malformed);
+        if (malformed) {
+            static std::atomic<bool> said{false};
+            if (!said.exchange(true)) fprintf(stderr, "porechop_amd: PC_JIT_R0=%s is not a row or a list of LEN|LEN:ROW entries; ignored\n", e);
+            return rule_r0;
+        }
+        return v == rule_r0 ? rule_r0 : (usable(v) ? v : R);
+    };
+    // the kernel's LDS (tables, three look-up tables, 512 bytes per lower row) times the twelve workgroups of a CU at three
+    // waves per SIMD must fit its 160 KiB, or the variant would run at a lower occupancy than the plain kernel: then none
+    auto lds_fits = [&](int K, int r0) { return 12L * (100L * K + 1536 + 512L * (R - r0)) <= 160L * 1024; };
+
+    // ---- The row-skipping variant of a pair of DIFFERENT lengths: the shorter adapter top-aligned (pc_bounds.h row_skip_plan_top),
+    // register row = adapter row in both halves, the padding letter below the shorter one.  No padding sits above the row the
+    // fast path tests, which lets that row sit lower.  The rows are numbered in row order, so the letter pairs of the rows
+    // above r0 are the first ones: the fast path fetches only the first PC_KUP terms of a column (the lower part and the
+    // one-column path read the full row), and it is the fast path's registers -- T, U and four sets of PC_KUP terms -- that
+    // decide the waves.  Three-wave kernels only, as below.  PC_SKIP_LAYOUT=bottom compiles the bottom-aligned variant
+    // instead (A/B runs: the options differ, so the caches keep both).  A pair whose top-aligned variant has no row by the
+    // rule, or no room, gets the bottom-aligned one if that has.  Not so under PC_JIT_R0: a row asked for in its place that
+    // this layout cannot use or has no room for means NO variant (the plain kernel runs), never the other layout at that
+    // row -- a measurement must not be of a layout it did not ask for.
+    // (No room whatever the row -- K_up >= 4, so 2R + 16 > 120 -- is found before the rule's simulation is paid for.)
+    const char *layout = getenv("PC_SKIP_LAYOUT");
+    bool no_variant = false;
+    if (rc.row_skip && rc.f16 && !check_range && rc.m_lo != rc.m_hi && 2 * R + 16 <= 120 && !(layout && !strcmp(layout, "bottom"))) {
+        std::vector<int> lo(R, kPadLetter), hi(R, kPadLetter), combo_of_row;
+        for (int i = 0; i < rc.m_lo; ++i) lo[i] = (int)pcl::letter_set((uint8_t)rc.ad_lo[i], rc.wildcards);
+        for (int i = 0; i < rc.m_hi; ++i) hi[i] = (int)pcl::letter_set((uint8_t)rc.ad_hi[i], rc.wildcards);
+        number_rows(lo, hi, combo_of_row);
+        const int K = ((int)d.combos.size() + 3) / 4 * 4;
+        const int m_min = std::min(rc.m_lo, rc.m_hi);
+        const int rule_r0 = top_rule_r0(rc);
+        const int r0 = overridden(rule_r0, [&](int v) { return v >= 2 && !(v & 1) && v < m_min; });
+        if (const char *e = getenv("PC_JIT_R0")) {           // a row asked for for this pair: this layout at that row, or nothing
+            bool malformed = false;
+            no_variant = pcb::row_skip_r0_override(e, rc.m_lo, rc.m_hi, -1, &malformed) != -1;
+        }
+        if (r0 < R) {
+            int k_up = 0;
+            for (int row = 0; row < r0; ++row) k_up = std::max(k_up, combo_of_row[row] + 1);
+            k_up = (k_up + 3) / 4 * 4;
+            if (2 * R + 4 * k_up <= 120 && lds_fits(K, r0)) {
+                d.K = K; d.waves = 3; d.r0 = r0; d.top = true;
+                options(combo_of_row, K, 3);
+                d.opts.push_back("-DPC_R0=" + std::to_string(r0));
+                d.opts.push_back("-DPC_TOP=1");
+                d.opts.push_back("-DPC_MLO=" + std::to_string(rc.m_lo));
+                d.opts.push_back("-DPC_MHI=" + std::to_string(rc.m_hi));
+                d.opts.push_back("-DPC_KUP=" + std::to_string(k_up));
+                return d;
+            }
+        }
+    }
+
+    // letters per register row of each half (bottom-aligned), kPadLetter = padding row
+    std::vector<int> lo(R, kPadLetter), hi(R, kPadLetter), combo_of_row;
     for (int i = 0; i < rc.m_lo; ++i) lo[R - rc.m_lo + i] = (int)pcl::letter_set((uint8_t)rc.ad_lo[i], rc.wildcards);
     for (int i = 0; i < rc.m_hi; ++i) hi[R - rc.m_hi + i] = (int)pcl::letter_set((uint8_t)rc.ad_hi[i], rc.wildcards);
-    std::vector<int> combo_of_row(R);
-    for (int row = 0; row < R; ++row) {
-        const int c = lo[row] * kLetters + hi[row];
-        int k = -1;
-        for (size_t i = 0; i < d.combos.size(); ++i) if (d.combos[i] == c) k = (int)i;
-        if (k < 0) { k = (int)d.combos.size(); d.combos.push_back(c); }
-        combo_of_row[row] = k;
-    }
+    number_rows(lo, hi, combo_of_row);
     const int K = ((int)d.combos.size() + 3) / 4 * 4;
     // Register budget: T, U and four sets of substitution terms (two columns in flight, two being
     // fetched) = 2R + 4K, plus ~50 of bookkeeping.  Up to 120 the column loop fits 168 VGPRs -- three waves
@@ -165,40 +264,18 @@ Derived derive(const Recipe &rc)
     // several times faster than the generic kernel's column in LDS.
     const int waves = (2 * R + 4 * K <= 120) ? 3 : (2 * R + 4 * K <= 140) ? 2 : 1;
     d.K = K; d.waves = waves;
-    std::string init;
-    for (int row = 0; row < R; ++row) { init += std::to_string(combo_of_row[row]); if (row + 1 < R) init += ","; }
-    const char *chk = getenv("PC_JIT_CHECK_RANGE");
-    const bool check_range = chk && *chk && *chk != '0';
     // the row its row-skipping fast path tests (pc_bounds.h): packed fp16 only, and not in the range-recording build, which
     // takes the one-column path throughout.  Three-wave kernels only: the longer pairs' kernels (two waves, or one with rows
     // parked in AGPRs) have no room for the lower part beside their rows, and their few workgroups per CU would pay for the
     // lower rows' LDS with occupancy.  PC_JIT_R0 overrides the rule (measurements; an unusable row means none)
-    const bool may_skip = rc.row_skip && rc.f16 && !check_range && waves == 3;
+    const bool may_skip = rc.row_skip && rc.f16 && !check_range && waves == 3 && !no_variant;
     d.r0 = may_skip ? pcb::row_skip_r0(rc.match, rc.mismatch, rc.gap_open, rc.gap_extend, R, rc.m_lo, rc.m_hi) : R;
-    if (const char *e = getenv("PC_JIT_R0")) {
-        // one row for every pair ("20") or a row per pair ("28|22:20,33|30:22"): pcb::row_skip_r0_override
-        bool malformed = false;
-        const int rule_r0 = d.r0;
-        const int v = pcb::row_skip_r0_override(e, rc.m_lo, rc.m_hi, rule_r0, &malformed);
+    if (may_skip) {
         const int pad = R - std::min(rc.m_lo, rc.m_hi);
-        if (malformed) {
-            static std::atomic<bool> said{false};
-            if (!said.exchange(true)) fprintf(stderr, "porechop_amd: PC_JIT_R0=%s is not a row or a list of LEN|LEN:ROW entries; ignored\n", e);
-        } else if (may_skip && v != rule_r0) {
-            d.r0 = (v >= 2 && !(v & 1) && v < R && v > pad) ? v : R;
-        }
+        d.r0 = overridden(d.r0, [&](int v) { return v >= 2 && !(v & 1) && v < R && v > pad; });
     }
-    // the kernel's LDS (tables, three look-up tables, 512 bytes per lower row) times the twelve workgroups of a CU at three
-    // waves per SIMD must fit its 160 KiB, or the variant would run at a lower occupancy than the plain kernel: then none
-    if (d.r0 < R && 12L * (100L * K + 1536 + 512L * (R - d.r0)) > 160L * 1024) d.r0 = R;
-    d.opts = {"--offload-arch=gfx950", "-O3", "-std=c++17",
-              "-DPC_R=" + std::to_string(R), "-DPC_K=" + std::to_string(K), "-DPC_COMBO_INIT=" + init,
-              std::string("-DPC_F16=") + (rc.f16 ? "1" : "0"), "-DPC_EPS=" + std::to_string(rc.eps),
-              "-DPC_OE=(" + std::to_string(rc.gap_open + rc.eps) + ")", "-DPC_CEN=(" + std::to_string(rc.cen) + ")",
-              "-DPC_KREN=" + std::to_string(rc.kren),
-              std::string("-DPC_WAVES=") + (getenv("PC_JIT_WAVES") ? getenv("PC_JIT_WAVES") : std::to_string(waves)),
-              std::string("-DPC_CHECK_RANGE=") + (check_range ? "1" : "0"),
-              std::string("-DPC_DUAL=") + (rc.ad_lo != rc.ad_hi ? "1" : "0")};
+    if (d.r0 < R && !lds_fits(K, d.r0)) d.r0 = R;
+    options(combo_of_row, K, waves);
     if (d.r0 < R) d.opts.push_back("-DPC_R0=" + std::to_string(d.r0));        // (the plain kernel's options are what they were)
     return d;
 }
@@ -391,7 +468,7 @@ bool hiprtc_compile(const std::vector<std::string> &opts, std::vector<char> &cod
 
 void fill_entry(Entry *e, const Recipe &rc, const Derived &d)
 {
-    e->R = rc.R; e->K = d.K; e->m_lo = rc.m_lo; e->m_hi = rc.m_hi; e->f16 = rc.f16; e->waves = d.waves; e->r0 = d.r0; e->kren = rc.kren;
+    e->R = rc.R; e->K = d.K; e->m_lo = rc.m_lo; e->m_hi = rc.m_hi; e->f16 = rc.f16; e->waves = d.waves; e->r0 = d.r0; e->top = d.top; e->kren = rc.kren;
     e->table = substitution_table(rc, d);           // empty: a table term outside the lane type's exact range (never expected)
 }
 
@@ -438,7 +515,7 @@ void finalize_entry(Entry *e, bool verbose)
         return;
     }
     Spec *sp = new Spec();
-    sp->R = e->R; sp->K = e->K; sp->m_lo = e->m_lo; sp->m_hi = e->m_hi; sp->f16 = e->f16; sp->waves = e->waves; sp->r0 = e->r0;
+    sp->R = e->R; sp->K = e->K; sp->m_lo = e->m_lo; sp->m_hi = e->m_hi; sp->f16 = e->f16; sp->waves = e->waves; sp->r0 = e->r0; sp->top = e->top;
     hipModule_t mod = nullptr;
     hipFunction_t fn = nullptr;
     if (hipModuleLoadData(&mod, e->code.data()) != hipSuccess || hipModuleGetFunction(&fn, mod, "pc_spec_score") != hipSuccess) {
@@ -619,7 +696,9 @@ bool row_skip_args(const Spec *sp, int match, int mismatch, int gap_open, int ga
 {
     a.skip_thr2 = 0; a.skip_w = 0;
     if (!sp || !sp->f16 || sp->r0 <= 0 || sp->r0 >= sp->R || floor_lo == INT32_MIN || floor_hi == INT32_MIN) return false;
-    const pcb::RowSkip p = pcb::row_skip_plan(match, mismatch, gap_open, gap_extend, sp->R, sp->r0, sp->m_lo, sp->m_hi, floor_lo, floor_hi);
+    // (thresholds and window of the layout the kernel was compiled with)
+    const pcb::RowSkip p = sp->top ? pcb::row_skip_plan_top(match, mismatch, gap_open, gap_extend, sp->R, sp->r0, sp->m_lo, sp->m_hi, floor_lo, floor_hi)
+                                   : pcb::row_skip_plan(match, mismatch, gap_open, gap_extend, sp->R, sp->r0, sp->m_lo, sp->m_hi, floor_lo, floor_hi);
     if (!p.ok) return false;
     // what M(r0, j) + r0 * eps must exceed: an integer of magnitude <= match * m + R * eps, exact in fp16 by spec_plan's gate
     const int eps = -gap_extend;

@@ -12,6 +12,7 @@ struct Spec {
     int R = 0, K = 0, m_lo = 0, m_hi = 0;
     int waves = 2;               // resident waves per SIMD the register allocation is asked to allow
     int r0 = 0;                  // the row-skipping variant: the register row it tests (pcb::row_skip_r0), < R; the plain kernel: R
+    bool top = false;            // the row-skipping variant's layout: the shorter adapter top-aligned (pcb::row_skip_plan_top), else bottom-aligned
     int blocks_per_cu = 8;       // resident 64-thread workgroups per CU (runtime occupancy query: registers and LDS)
     bool f16 = false;            // packed-fp16 variant (5 ops per cell pair) vs packed-int16 (6)
     void *module = nullptr, *function = nullptr;

@@ -57,10 +57,33 @@ namespace pcj {
 // defines prepended by pc_jit.cpp: PC_DUAL (1: the two adapters differ), PC_R, PC_K (multiple of 4), PC_COMBO_INIT (R comma-separated
 // ints), PC_F16, PC_EPS (= -gap_extend), PC_OE (= gap_open + PC_EPS), PC_CEN (C), PC_KREN,
 // PC_WAVES (resident waves per SIMD the register allocation must allow), PC_CHECK_RANGE (0/1); the row-skipping variant
-// of a pair (a kernel of its own: pc_bounds.h row_skip_plan) also gets PC_R0, the register row it tests
+// of a pair (a kernel of its own: pc_bounds.h row_skip_plan) also gets PC_R0, the register row it tests.
+// PC_TOP=1 (with PC_MLO, PC_MHI, PC_KUP; only ever together with PC_R0): the row-skipping variant of a pair of different
+// lengths, the shorter adapter TOP-aligned (pc_bounds.h row_skip_plan_top).  Register row = adapter row in both halves:
+//   * column 0's lower-bound state "row-0 start + vertical gap" counts its rows from register row 1 in both halves;
+//   * the tracked last row of a half is register row m_h -- PC_MLO / PC_MHI, compile-time constants, both below PC_R0 -- so the
+//     tracked term is M(m_h, j) + m_h * eps, a packed select of two rows, formed by the one-column path and, while the lower
+//     rows are on, by lower_block; packbest / unpack_best and every candidate term take m_h * eps per half;
+//   * the last column's candidates are register rows 1 .. m_h of each half and never a row below m_h: the padding rows
+//     below the shorter adapter hold real numbers (their letter scores 0 against everything, so they carry the maximum of
+//     what lies above and to the left on), which may well exceed the real rows' -- nothing reads them, nothing takes them;
+//   * those numbers stay inside spec_plan's range gate: a padding cell's M is at most the largest M of the real rows (0 is
+//     added on the diagonal, gaps only cost), so <= match * R like every cell, and at least the in-column alternative "row-0
+//     start + vertical gap" every cell has, which is what the gate's lower end is made of (the diagonal term 0 is >= the
+//     gate's open + ext for a rewarded mismatch, >= mismatch otherwise); its register row is <= R like every row's;
+//   * the rows above PC_R0 use the first PC_KUP letter pairs only (pc_jit.cpp numbers them in row order): the fast path
+//     fetches PC_KUP terms per column, the lower part and the one-column path read the full row.
 static const char *kSpecSource = R"PCJIT(
 typedef unsigned int u32;
 typedef long long i64;
+#ifndef PC_TOP
+#define PC_TOP 0
+#endif
+#if !PC_TOP
+#define PC_MLO PC_R
+#define PC_MHI PC_R
+#define PC_KUP PC_K
+#endif
 #if PC_F16
 // Packed FP16: every value formed is an integer with |v| <= 2048 (host-side gate), which fp16
 // holds and adds exactly; -infinity is the real one.
@@ -103,10 +126,10 @@ __device__ __forceinline__ u32 WV16(u16x2 x) { return __builtin_bit_cast(u32, x)
 __device__ __forceinline__ u32 pk_minu(u32 a, u32 b) { return WV16(__builtin_elementwise_min(UV16(a), UV16(b))); }
 __device__ __forceinline__ u32 pk_subu(u32 a, u32 b) { return WV16(UV16(a) - UV16(b)); }
 __device__ __forceinline__ u32 pk_madu(u32 a, u32 k, u32 c) { return WV16(UV16(a) * UV16(k) + UV16(c)); }
-// packed "best so far" in the tracked-score domain (score + R*eps); the chunk>0 sentinel maps to -inf
+// packed "best so far" in the tracked-score domain (score + R*eps; top-aligned: + m*eps of each half); the chunk>0 sentinel maps to -inf
 __device__ __forceinline__ u32 packbest(int l, int h)
 {
-    const u32 v = pack2x(l > -20000 ? l + PC_R * PC_EPS : 0, h > -20000 ? h + PC_R * PC_EPS : 0);
+    const u32 v = pack2x(l > -20000 ? l + PC_MLO * PC_EPS : 0, h > -20000 ? h + PC_MHI * PC_EPS : 0);
     return (l > -20000 ? (v & 0xFFFFu) : (PC_NEGBITS & 0xFFFFu)) | (h > -20000 ? (v & 0xFFFF0000u) : (PC_NEGBITS & 0xFFFF0000u));
 }
 
@@ -173,7 +196,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
     }
     __syncthreads();
     const u32 OE2 = pack2(PC_OE), EPS2 = pack2(PC_EPS), NEG2 = PC_NEGBITS;
-    const int pad_lo = R - a.m_lo, pad_hi = R - a.m_hi;
+    const int pad_lo = PC_TOP ? 0 : R - a.m_lo, pad_hi = PC_TOP ? 0 : R - a.m_hi;   // (top-aligned: no padding above)
     // previous-column state of the lanes whose read ends (one region per half: in a tile of two read
     // streams the halves of a lane end in different columns)
     uint2 *fin = a.fin_scratch + (i64)blockIdx.x * 2 * R * 64;
@@ -250,8 +273,8 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         u32 pos2 = ((u32)bj_lo & 0xFFFFu) | ((u32)bj_hi << 16);
         bool packed_ahead = false;                          // wave-uniform: (best2, pos2) are newer than (bs, bj)
         auto unpack_best = [&]() {
-            bs_lo = ((best2 & 0xFFFFu) == (PC_NEGBITS & 0xFFFFu)) ? -32768 : lo16(best2) - R * PC_EPS;
-            bs_hi = ((best2 >> 16) == (PC_NEGBITS >> 16)) ? -32768 : hi16(best2) - R * PC_EPS;
+            bs_lo = ((best2 & 0xFFFFu) == (PC_NEGBITS & 0xFFFFu)) ? -32768 : lo16(best2) - PC_MLO * PC_EPS;
+            bs_hi = ((best2 >> 16) == (PC_NEGBITS >> 16)) ? -32768 : hi16(best2) - PC_MHI * PC_EPS;
             bj_lo = ((pos2 & 0xFFFFu) == 0xFFFFu) ? -1 : (int)(pos2 & 0xFFFFu);
             bj_hi = ((pos2 >> 16) == 0xFFFFu) ? -1 : (int)(pos2 >> 16);
             bi_lo = a.m_lo; bi_hi = a.m_hi;                 // every cell tracked inside the column loop is a last-row cell
@@ -311,15 +334,19 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #else
 #define PC_NOTE_V(x)
 #endif
-        auto fetch_S = [&](u32 (&S)[K], u32 bl, u32 bh) {
+        auto fetch_Sn = [&](auto up, u32 (&S)[K], u32 bl, u32 bh) {
+            constexpr bool UP = decltype(up)::fast;
 #if PC_DUAL
             const uint4 *row = (const uint4 *)((const char *)s_tab + (u32)lut_one[bl]);
 #else
             const uint4 *row = (const uint4 *)((const char *)s_tab + ((u32)lut_lo[bl] + (u32)lut_hi[one_stream ? bl : bh]));
 #endif
 #pragma clang loop unroll(full)
-            for (int q = 0; q < K / 4; ++q) { const uint4 v = row[q]; S[4*q] = v.x; S[4*q+1] = v.y; S[4*q+2] = v.z; S[4*q+3] = v.w; }
+            for (int q = 0; q < (UP ? PC_KUP : K) / 4; ++q) { const uint4 v = row[q]; S[4*q] = v.x; S[4*q+1] = v.y; S[4*q+2] = v.z; S[4*q+3] = v.w; }
         };
+        auto fetch_S = [&](u32 (&S)[K], u32 bl, u32 bh) { fetch_Sn(SlowT{}, S, bl, bh); };
+        // the terms of the rows above r0 only (row skip, top-aligned: the first PC_KUP letter pairs)
+        auto fetch_S_up = [&](u32 (&S)[K], u32 bl, u32 bh) { fetch_Sn(FastT{}, S, bl, bh); };
         // One column.  Returns the tracked last-row term T~(R,j) - top(j) = M(R,j) + R*eps.
         // FastT: every stream of the tile tracks this column and none ends in it (the caller
         // resolves maxima per 4-column block); SlowT: per-stream masks, last-column handling.
@@ -440,10 +467,14 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #undef PC_ROW_FULL
 #undef PC_ROW_TAIL
             }
+#if PC_TOP
+            const u32 cand = pk_sub((T[PC_MLO - 1] & 0xFFFFu) | (T[PC_MHI - 1] & 0xFFFF0000u), topn);   // each half's own last row
+#else
             const u32 cand = pk_sub(T[R - 1], topn);
+#endif
             PC_NOTE_V(cand) PC_NOTE_V(topn)
             if constexpr (!FAST) {
-                const int cl = lo16(cand) - R * PC_EPS, ch = hi16(cand) - R * PC_EPS;
+                const int cl = lo16(cand) - PC_MLO * PC_EPS, ch = hi16(cand) - PC_MHI * PC_EPS;
                 const bool tr_lo = j > tf_lo && (tail_lo ? j < n_lo : j <= n_lo);
                 const bool tr_hi = j > tf_hi && (tail_hi ? j < n_hi : j <= n_hi);
                 if (tr_lo && cl > bs_lo) { bs_lo = cl; bi_lo = a.m_lo; bj_lo = j; }
@@ -778,7 +809,7 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
             } else {                                                  // columns beyond u16: the plain way
 #pragma clang loop unroll(full)
                 for (int k = 0; k < NC; ++k) {
-                    const int cl = lo16(cs[k]) - R * PC_EPS, ch = hi16(cs[k]) - R * PC_EPS;
+                    const int cl = lo16(cs[k]) - PC_MLO * PC_EPS, ch = hi16(cs[k]) - PC_MHI * PC_EPS;
                     if (cl > bs_lo) { bs_lo = cl; bi_lo = a.m_lo; bj_lo = jb + k; }
                     if (ch > bs_hi) { bs_hi = ch; bi_hi = a.m_hi; bj_hi = jb + k; }
                 }
@@ -804,7 +835,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
         int count_from = 0x7FFFFFFF;
         // the rows below r0 over the block's four columns, one pass over the rows: column k's diagonal term of the first of them
         // comes from dg[k] = T~(r0, j0 + k - 1), its V from vv[k] = V~(r0 + 1, j0 + k); the substitution terms are read from
-        // the table again (this is the rare part: the column pairs' four sets need not stay in registers for it)
+        // the table again (this is the rare part: the column pairs' four sets need not stay in registers for it).
+        // Top-aligned, the rows below the shorter adapter's last one are padding in its half: they are computed and stored
+        // all the same, because the other half of the same packed registers is the longer adapter's real rows.
         auto lower_block = [&](u32 (&dg)[4], u32 (&vv)[4], u32 (&cs)[4]) {
             const char *srow[4];
 #pragma clang loop unroll(full)
@@ -818,6 +851,10 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #endif
             }
             u32 t[4] = {NEG2, NEG2, NEG2, NEG2};
+#if PC_TOP
+            u32 t_lo[4] = {NEG2, NEG2, NEG2, NEG2};                                   // T~(m_lo, .): the low half's own last row
+            static_assert(PC_MLO > (PC_R0) && PC_MHI > (PC_R0) && (PC_MLO == PC_R || PC_MHI == PC_R), "both last rows lie below r0");
+#endif
 #pragma clang loop unroll(full)
             for (int r = PC_R0; r < R; ++r) {
                 const uint2 tu = s_low[(r - PC_R0) * 64 + lane];
@@ -830,10 +867,19 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                     tl = pk_add(pk_maxq(pk_maxq(pk_add(dg[k], sk), h), vv[k]), OE2);  // T~(r, j0 + k)
                     vv[k] = pk_maxq(vv[k], tl);
                     dg[k] = dnext;
+#if PC_TOP
+                    if (r == PC_MLO - 1) t_lo[k] = tl;
+                    if (r == PC_MHI - 1) t[k] = tl;
+#else
                     t[k] = tl;
+#endif
                 }
                 s_low[(r - PC_R0) * 64 + lane] = make_uint2(tl, h);                   // U = H~(r, j0 + 3): the one-column convention
             }
+#if PC_TOP
+#pragma clang loop unroll(full)
+            for (int k = 0; k < 4; ++k) t[k] = (t_lo[k] & 0xFFFFu) | (t[k] & 0xFFFF0000u);   // the tracked term of each half: one packed select
+#endif
             u32 tk = top;                                     // (top is T~(0, j0 + 3) now)
 #pragma clang loop unroll(full)
             for (int k = 3; k >= 0; --k) { cs[k] = pk_sub(t[k], tk); tk = pk_sub(tk, EPS2); }
@@ -883,14 +929,14 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 for (;;) {
                     // (three sets of substitution terms in flight, not four; row r0's interface of the first column pair
                     // stays in registers over the second)
-                    fetch_S(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
-                    fetch_S(SC, (cur_lo >> 16) & 0xFF, (cur_hi >> 16) & 0xFF);
+                    fetch_S_up(SB, (cur_lo >> 8) & 0xFF, (cur_hi >> 8) & 0xFF);
+                    fetch_S_up(SC, (cur_lo >> 16) & 0xFF, (cur_hi >> 16) & 0xFF);
                     const u32 tprev = T[PC_R0 - 1];           // T~(r0, j0 - 1)
                     u32 t0, t1, t2, t3;                       // M(r0, .) + r0 * eps of the four columns
                     column2(RowsT<PC_R0>{}, SA, SB, t0, t1);
                     const u32 p_x0 = if_x0, p_x1 = if_x1, p_va = if_va, p_vb = if_vb, p_m0 = T[PC_R0 - 2], p_m1 = T[PC_R0 - 1];
-                    fetch_S(SD, cur_lo >> 24, cur_hi >> 24);
-                    fetch_S(SA, nxt_lo & 0xFF, nxt_hi & 0xFF);
+                    fetch_S_up(SD, cur_lo >> 24, cur_hi >> 24);
+                    fetch_S_up(SA, nxt_lo & 0xFF, nxt_hi & 0xFF);
                     column2(RowsT<PC_R0>{}, SC, SD, t2, t3);
                     const u32 tr = pk_max(pk_max(pk_max(t0, t1), pk_max(t2, t3)), a.skip_thr2);
                     if (__any(tr != a.skip_thr2)) { low_until = j0 + 3 + skip_w; if (j0 < count_from) count_from = j0; }
@@ -937,6 +983,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
                 for (int r = PC_R0; r < R; ++r) { const uint2 tu = s_low[(r - PC_R0) * 64 + lane]; T[r] = tu.x; U[r] = tu.y; }
                 if (count_from < j0) n_pair += (u32)(j0 - count_from) / 4;
                 if (j0 > nmax) break;
+#if PC_KUP < PC_K
+                fetch_S(SA, cur_lo & 0xFF, cur_hi & 0xFF);    // the one-column path reads the full row
+#endif
                 block_head(j0);
             }
             {
@@ -1006,8 +1055,9 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #endif
                 const int il = r - pad_lo + 1, ih = r - pad_hi + 1;
                 const int cl = lo16(c) - (r + 1) * PC_EPS, ch = hi16(c) - (r + 1) * PC_EPS;
-                if (have_lo && il >= 1 && cl > bs_lo) { bs_lo = cl; bi_lo = il; bj_lo = n_lo; }
-                if (have_hi && ih >= 1 && ch > bs_hi) { bs_hi = ch; bi_hi = ih; bj_hi = n_hi; }
+                // (top-aligned: rows 1 .. m of each half, never a padding row below -- elsewhere r < R says nothing)
+                if (have_lo && il >= 1 && r < PC_MLO && cl > bs_lo) { bs_lo = cl; bi_lo = il; bj_lo = n_lo; }
+                if (have_hi && ih >= 1 && r < PC_MHI && ch > bs_hi) { bs_hi = ch; bi_hi = ih; bj_hi = n_hi; }
             }
         } else {
             const bool ev_lo = have_lo && tail_lo && n_lo > 0, ev_hi = have_hi && tail_hi && n_hi > 0;
@@ -1039,8 +1089,8 @@ extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P
 #endif
                     const int il = r - pad_lo + 1, ih = r - pad_hi + 1;
                     const int cl = lo16(c) - (r + 1) * PC_EPS, ch = hi16(c) - (r + 1) * PC_EPS;
-                    if (ev_lo && il >= 1 && cl > bs_lo) { bs_lo = cl; bi_lo = il; bj_lo = n_lo; }
-                    if (ev_hi && ih >= 1 && ch > bs_hi) { bs_hi = ch; bi_hi = ih; bj_hi = n_hi; }
+                    if (ev_lo && il >= 1 && r < PC_MLO && cl > bs_lo) { bs_lo = cl; bi_lo = il; bj_lo = n_lo; }
+                    if (ev_hi && ih >= 1 && r < PC_MHI && ch > bs_hi) { bs_hi = ch; bi_hi = ih; bj_hi = n_hi; }
                 }
             }
         }

@@ -2,7 +2,8 @@
 """Resource and fast-block census of EVERY packed-fp16 specialised score kernel of a kernel cache, without a GPU: each
 kernel is recompiled to a listing (hipcc -S) from the given pc_jit_source.h with the options its cache file records; the
 block-resolved (fast) block is the basic block with the most v_pk_maximum3_f16.  One line per kernel: the row its row-skipping
-fast path tests (r0 = R: the plain kernel), registers, scratch, LDS, occupancy (the compiler's, which counts LDS in), and the
+fast path tests (r0 = R: the plain kernel), its layout (top = 1: the shorter adapter top-aligned, with the K_up terms its
+fast path fetches per column; else K_up = K), registers, scratch, LDS, occupancy (the compiler's, which counts LDS in), and the
 block's VALU instructions, scratch instructions, register moves and s_nops.
    python tools/panel_isa.py [porechop_amd/csrc/pc_jit_source.h [porechop_amd/kernel_cache]] > panel.txt"""
 import os, re, shutil, subprocess, sys, collections, tempfile
@@ -40,7 +41,7 @@ def run(defs):
     c = collections.Counter(i.split()[0] for i in best[1])
     g = lambda k: int(re.search(r'; %s: (\d+)' % k, out).group(1))
     d = dict(x[2:].split('=', 1) for x in defs)
-    return (int(d['PC_R']), int(d['PC_K']), int(d['PC_WAVES']), int(d['PC_DUAL']), int(d.get('PC_R0', d['PC_R'])), g('NumVgprs'), g('NumAgprs'), g('ScratchSize'),
+    return (int(d['PC_R']), int(d['PC_K']), int(d['PC_WAVES']), int(d['PC_DUAL']), int(d.get('PC_R0', d['PC_R'])), int(d.get('PC_TOP', 0)), int(d.get('PC_KUP', d['PC_K'])), g('NumVgprs'), g('NumAgprs'), g('ScratchSize'),
             g('LDSByteSize'), g('Occupancy'),
             c['v_pk_maximum3_f16'], sum(v for k, v in c.items() if k.startswith('v_')), sum(v for k, v in c.items() if k.startswith('scratch_')),
             c['v_mov_b32_e32'] + c.get('v_accvgpr_read_b32', 0) + c.get('v_accvgpr_write_b32', 0), c['s_nop'])
@@ -49,5 +50,5 @@ try:
         res = list(ex.map(run, jobs.values()))
 finally:
     shutil.rmtree(tmpd, ignore_errors=True)
-print('R K waves dual r0 vgpr agpr scratchB ldsB occupancy | fast block: max3 VALU scratch_instrs moves s_nop')
+print('R K waves dual r0 top K_up vgpr agpr scratchB ldsB occupancy | fast block: max3 VALU scratch_instrs moves s_nop')
 for r in sorted(res): print(*r)
