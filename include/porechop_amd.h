@@ -398,6 +398,26 @@ int pc_consensus_round_stranded(pc_ctx *ctx, const void *d_arena, const void *d_
                                 int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
                                 void *stream);
 
+/* pc_consensus_round_stranded (d_member_strand may be NULL) that also leaves ONE QUALITY VALUE PER CONSENSUS BYTE.
+ *   * h_qtab: 256 HOST bytes, each 0 .. 93 (Phred, not ASCII), consumed before the call returns.  d_qual: device memory laid out
+ *     exactly like d_cons -- group g starts at the same byte, and d_cons_len[g] bytes are valid.
+ *   * d_qual[byte] = h_qtab[min(margin, 255)], margin the VOTE MARGIN of the base at that byte (csrc/pc_consensus.h:
+ *     column_margin, slot_margin; integers only).  Column whose call is base b: with c the five counters as the call sees them
+ *     (the template's own vote included) and e = c, less one for the template's base when tmpl_counts == 0 (an earlier
+ *     consensus decides ties but is no evidence), margin = max(0, e[b] - max over k != b of e[k]), deletion among the k.
+ *     Insertion slot emitted with base b: with cnt its four counters and absent = d_voters[g] - their sum, margin = max(0,
+ *     cnt[b] - max(absent, max over k != b of cnt[k])).  A column where deletion leads and a slot that is not emitted have no
+ *     byte and no quality; which bases are emitted, and their order, are those of pc_consensus_round_stranded.
+ *   * PC_ERR_BAD_ARG before anything is launched: a table entry above 93, or exactly one of h_qtab and d_qual NULL.  With both
+ *     NULL the call IS pc_consensus_round_stranded: the same kernels, the same bytes.
+ *   * Slices, the scratch budget, PC_ERR_OVER_BUDGET, the error word and everything else as above. */
+int pc_consensus_round_quality(pc_ctx *ctx, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off,
+                               const int32_t *h_tmpl_len, const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off,
+                               const int32_t *d_member_len, const int32_t *d_member_group, const uint8_t *d_member_strand,
+                               int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts, uint8_t *d_cons,
+                               int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
+                               void *stream, const uint8_t *h_qtab, uint8_t *d_qual);
+
 /* Load-balancing hint for the whole-read scans of the following pc_scan_device calls: the typical
  * (mean) window length, when max_len is far above it -- real read sets are log-normal, the longest read
  * tens of times the mean.  The score pass then cuts every window into column chunks about that long,

@@ -31,7 +31,7 @@ EXPORTS = [
     "pc_scan_device_floored_flags", "pc_round_select", "pc_mask_rule_gate", "pc_mask_rule_must_realign",
     "pc_umi_extract", "pc_umi_span", "pc_readset_annotate",
     "pc_umi_neighbours", "pc_consensus_round",
-    "pc_umi_neighbours_stranded", "pc_consensus_round_stranded",
+    "pc_umi_neighbours_stranded", "pc_consensus_round_stranded", "pc_consensus_round_quality",
 ]
 
 
@@ -123,6 +123,9 @@ def load_library():
     # pc_consensus_round's arguments with d_member_strand behind d_member_group
     L.pc_consensus_round_stranded.argtypes = L.pc_consensus_round.argtypes[:10] + [c_vp] + L.pc_consensus_round.argtypes[10:]
     L.pc_consensus_round_stranded.restype = c_int
+    # pc_consensus_round_stranded's arguments, then h_qtab and d_qual
+    L.pc_consensus_round_quality.argtypes = L.pc_consensus_round_stranded.argtypes + [c_vp, c_vp]
+    L.pc_consensus_round_quality.restype = c_int
     L.pc_sync.argtypes = [c_vp, c_vp]
     L.pc_sync.restype = c_int
     L.pc_copy_windows.argtypes = [c_vp, c_vp, c_vp, c_vp, ctypes.c_int64, c_vp, c_vp, c_int, c_vp]

@@ -436,13 +436,16 @@ class Aligner:
 
     # ---- UMI consensus, one round (pc_consensus.hip, pc_consensus.h) ------------------------------------------------------
     def consensus_round(self, arena, tmpl_off, tmpl_len, member_off, member_len, member_group, band, max_err_pct, max_len=65535,
-                        tmpl_counts=1, tmpl_arena=None, return_votes=False, stream=None, member_strand=None):
+                        tmpl_counts=1, tmpl_arena=None, return_votes=False, stream=None, member_strand=None, qual_table=None):
         """One round of the UMI consensus (pc_consensus_round): every member aligned to its group's template inside `band`, the
         votes, the call.  arena: CUDA uint8 tensor holding the members (and the templates, unless tmpl_arena is given: another
         CUDA uint8 tensor).  tmpl_off int64[G], tmpl_len int32[G], member_off int64[M], member_len int32[M], member_group
         int32[M]: numpy arrays, the members ordered by group.  tmpl_counts: 1 when the template is a read of its group and
         stands for it among the voters, 0 when it is an earlier consensus.  member_strand: None, or uint8[M] (numpy) -- a member
         whose strand is 1 is read as its reverse complement (pc_consensus_round_stranded); None is pc_consensus_round itself.
+        qual_table: None, or uint8[256] (numpy; each 0 .. 93, consensus.quality_table()) -- the call is pc_consensus_round_quality,
+        and Round.qual holds one Phred value per byte of cons, gathered on the device with the index that gathers the sequences;
+        a table entry above 93 raises before anything is launched.  None: the calls above, and Round.qual is None.
         -> consensus.Round (numpy): cons the consensus bytes of all groups back to back, lens[G], status[M] (0 accepted, 1
         rejected, 2 invalid), distance[M], voters[G], and votes (a list of uint32 arrays, 21 la + 16 counters per group) when
         return_votes, else None.  Only the sequences, lengths and per-member words come back from the device.  The call syncs:
@@ -474,17 +477,27 @@ class Aligner:
         votes = torch.zeros(int(vote_off[-1]) + 16, dtype=torch.int32, device=dev) if return_votes else None
         d_off, d_len, d_grp = (torch.from_numpy(x).to(dev) if M else torch.zeros(1, dtype=torch.from_numpy(x).dtype, device=dev)
                                for x in (member_off, member_len, member_group))
+        qual = None
+        if qual_table is not None:
+            qual_table = np.ascontiguousarray(qual_table, dtype=np.uint8)
+            assert qual_table.shape == (pcc.QUAL_ENTRIES,), "a quality table is uint8[256]"
+            qual = torch.empty_like(cons)
         refused = ctypes.c_int64(-1)
         head = (self._ctx, arena.data_ptr(), tmpl_arena.data_ptr(), tmpl_off.ctypes.data, tmpl_len.ctypes.data, first.ctypes.data, G,
                 d_off.data_ptr(), d_len.data_ptr(), d_grp.data_ptr())
         tail = (M, int(band), int(max_err_pct), int(max_len), int(tmpl_counts), cons.data_ptr(), lens.data_ptr(), voters.data_ptr(),
                 out.data_ptr(), votes.data_ptr() if votes is not None else None, ctypes.byref(refused), ctypes.c_void_p(s))
-        if member_strand is None:
-            rc = self.lib.pc_consensus_round(*head, *tail)
-        else:
+        d_strand = None
+        if member_strand is not None:
             member_strand = np.ascontiguousarray(member_strand, dtype=np.uint8)
             assert member_strand.shape == (M,)
             d_strand = torch.from_numpy(member_strand).to(dev) if M else torch.zeros(1, dtype=torch.uint8, device=dev)
+        if qual is not None:
+            rc = self.lib.pc_consensus_round_quality(*head, d_strand.data_ptr() if d_strand is not None else None, *tail,
+                                                     qual_table.ctypes.data, qual.data_ptr())
+        elif d_strand is None:
+            rc = self.lib.pc_consensus_round(*head, *tail)
+        else:
             rc = self.lib.pc_consensus_round_stranded(*head, d_strand.data_ptr(), *tail)
         if rc == -6:
             raise pcc.OverBudget(int(refused.value))
@@ -497,14 +510,16 @@ class Aligner:
             starts = torch.from_numpy(cons_off[:G]).to(dev) - (torch.cumsum(d_lens, 0) - d_lens)
             at = torch.repeat_interleave(starts, d_lens) + torch.arange(total, dtype=torch.int64, device=dev)
             h_cons = cons[at].cpu().numpy()
+            h_qual = qual[at].cpu().numpy() if qual is not None else None
         else:
             h_cons = np.zeros(0, dtype=np.uint8)
+            h_qual = np.zeros(0, dtype=np.uint8) if qual is not None else None
         h_out = out[:M].cpu().numpy()
         h_votes = None
         if votes is not None:
             flat = votes.cpu().numpy().view(np.uint32)
             h_votes = [flat[vote_off[g]:vote_off[g + 1]].copy() for g in range(G)]
-        return pcc.Round(h_cons, h_lens, h_out[:, 0].copy(), h_out[:, 1].copy(), voters[:G].cpu().numpy(), h_votes)
+        return pcc.Round(h_cons, h_lens, h_out[:, 0].copy(), h_out[:, 1].copy(), voters[:G].cpu().numpy(), h_votes, h_qual)
 
     # ---- paths of middle hits (pc_paths.hip) ----------------------------------------------------------------------------
     def middle_paths_cols(self, max_len):

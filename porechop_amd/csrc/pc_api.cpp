@@ -1301,7 +1301,23 @@ int pc_consensus_round_stranded(pc_ctx *c, const void *d_arena, const void *d_tm
                                 int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
                                 void *stream_v)
 {
+    return pc_consensus_round_quality(c, d_arena, d_tmpl_arena, h_tmpl_off, h_tmpl_len, h_group_first, n_groups, d_member_off, d_member_len,
+                                      d_member_group, d_member_strand, n_members, band, max_err_pct, max_len, tmpl_counts, d_cons, d_cons_len,
+                                      d_voters, d_member_out, d_votes, refused_group, stream_v, nullptr, nullptr);
+}
+
+int pc_consensus_round_quality(pc_ctx *c, const void *d_arena, const void *d_tmpl_arena, const int64_t *h_tmpl_off,
+                               const int32_t *h_tmpl_len, const int64_t *h_group_first, int64_t n_groups, const int64_t *d_member_off,
+                               const int32_t *d_member_len, const int32_t *d_member_group, const uint8_t *d_member_strand,
+                               int64_t n_members, int band, int max_err_pct, int max_len, int tmpl_counts, uint8_t *d_cons,
+                               int32_t *d_cons_len, int32_t *d_voters, int32_t *d_member_out, uint32_t *d_votes, int64_t *refused_group,
+                               void *stream_v, const uint8_t *h_qtab, uint8_t *d_qual)
+{
     if (refused_group) *refused_group = -1;
+    if ((h_qtab == nullptr) != (d_qual == nullptr)) return PC_ERR_BAD_ARG;
+    if (h_qtab)
+        for (int m = 0; m < pcc::QUAL_ENTRIES; ++m)
+            if (h_qtab[m] > pcc::MAX_QUAL) return PC_ERR_BAD_ARG;
     if (!c || n_groups < 0 || n_members < 0 || n_groups > (int64_t)INT32_MAX || n_members > (int64_t)INT32_MAX) return PC_ERR_BAD_ARG;
     if (band < 1 || band > pcc::MAX_BAND || max_len < 1 || max_len > pcc::MAX_LEN_LIMIT) return PC_ERR_BAD_ARG;
     if (max_err_pct < 0 || max_err_pct > 100 || tmpl_counts < 0 || tmpl_counts > 1) return PC_ERR_BAD_ARG;
@@ -1378,7 +1394,15 @@ int pc_consensus_round_stranded(pc_ctx *c, const void *d_arena, const void *d_tm
         else { a.votes = c->d_cons_votes.as<uint32_t>(); a.vote_base = vote_off[s.g0]; }
         HIP_TRY(hipMemsetAsync(a.votes + (vote_off[s.g0] - a.vote_base), 0, s.votes, stream));
         if (pck::launch_consensus_pileup(a, stream)) return PC_ERR_NO_DEVICE;
-        if (pck::launch_consensus_call(a, stream)) return PC_ERR_NO_DEVICE;
+        if (!d_qual) {                                              // the call as it was: the same kernel, the same bytes
+            if (pck::launch_consensus_call(a, stream)) return PC_ERR_NO_DEVICE;
+        } else {
+            pck::ConsensusQualityArgs q;
+            q.a = a;
+            memcpy(q.qtab, h_qtab, sizeof q.qtab);
+            q.qual = d_qual;
+            if (pck::launch_consensus_call_quality(q, stream)) return PC_ERR_NO_DEVICE;
+        }
     }
     return PC_OK;
 }

@@ -29,6 +29,9 @@
 // sum of its four counters exceeds `voters`; its base is its leader, ties to the smallest code.  Output order: gap 0's slots,
 // column 0, gap 1's slots, ..., gap la's slots: at most 5 la + 4 bytes.
 //
+// QUALITY (only when the caller hands in a table of 256 Phred values).  An emitted base gets qtab[min(margin, 255)], margin its
+// votes less those of its strongest alternative: column_margin() and slot_margin() below state it, in integers.
+//
 // STRAND.  A member of strand 1 is read as its REVERSE COMPLEMENT: its base j (0-based) is the complement of the stored byte
 // lb - 1 - j -- on codes 0 <-> 3, 1 <-> 2, code 4 stays 4 (comp_code); U reads as T, whose complement is A.  member_byte() is the
 // one place that says so: the device's two refills of a member's bytes go through it, and everything downstream (DP, trace,
@@ -245,5 +248,37 @@ PCC_HD int call_slot(const uint32_t *v, uint32_t voters)
 }
 
 PCC_HD uint8_t letter(int c) { return (uint8_t)("ACGT"[c]); }
+
+// QUALITY of an emitted base: qtab[quality_index(margin)], qtab the caller's 256 Phred values (0 .. MAX_QUAL), margin the base's
+// VOTE MARGIN -- integers only; no formula is evaluated here, so host and device cannot disagree on a rounding.  A column where
+// deletion leads and a slot that is not emitted have no quality.
+constexpr int QUAL_ENTRIES = 256;
+constexpr int MAX_QUAL = 93;                      // Phred + 33 stays printable
+PCC_HD int quality_index(uint32_t margin) { return margin < (uint32_t)QUAL_ENTRIES ? (int)margin : QUAL_ENTRIES - 1; }
+
+// Column whose call is base b < 4.  v: the five counters as the call saw them, the template's own vote included.  The evidence
+// e[k] is v[k], less one for the template's code (< 4) when tmpl_counts is 0: an earlier consensus is not a read -- its vote
+// still decides ties, but it is no evidence; with tmpl_counts 1 the template is a read of the group and its vote counts.
+// margin = max(0, e[b] - max over k != b of e[k]), deletion among the k.
+PCC_HD uint32_t column_margin(const uint32_t *v, int tmpl_code, int tmpl_counts, int b)
+{
+    int64_t lead = 0, rest = 0;
+    for (int k = 0; k < 5; ++k) {
+        const int64_t e = (int64_t)v[k] - ((tmpl_counts == 0 && k == tmpl_code && tmpl_code < 4) ? 1 : 0);
+        if (k == b) lead = e;
+        else if (e > rest) rest = e;
+    }
+    return lead > rest ? (uint32_t)(lead - rest) : 0u;
+}
+
+// Slot emitted with base b.  v: the slot's four counters; absent = voters - their sum, the voters that hold no base here (never
+// negative: only accepted members vote in slots, at most once each).  margin = max(0, v[b] - max(absent, max over k != b of v[k])).
+PCC_HD uint32_t slot_margin(const uint32_t *v, uint32_t voters, int b)
+{
+    int64_t rest = (int64_t)voters - ((int64_t)v[0] + v[1] + v[2] + v[3]);
+    for (int k = 0; k < 4; ++k)
+        if (k != b && (int64_t)v[k] > rest) rest = v[k];
+    return (int64_t)v[b] > rest ? (uint32_t)((int64_t)v[b] - rest) : 0u;
+}
 
 }  // namespace pcc

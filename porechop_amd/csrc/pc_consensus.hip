@@ -31,8 +31,16 @@
 // consensus_call_kernel: one block of 256 per group.  A thread takes position p: gap p's slots, then column p (adding the
 // template's own vote to the column first); the bytes it emits (at most five, packed in a register) are placed by a block-wide
 // prefix sum, chunk after chunk of 256 positions.  It leaves voters[g] = accepted members + tmpl_counts.
+//
+// consensus_call_kernel<true>: the same call (one body; <false> is consensus_call_kernel as it was, instruction for
+// instruction) that also leaves ONE QUALITY BYTE PER EMITTED BASE.  When a thread emits a base the counters that decided it are in its registers:
+// it turns them into the base's vote margin (pcc::column_margin, pcc::slot_margin), looks the margin up in the caller's table
+// of 256 Phred values -- staged in LDS once per block, the index differs from lane to lane --, packs the up to five quality
+// bytes beside its base bytes and stores them at the same offsets of a second array.  The table and the quality pointer come in
+// an argument struct of the kernel's own (ConsensusQualityArgs): ConsensusArgs keeps its layout.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "pc_consensus.h"
 #include "pc_kernels.h"
@@ -267,11 +275,29 @@ __global__ __launch_bounds__(64) void consensus_pileup_kernel(ConsensusArgs a)
     if (status == pcc::ST_INVALID) atomicAdd(a.err, 1u);
 }
 
-__global__ __launch_bounds__(256) void consensus_call_kernel(ConsensusArgs a)
+// QUAL: the argument struct is ConsensusQualityArgs, whose table is staged in LDS first; without it the kernel is the call as it
+// was, instruction for instruction.
+template <bool QUAL>
+__global__ __launch_bounds__(256) void consensus_call_kernel(typename std::conditional<QUAL, ConsensusQualityArgs, ConsensusArgs>::type args)
 {
     __shared__ int32_t s_scan[256];
 
     const int tid = threadIdx.x;
+    const ConsensusArgs *args_a;
+    const uint8_t *s_qtab = nullptr;
+    uint8_t *qual_all = nullptr;
+    if constexpr (QUAL) {
+        __shared__ uint8_t s_table[pcc::QUAL_ENTRIES];
+        static_assert(pcc::QUAL_ENTRIES == 256, "one table entry per thread of the block");
+        s_table[tid] = args.qtab[tid];
+        __syncthreads();
+        s_qtab = s_table;
+        qual_all = args.qual;
+        args_a = &args.a;
+    } else {
+        args_a = &args;
+    }
+    const ConsensusArgs &a = *args_a;
     const int64_t g = a.first_group + blockIdx.x;
     const int la = a.tmpl_len[g];
     if (la < 1 || la > a.max_len) {
@@ -281,23 +307,32 @@ __global__ __launch_bounds__(256) void consensus_call_kernel(ConsensusArgs a)
     uint32_t *v = a.votes + (a.vote_off[g] - a.vote_base);
     const uint8_t *ta = a.tmpl_arena + a.tmpl_off[g];
     uint8_t *cons = a.cons + a.cons_off[g];
+    uint8_t *qual = QUAL ? qual_all + a.cons_off[g] : nullptr;
     const uint32_t voters = (uint32_t)(a.voters[g] + a.tmpl_counts);
     int64_t base = 0;
     for (int64_t p0 = 0; p0 <= la; p0 += 256) {
         const int64_t p = p0 + tid;
-        uint64_t bytes = 0;
+        uint64_t bytes = 0, quals = 0;
         int n = 0;
         if (p <= la) {
 #pragma unroll
             for (int s = 0; s < pcc::INS_SLOTS; ++s) {
                 const int c = pcc::call_slot(v + pcc::slot_counter(la, p, s, 0), voters);
-                if (c >= 0) { bytes |= (uint64_t)pcc::letter(c) << (8 * n); ++n; }
+                if (c >= 0) {
+                    bytes |= (uint64_t)pcc::letter(c) << (8 * n);
+                    if (QUAL) quals |= (uint64_t)s_qtab[pcc::quality_index(pcc::slot_margin(v + pcc::slot_counter(la, p, s, 0), voters, c))] << (8 * n);
+                    ++n;
+                }
             }
             if (p < la) {
                 const int tc = pcc::code(ta[p]);
                 if (tc < 4) v[pcc::col_counter(p, tc)] += 1u;          // the template's own vote: this thread is the column's only writer now
                 const int c = pcc::call_column(v + pcc::col_counter(p, 0), tc);
-                if (c < 4) { bytes |= (uint64_t)pcc::letter(c) << (8 * n); ++n; }
+                if (c < 4) {
+                    bytes |= (uint64_t)pcc::letter(c) << (8 * n);
+                    if (QUAL) quals |= (uint64_t)s_qtab[pcc::quality_index(pcc::column_margin(v + pcc::col_counter(p, 0), tc, a.tmpl_counts, c))] << (8 * n);
+                    ++n;
+                }
             }
         }
         s_scan[tid] = n;
@@ -310,6 +345,8 @@ __global__ __launch_bounds__(256) void consensus_call_kernel(ConsensusArgs a)
         }
         const int64_t at = base + s_scan[tid] - n;
         for (int t = 0; t < n; ++t) cons[at + t] = (uint8_t)(bytes >> (8 * t));
+        if (QUAL)
+            for (int t = 0; t < n; ++t) qual[at + t] = (uint8_t)(quals >> (8 * t));
         base += s_scan[255];
         __syncthreads();
     }
@@ -346,7 +383,15 @@ int launch_consensus_pileup(const ConsensusArgs &a, void *stream)
 int launch_consensus_call(const ConsensusArgs &a, void *stream)
 {
     if (a.n_groups <= 0) return 0;
-    hipLaunchKernelGGL(consensus_call_kernel, dim3((unsigned)a.n_groups), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(consensus_call_kernel<false>, dim3((unsigned)a.n_groups), dim3(256), 0, (hipStream_t)stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int launch_consensus_call_quality(const ConsensusQualityArgs &q, void *stream)
+{
+    if (q.a.n_groups <= 0) return 0;
+    if (!q.qual) return 1;
+    hipLaunchKernelGGL(consensus_call_kernel<true>, dim3((unsigned)q.a.n_groups), dim3(256), 0, (hipStream_t)stream, q);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

@@ -514,4 +514,13 @@ struct ConsensusArgs {
 int launch_consensus_pileup(const ConsensusArgs &a, void *stream);
 int launch_consensus_call(const ConsensusArgs &a, void *stream);
 
+// consensus_call_quality_kernel: consensus_call_kernel that also writes one quality byte per emitted base (pc_consensus.h:
+// column_margin, slot_margin).  An argument struct of its own, so that ConsensusArgs keeps its layout.
+struct ConsensusQualityArgs {
+    ConsensusArgs a;
+    uint8_t qtab[256];           // Phred value by vote margin (0 .. 93 each), by value: consumed at the launch
+    uint8_t *qual;               // laid out like a.cons: group g's bytes start at a.cons_off[g], cons_len[g] of them are valid
+};
+int launch_consensus_call_quality(const ConsensusQualityArgs &q, void *stream);
+
 }  // namespace pck

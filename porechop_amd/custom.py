@@ -21,6 +21,11 @@ command line of `python -m porechop_amd` (the reference's option set, unchanged 
                      (3), --umi_consensus_max_reads N (256), --umi_consensus_band N (64), --umi_consensus_rounds N (2),
                      --umi_consensus_max_err_pct N (30), --umi_consensus_max_len N (65535).  The reads stay resident: the input
                      is not streamed.
+  --umi_consensus_fastq PATH  (with --umi; alone or beside --umi_consensus) the same records as FASTQ with one quality value per
+                     base: the Phred value of the base's vote margin -- its votes less those of the strongest alternative --
+                     from a table built for --umi_consensus_vote_err_pct N (1..50, default 10: each vote wrong with that
+                     probability, independently) and capped at --umi_consensus_max_qual N (1..93, default 60).  The report gains
+                     the columns expected_errors and low_qual (bases below Q10).
   --umi_strands      (with --umi, --umi_groups or --umi_consensus, and START+END keys) both strands of a molecule are one group: a
                      read of the minus strand shows the key START+END as rc(END)+rc(START), so keys are compared as they stand
                      and mirrored, the groups TSV gains a strand column (+ / -), and the consensus piles the - reads up as
@@ -54,6 +59,10 @@ def build_custom_parser(prog="porechop_amd.custom"):
     p.add_argument("--umi_consensus_rounds", type=int, default=2, help="rounds: a round's consensus is the next one's template (default: 2)")
     p.add_argument("--umi_consensus_max_err_pct", type=int, default=30, help="a member further than this from the template sits the round out (default: 30)")
     p.add_argument("--umi_consensus_max_len", type=int, default=65535, help="groups whose template is longer get no sequence (default: 65535)")
+    p.add_argument("--umi_consensus_fastq", metavar="PATH", help="the consensus sequences as FASTQ, one quality value per base from its vote margin (needs --umi)")
+    p.add_argument("--umi_consensus_vote_err_pct", type=int, default=None,
+                   help="the quality table's model: each vote is wrong with this probability in percent, 1..50 (default: 10; needs --umi_consensus_fastq)")
+    p.add_argument("--umi_consensus_max_qual", type=int, default=None, help="the highest quality value written, 1..93 (default: 60; needs --umi_consensus_fastq)")
     p.add_argument("--umi_strands", action="store_true",
                    help="group and call across both strands of a molecule: a key START+END also matches its mirror rc(END)+rc(START) "
                         "(needs --umi, --umi_groups or --umi_consensus, and keys of both sides)")
@@ -101,7 +110,13 @@ def main(argv=None):
     if a.umi_groups is not None:
         kw.update(umi=a.umi, umi_groups=a.umi_groups, umi_group_by=a.umi_group_by, umi_max_dist=a.umi_max_dist,
                   umi_group_method=a.umi_group_method, umi_group_max_keys=a.umi_group_max_keys)
-    if a.umi_consensus is not None or a.umi_consensus_report is not None:
+    if a.umi_consensus_fastq is None and (a.umi_consensus_vote_err_pct is not None or a.umi_consensus_max_qual is not None):
+        sys.exit("Error: --umi_consensus_vote_err_pct and --umi_consensus_max_qual need --umi_consensus_fastq")
+    if a.umi_consensus is not None or a.umi_consensus_report is not None or a.umi_consensus_fastq is not None:
+        if a.umi_consensus_fastq is not None:
+            kw.update(umi_consensus_fastq=a.umi_consensus_fastq,
+                      umi_consensus_vote_err_pct=10 if a.umi_consensus_vote_err_pct is None else a.umi_consensus_vote_err_pct,
+                      umi_consensus_max_qual=60 if a.umi_consensus_max_qual is None else a.umi_consensus_max_qual)
         kw.update(umi=a.umi, umi_consensus=a.umi_consensus, umi_consensus_report=a.umi_consensus_report,
                   umi_group_by=a.umi_group_by, umi_max_dist=a.umi_max_dist, umi_group_method=a.umi_group_method,
                   umi_group_max_keys=a.umi_group_max_keys, umi_consensus_min_reads=a.umi_consensus_min_reads,

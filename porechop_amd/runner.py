@@ -80,7 +80,8 @@ class RunResult:
     # run(..., umi_groups=PATH): per read None (no key) or (group id from 1, the group's representative key)
     umi_groups: Optional[List[Optional[tuple]]] = None
     # run(..., umi_consensus=PATH): one dict per group, in group order (porechop_amd.consensus.call_groups): group,
-    # representative, members, used, rejected, skipped, rounds, length, status, sequence (bytes; None unless status is "called")
+    # representative, members, used, rejected, skipped, rounds, length, status, sequence (bytes; None unless status is "called");
+    # with umi_consensus_fastq=PATH also quality (bytes of Phred values, one per base of sequence; None without a sequence)
     consensus: Optional[List[dict]] = None
 
 
@@ -469,15 +470,25 @@ def _group_umis(path, umis, names, pl, by, max_dist, method, max_keys, strands=F
 CONSENSUS_OPTIONS = ("min_reads", "max_reads", "band", "rounds", "max_err_pct", "max_len")
 
 
-def _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, values):
-    """The refusals of run(umi_consensus=PATH) that need no panel; values: the six numeric options in CONSENSUS_OPTIONS' order."""
+QUALITY_DEFAULTS = dict(vote_err_pct=10, max_qual=60)
+
+
+def _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, values, fastq=None, vote_err_pct=10, max_qual=60):
+    """The refusals of run(umi_consensus=PATH) and run(umi_consensus_fastq=PATH) that need no panel; values: the six numeric
+    options in CONSENSUS_OPTIONS' order."""
     from . import consensus as cs
-    if umi_consensus_report is not None and umi_consensus is None:
-        raise UsageError("Error: --umi_consensus_report needs --umi_consensus")
-    if umi_consensus is None:
+    if umi_consensus_report is not None and umi_consensus is None and fastq is None:
+        raise UsageError("Error: --umi_consensus_report needs --umi_consensus or --umi_consensus_fastq")
+    if fastq is None and (vote_err_pct != QUALITY_DEFAULTS["vote_err_pct"] or max_qual != QUALITY_DEFAULTS["max_qual"]):
+        raise UsageError("Error: --umi_consensus_vote_err_pct and --umi_consensus_max_qual need --umi_consensus_fastq")
+    if umi_consensus is None and fastq is None:
         return
     if not umi:
-        raise UsageError("Error: --umi_consensus needs --umi")
+        raise UsageError("Error: --umi_consensus%s needs --umi" % ("" if umi_consensus is not None else "_fastq"))
+    if fastq is not None:
+        for name, v, hi in (("vote_err_pct", vote_err_pct, 50), ("max_qual", max_qual, cs.MAX_QUAL)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= int(v) <= hi:
+                raise UsageError("Error: --umi_consensus_%s must be a whole number in 1..%d" % (name, hi))
     if sharded:
         raise UsageError("Error: the UMI consensus is not available in a sharded run (one process per GPU): run it in a single process")
     try:
@@ -488,10 +499,11 @@ def _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, shard
         raise UsageError("Error: --umi_consensus_%s %s" % bad)
 
 
-def _consensus(fasta, report, res, rs, reads, pr, num, pl, values, strands=False):
+def _consensus(fasta, report, res, rs, reads, pr, num, pl, values, strands=False, fastq=None, qual_table=None):
     """run(umi_consensus=PATH) after the piece plan: the groups' members (reads written as exactly one piece), the rounds over
-    the arena _upload made -- on the library when the aligner has consensus_round, in numpy otherwise -- and the two files ->
-    RunResult.consensus."""
+    the arena _upload made -- on the library when the aligner has consensus_round, in numpy otherwise -- and the files ->
+    RunResult.consensus.  fastq / qual_table (run(umi_consensus_fastq=PATH)): the rounds also leave a quality per base, the
+    rows carry `quality`, PATH gets the FASTQ and the report its two quality columns."""
     from . import consensus as cs
     lengths = np.asarray(rs.lengths, dtype=np.int64)
     groups = cs.members(res.umi_groups, lengths, res.start_trim, res.end_trim, pr, num)
@@ -499,11 +511,16 @@ def _consensus(fasta, report, res, rs, reads, pr, num, pl, values, strands=False
     seq_len = np.maximum(lengths - np.asarray(res.end_trim, dtype=np.int64) - np.asarray(res.start_trim, dtype=np.int64), 0)
     written = []
     strand_kw = dict(read_strand=[0 if e is None else int(e[2]) for e in res.umi_groups]) if strands else {}
+    report_kw = dict(minus=True) if strands else {}
+    if qual_table is not None:
+        strand_kw["qual_table"] = qual_table
+        report_kw["quality"] = True
     try:
         out = cs.call_groups(groups, rs.arena, seq_off, seq_len, *[int(v) for v in values], aligner=pl.aligner,
                              dev_arena=reads.arena if reads is not None else None, device=pl.device, **strand_kw)
-        for path, text in ((fasta, cs.fasta_text(out)), (report, cs.report_text(out, minus=True) if strands else cs.report_text(out))):
+        for path, text in ((fasta, cs.fasta_text), (fastq, cs.fastq_text), (report, lambda rows: cs.report_text(rows, **report_kw))):
             if path is not None:
+                text = text(out)
                 written.append(path)
                 with open(path, "w") as fh:
                     fh.write(text)
@@ -819,7 +836,7 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
                  report_paths: bool = False, report_middle_paths: bool = False, wildcards: bool = False, umi: bool = False,
                  umi_report: str = None, umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2,
                  umi_group_method: str = "directional", umi_group_max_keys: int = 1 << 20, umi_consensus: str = None,
-                 umi_strands: bool = False) -> Optional[RunResult]:
+                 umi_strands: bool = False, umi_consensus_fastq: str = None) -> Optional[RunResult]:
     """run() for a plain FASTQ file as a STREAM of blocks: a loader thread parses block k+1 (pc_readset_load_segment,
     all host cores) while block k is uploaded and scanned on the GPU and a writer thread formats and writes block k-1
     (pc_readset_write_at) -- host memory holds three blocks instead of the input, and ingest, scan and writing overlap.
@@ -834,8 +851,9 @@ def run_streamed(input_path, output, barcode_dir, opts: Options, device=None, al
     without the check reads): the caller loads the whole file."""
     import queue
     import threading
-    if umi_consensus is not None:
-        raise UsageError("Error: --umi_consensus is not available in a streamed run: the reads must stay resident; use run()")
+    if umi_consensus is not None or umi_consensus_fastq is not None:
+        raise UsageError("Error: --umi_consensus%s is not available in a streamed run: the reads must stay resident; use run()" % (
+            "" if umi_consensus is not None else "_fastq"))
     _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
     _check_umi_strand_options(umi, umi_strands, umi_groups is not None, umi_group_by)
     block_bytes = block_bytes or _stream_block_bytes()
@@ -1246,7 +1264,8 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         umi_groups: str = None, umi_group_by: str = None, umi_max_dist: int = 2, umi_group_method: str = "directional",
         umi_group_max_keys: int = 1 << 20, umi_consensus: str = None, umi_consensus_report: str = None,
         umi_consensus_min_reads: int = 3, umi_consensus_max_reads: int = 256, umi_consensus_band: int = 64, umi_consensus_rounds: int = 2,
-        umi_consensus_max_err_pct: int = 30, umi_consensus_max_len: int = 65535, umi_strands: bool = False) -> RunResult:
+        umi_consensus_max_err_pct: int = 30, umi_consensus_max_len: int = 65535, umi_strands: bool = False,
+        umi_consensus_fastq: str = None, umi_consensus_vote_err_pct: int = 10, umi_consensus_max_qual: int = 60) -> RunResult:
     """Porechop's main() on arrays.  output=None and barcode_dir=None writes to stdout.
     `aligner` is for tests only (see Pipeline).
 
@@ -1299,6 +1318,13 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     consensus_round), so with umi_consensus given run() takes this plain driver whatever the input's size: the reads must be
     resident.  Not available in run_streamed or in a sharded run.  Off, every byte and every launch is what it was.
 
+    umi_consensus_fastq=PATH (with umi=True; alone or beside umi_consensus, either one makes the consensus run) writes the same
+    records as FASTQ, with ONE QUALITY VALUE PER BASE: the Phred value that consensus.quality_table(umi_consensus_vote_err_pct,
+    umi_consensus_max_qual) gives the base's vote margin -- its votes less those of the strongest alternative (DESIGN.md section
+    18; Aligner.consensus_round(qual_table=...)).  RunResult.consensus rows then carry `quality` (bytes of Phred values) and
+    the report two more columns, expected_errors and low_qual.  umi_consensus_vote_err_pct (1..50, default 10) and
+    umi_consensus_max_qual (1..93, default 60) are choices, not measurements; a value other than the default without
+    umi_consensus_fastq is a UsageError.
     umi_strands=True (with umi=True, umi_groups or umi_consensus, and START+END keys: umi_group_by "both" or None on a panel with
     degenerate letters on both sides) groups and calls ACROSS BOTH STRANDS of a molecule (DESIGN.md sections 17 and 18).  A read of
     the minus strand shows the key START+END as rc(END)+rc(START), its mirror; the panel must list the UMI adapter in both
@@ -1345,10 +1371,12 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
     _check_umi_group_options(umi, umi_groups, umi_group_by, umi_max_dist, umi_group_method)
     consensus_values = (umi_consensus_min_reads, umi_consensus_max_reads, umi_consensus_band, umi_consensus_rounds, umi_consensus_max_err_pct,
                         umi_consensus_max_len)
-    _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, consensus_values)
-    if umi_consensus is not None and umi_groups is None:         # the groups are made all the same; only the TSV is not written
+    _check_umi_consensus_options(umi, umi_consensus, umi_consensus_report, sharded, consensus_values, umi_consensus_fastq,
+                                 umi_consensus_vote_err_pct, umi_consensus_max_qual)
+    consensing = umi_consensus is not None or umi_consensus_fastq is not None
+    if consensing and umi_groups is None:         # the groups are made all the same; only the TSV is not written
         _check_umi_group_options(umi, "", umi_group_by, umi_max_dist, umi_group_method)
-    grouping = umi_groups is not None or umi_consensus is not None
+    grouping = umi_groups is not None or consensing
     _check_umi_strand_options(umi, umi_strands, grouping, umi_group_by)
     group_kw = {} if umi_groups is None else dict(umi_groups=umi_groups, umi_group_by=umi_group_by, umi_max_dist=umi_max_dist,
                                                   umi_group_method=umi_group_method, umi_group_max_keys=umi_group_max_keys)
@@ -1356,7 +1384,7 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         group_kw["umi_strands"] = True
     # (a .gz file holds about three times its size in FASTQ)
     if (os.path.isfile(input_path) and os.path.getsize(input_path) * (3 if _is_gzip(input_path) else 1) > 2 * _stream_block_bytes()
-            and not sharded and umi_consensus is None):
+            and not sharded and not consensing):
         streamed = run_streamed(input_path, output, barcode_dir, opts, device=device, aligner=aligner, adapter_panel=adapter_panel,
                                 report=report, report_paths=report_paths, report_middle_paths=report_middle_paths, wildcards=wildcards,
                                 umi=umi, umi_report=umi_report, **group_kw)
@@ -1448,11 +1476,16 @@ def run(input_path, output=None, barcode_dir=None, options: Options = None, devi
         res.out_format = fmt
         pr, ps_, pn_, num, read_bases, n_split = _plan_pieces(opts, barcode_dir, rs.lengths, sc, matching, pl, match_idx)
         res.middle_hit_reads = n_split
-        if umi_consensus is not None:
+        if consensing:
             lap("plan_output")
             try:
+                quality_kw = {}
+                if umi_consensus_fastq is not None:
+                    from . import consensus as cs
+                    quality_kw = dict(fastq=umi_consensus_fastq,
+                                      qual_table=cs.quality_table(int(umi_consensus_vote_err_pct), int(umi_consensus_max_qual)))
                 res.consensus = _consensus(umi_consensus, umi_consensus_report, res, rs, reads, pr, num, pl, consensus_values,
-                                           bool(umi_strands))
+                                           bool(umi_strands), **quality_kw)
             except Exception:                                    # nothing of this run is left behind
                 for path in (umi_report, umi_groups, report):
                     if path is not None and os.path.isfile(path):
